@@ -1,9 +1,13 @@
 """Benchmark: Msamples/s of the srr HIP path tracer on BASELINE.json's config
 (Cornell box + Utah teapot, 6,400 triangles, 512x512, 1024 spp, MI355X).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \\
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds the legs that take runs of their own (the CPU baseline of the same
+frame); --dump-outputs DIR writes the last timed step's frame to DIR/frame.npy.
 
 One step = one whole frame through the C-ABI (srr_render_device, inputs
 resident in HBM) on every rank, then the frame-end exchange over RCCL
@@ -65,7 +69,15 @@ def parse():
                     help="one frame at a time (srr_render_device) instead of two in flight "
                          "(srr_render_device_async: frame k+1's persistent blocks start on the CUs frame k's last "
                          "paths free, and frame k's exchange runs while frame k+1 renders)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the CPU baseline of the same frame "
+                         "(cpu_baseline in the result line, --cpu-seconds of host time; --no-cpu-baseline drops it)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step returned to its caller: DIR/frame.npy (the "
+                         "assembled frame's per-pixel means, float32 [nx*ny, 3]; a fixed seeded sample of its "
+                         "pixels when the frame exceeds 64 MB) and DIR/world_rays.npy (rank 0's world ray count "
+                         "of that step, float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--count-visits", action="store_true", help="diagnostic: count mesh box/triangle tests (slower)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--force-dist", action="store_true",
@@ -211,6 +223,24 @@ def _lib_sha256(path):
         return None
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, frame, world_rays):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files
+    under d.  frame: the assembled [nx*ny, 3] float32 means; when it exceeds
+    DUMP_MAX_BYTES, a fixed seeded sample of its pixels (ascending) that fits."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    budget = DUMP_MAX_BYTES - 4096  # the world ray count and the .npy headers
+    if frame.nbytes > budget:
+        n = budget // (frame.nbytes // frame.shape[0])
+        frame = frame[np.sort(np.random.default_rng(0).choice(frame.shape[0], size=n, replace=False))]
+    np.save(os.path.join(d, "frame.npy"), frame)
+    np.save(os.path.join(d, "world_rays.npy"), np.array([world_rays], dtype=np.float64))
+
+
 def bench_line(a, text, cfg, nx, ny, spp, rays_total, elapsed, trace_ms, launches, world, workload_tail,
                parallelism, extra, rays_local=None, frame_spp=None, visits=None):
     """The JSON line (rank 0): value = every device's world rays over the slowest
@@ -338,7 +368,7 @@ def bench_line(a, text, cfg, nx, ny, spp, rays_total, elapsed, trace_ms, launche
     if a.count_visits:
         out["visits"] = {"box_tests_per_ray": visits[0] / max(rays, 1), "tri_tests_per_ray": visits[1] / max(rays, 1),
                          "stack_overflows": visits[2], "note": "counting run: timing not representative"}
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         # the reference's own code when its harness was built (oracle/_ref), else the
         # bit-exact restatement; the two are different harnesses (processes vs threads),
         # so neither calibrates the other
@@ -385,6 +415,8 @@ def bench_capi(a, rend, devices, text, sc, cfg, nx, ny, spp, dev, n_dev):
     if a.save_frame:
         import numpy as np
         np.save(a.save_frame, bufs[(a.steps - 1) % len(bufs)].cpu().numpy())
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, bufs[(a.steps - 1) % len(bufs)].cpu().numpy(), sts[-1]["world_rays"])
     out = bench_line(a, text, cfg, nx, ny, spp, rays, elapsed, trace_ms, launches, world=a.gpus,
                      workload_tail=(f", {a.tile}x{a.tile} tiles round-robin over {a.gpus} devices of ONE process "
                                     f"(srr_renderer_create_multi), one {rend.transport.upper()} gather to device 0"
@@ -508,6 +540,7 @@ def main():
     for st in run_frames(a.steps):
         visits = [visits[0] + st["box_tests"], visits[1] + st["tri_tests"], visits[2] + st["stack_overflows"]]
         rays += st["world_rays"]
+        last_rays = st["world_rays"]
         trace_ms += st["trace_ms"]
         launches += st["trace_launches"]
     barrier()
@@ -526,6 +559,8 @@ def main():
     if rank == 0 and a.save_frame:
         import numpy as np
         np.save(a.save_frame, frame[0].cpu().numpy())
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, frame[0].cpu().numpy(), last_rays)
     if rank == 0:
         coll = "RCCL" if backend == "nccl" else "host-staged gloo"
         tail = ((f", {a.tile}x{a.tile} tiles round-robin over {world} GPUs, one {coll} gather to rank 0 at frame end"

@@ -3,7 +3,7 @@ chunked sample ranges accumulate in sample order, so any chunking -- including
 a save in one renderer and a resume in a fresh one -- is bitwise the one-shot
 image; and the PPM writer reproduces the reference's own output files byte for
 byte (Raytracing_n.cpp:873-886)."""
-import glob
+import hashlib
 import os
 
 import numpy as np
@@ -11,6 +11,8 @@ import pytest
 
 from srr import capi, scenes
 from srr.progressive import Progressive
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def test_accum_symbols_exported():
@@ -28,14 +30,21 @@ def _read_ppm(path):
     return nx, ny, np.array([int(t) for t in tok[4:4 + 3 * nx * ny]], np.uint8).reshape(-1, 3)
 
 
-@pytest.mark.parametrize("path", sorted(glob.glob("/root/reference/results/*.ppm"))[:2] or ["missing"])
-def test_ppm_writer_matches_reference_outputs(path, tmp_path):
-    if not os.path.exists(path):
-        pytest.skip("reference results not present")
-    nx, ny, px = _read_ppm(path)
+@pytest.mark.parametrize("name", ["20191108_soldier", "20191108_soldier_sky2"])
+def test_ppm_writer_matches_reference_outputs(name, tmp_path):
+    """Two of the reference's own result files (tests/golden/make_ppm.py: their
+    pixels, length and SHA-256): written from the pixels, the file is the
+    reference's byte for byte, and reads back as the same pixels."""
+    fx = np.load(os.path.join(GOLDEN, f"ppm_{name}.npz"))
+    nx, ny, px = int(fx["nx"]), int(fx["ny"]), fx["pixels"]
     out = tmp_path / "o.ppm"
     capi.write_ppm(str(out), nx, ny, px)
-    assert out.read_bytes() == open(path, "rb").read()
+    got = out.read_bytes()
+    assert len(got) == int(fx["nbytes"])
+    assert hashlib.sha256(got).hexdigest() == str(fx["sha256"])
+    rnx, rny, rpx = _read_ppm(str(out))
+    assert (rnx, rny) == (nx, ny)
+    np.testing.assert_array_equal(rpx, px)
 
 
 @pytest.mark.gpu

@@ -22,7 +22,7 @@ for c in FETCH_SIZE WRITE_SIZE; do
 done
 python $R/tools/pmc_traffic.py $O/$TAG.pmc_FETCH_SIZE $O/$TAG.pmc_WRITE_SIZE k_paths $O/$TAG.pmc_$SCENE.json || exit 1
 cd $R
-timeout -k 10 600 python bench.py --scene $SCENE > $O/$TAG.bench.log 2>&1 || { tail -5 $O/$TAG.bench.log; exit 1; }
+timeout -k 10 600 python bench.py --full --scene $SCENE > $O/$TAG.bench.log 2>&1 || { tail -5 $O/$TAG.bench.log; exit 1; }
 grep '^{' $O/$TAG.bench.log | cut -c1-300
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/$TAG.prof -o run --output-format csv -- \

@@ -33,7 +33,7 @@ CFG
     rc=$?; echo "tests rc=$rc"; tail -1 $O/r04final.tests.log; [ $rc -eq 0 ] || exit 1
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/r04final.smoke.log 2>&1 || { tail -5 $O/r04final.smoke.log; exit 1; }
     tail -1 $O/r04final.smoke.log
-    timeout -k 10 600 python bench.py > $O/r04final.bench.log 2>&1 || { tail -5 $O/r04final.bench.log; exit 1; }
+    timeout -k 10 600 python bench.py --full > $O/r04final.bench.log 2>&1 || { tail -5 $O/r04final.bench.log; exit 1; }
     grep '^{' $O/r04final.bench.log | cut -c1-200
     cd /tmp && export TMPDIR=/tmp
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/r04final.prof -o run --output-format csv -- \

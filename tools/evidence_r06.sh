@@ -22,7 +22,7 @@ case "$1" in
     rc=$?; echo "tests rc=$rc"; tail -1 $O/r06final.tests.log; [ $rc -eq 0 ] || exit 1
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/r06final.smoke.log 2>&1 || { tail -5 $O/r06final.smoke.log; exit 1; }
     tail -1 $O/r06final.smoke.log
-    timeout -k 10 600 python bench.py > $O/r06final.bench.log 2>&1 || { tail -5 $O/r06final.bench.log; exit 1; }
+    timeout -k 10 600 python bench.py --full > $O/r06final.bench.log 2>&1 || { tail -5 $O/r06final.bench.log; exit 1; }
     grep '^{' $O/r06final.bench.log | cut -c1-200
     cd /tmp && export TMPDIR=/tmp
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/r06final.prof -o run --output-format csv -- \

@@ -9,7 +9,7 @@ timeout -k 10 900 python -u -m pytest -x -q --timeout 300 --timeout-method threa
 rc=$?; echo "tests rc=$rc"; tail -1 $O/$TAG.tests.log; [ $rc -eq 0 ] || exit 1
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/$TAG.smoke.log 2>&1 || { tail -5 $O/$TAG.smoke.log; exit 1; }
 tail -1 $O/$TAG.smoke.log
-timeout -k 10 600 python bench.py > $O/$TAG.bench.log 2>&1 || { tail -5 $O/$TAG.bench.log; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/$TAG.bench.log 2>&1 || { tail -5 $O/$TAG.bench.log; exit 1; }
 grep '^{' $O/$TAG.bench.log | cut -c1-200
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/$TAG.prof -o run --output-format csv -- \
