@@ -25,6 +25,13 @@
  *                                one device still goes through the RCCL gather)
  *   --dry-run                    build the scene and print its digest
  *                                (srr_scene_digest), no GPU
+ *   --adaptive REL_TOL           adaptive sampling (srr_render_adaptive, one GPU):
+ *                                --ns is the per-pixel budget; a pixel stops once
+ *                                the relative standard error of its mean luminance
+ *                                is at most REL_TOL
+ *   --batch-spp 16 --min-spp 16  its samples per pass / fewest samples per pixel
+ *   --count-map FILE             its per-pixel sample counts as a PNG of grey
+ *                                levels 255 * count / ns
  * Differences, all forced by the reference: its render threads race on shared
  * state and its pixel mapping scrambles non-square frames (Q12);
  * srr renders every (pixel, sample) path with its per-path seed.  Exit codes:
@@ -59,9 +66,13 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
   std::vector<int> devices;
   std::string name, out = "out.ppm", text_path;
   bool dry = false;
+  double adaptive = -1;  // --adaptive REL_TOL (< 0: fixed spp)
+  int batch_spp = 16, min_spp = 16;
+  std::string count_map;
   auto usage = [&]() {
     std::fprintf(stderr, "usage: %s [--sceneid N | --scene NAME] [--nx N] [--ny N] [--ns N] [--max-depth N] "
-                         "[--device N] [--gpus N | --devices a,b,..] [--tile N] [--out FILE] [--dry-run]\nscenes:",
+                         "[--device N] [--gpus N | --devices a,b,..] [--tile N] [--out FILE] [--dry-run] "
+                         "[--adaptive REL_TOL [--batch-spp N] [--min-spp N] [--count-map FILE]]\nscenes:",
                  argv[0]);
     for (int k = 0; k < n_scenes; ++k) std::fprintf(stderr, " %d:%s", scenes[k].sceneid, scenes[k].name);
     std::fprintf(stderr, "\n");
@@ -92,6 +103,10 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
     }
     else if (a == "--out" && i + 1 < argc) out = argv[++i];
     else if (a == "--dry-run") dry = true;
+    else if (a == "--adaptive" && i + 1 < argc) ok = (adaptive = std::atof(argv[++i])) >= 0;
+    else if (a == "--batch-spp") ok = num(batch_spp) && batch_spp >= 1;
+    else if (a == "--min-spp") ok = num(min_spp) && min_spp >= 1;
+    else if (a == "--count-map" && i + 1 < argc) count_map = argv[++i];
     else ok = false;
     if (!ok) return usage();
   }
@@ -99,6 +114,7 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
   for (int k = 0; k < n_scenes; ++k)
     if (name.empty() ? scenes[k].sceneid == sceneid : name == scenes[k].name) e = &scenes[k];
   if ((!e && text_path.empty()) || nx < 1 || ny < 1 || ns < 1) return usage();
+  if (adaptive < 0 && !count_map.empty()) return usage();
   const char* scene_name = text_path.empty() ? e->name : text_path.c_str();
 
   srr_scene* s = nullptr;
@@ -158,9 +174,36 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
   std::vector<unsigned char> rgb8(3 * (size_t)nx * ny);
   srr_stats st{};
   const auto t0 = std::chrono::steady_clock::now();
-  int rc = srr_render(r, &p, nullptr, rgb8.data(), &st);
+  int rc;
+  srr_adaptive_stats ast{};
+  std::vector<int32_t> count;
+  if (adaptive >= 0) {
+    srr_adaptive_params ap{};
+    ap.struct_size = sizeof ap;
+    ap.batch_spp = batch_spp;
+    ap.min_spp = min_spp;
+    ap.rel_tol = (float)adaptive;
+    ap.abs_eps = 1e-3f;
+    ast.struct_size = sizeof ast;
+    count.resize((size_t)nx * ny);
+    rc = srr_render_adaptive_host(r, &p, &ap, nullptr, count.data(), rgb8.data(), &ast);
+    st.world_rays = ast.world_rays;
+  } else {
+    rc = srr_render(r, &p, nullptr, rgb8.data(), &st);
+  }
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (rc == 0) rc = srr_write_ppm(out.c_str(), nx, ny, rgb8.data());
+  if (rc == 0 && !count_map.empty()) {  // grey level 255 * count / ns, rounded down
+    std::vector<unsigned char> grey(3 * count.size());
+    for (size_t i = 0; i < count.size(); ++i) {
+      const long long g = (long long)count[i] * 255 / ns;
+      grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = (unsigned char)(g < 0 ? 0 : g > 255 ? 255 : g);
+    }
+    rc = srr_write_png(count_map.c_str(), nx, ny, grey.data());
+  }
+  if (rc == 0 && adaptive >= 0)
+    std::fprintf(stderr, "adaptive: %lld of %lld samples in %d passes, %lld pixels stopped early\n",
+                 (long long)ast.paths, (long long)nx * ny * ns, (int)ast.passes, (long long)ast.pixels_retired);
   if (rc < 0) std::fprintf(stderr, "%s\n", srr_last_error());
   else {
     std::printf("%dms\n", (int)ms);  // :934-937

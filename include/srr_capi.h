@@ -252,6 +252,68 @@ int srr_render_wait(srr_renderer* r, int64_t ticket, srr_stats* stats);
  * (the whole image when shard_count <= 1) as mean radiance (npix*3, may be NULL)
  * and 8-bit tone-mapped rgb8 (npix*3, Raytracing_n.cpp:850-867, may be NULL). */
 int srr_render(srr_renderer* r, const srr_params* p, float* mean, unsigned char* rgb8, srr_stats* stats);
+/* ---- Adaptive sampling (no reference counterpart: the reference gives every
+ * pixel ns samples, Raytracing_n.cpp:41).  The frame is rendered in passes; in
+ * each pass every still-active pixel receives w = min(batch_spp, p->spp - n)
+ * samples with the global sample indices [n, n + w), n being the samples it holds
+ * (the same for every active pixel: pixels only ever retire).  After a pass a
+ * pixel retires when n reached the budget p->spp, or when n >= min_spp,
+ * rel_tol > 0 and the convergence rule below holds; the frame ends when no pixel
+ * is active.  A pixel that ends with n_i samples holds bitwise the value a
+ * fixed-spp frame of spp = n_i gives it.
+ *
+ * Convergence rule.  Per sample (after de_nan) the luminance is
+ *   y = (0.2126f*r + 0.7152f*g) + 0.0722f*b          (Rec. 709 weights)
+ * and the pixel keeps s1 += y, s2 += y*y, folded in sample order in float32.
+ * With nf = (float)n the pixel is converged iff, every operation in float32,
+ * evaluated in exactly this order and without fused multiply-add,
+ *   (s2*nf - s1*s1) <= ((rel_tol*rel_tol) * (nf - 1.0f)) * ((s1 + abs_eps*nf) * (s1 + abs_eps*nf))
+ * Origin (nothing of it is the reference's): the standard error of the mean of n
+ * samples is sem = sqrt(var / n) with the unbiased var = (s2 - s1*s1/n) / (n - 1);
+ * the test sem <= rel_tol * (mean + abs_eps), mean = s1/n, squared and multiplied
+ * through by n*n*(n - 1), is the inequality above: no division, no square root.
+ * rel_tol = 0 never retires a pixel early (the rule itself holds for a pixel of
+ * zero variance, so the pass loop does not ask it then).  Early stopping biases
+ * dark pixels lit by rare events: min_spp is the guard. */
+typedef struct srr_adaptive_params {
+  uint32_t struct_size; /* sizeof(srr_adaptive_params) of the caller              */
+  int batch_spp;        /* samples every still-active pixel receives per pass, >= 1 */
+  int min_spp;          /* no pixel retires with fewer samples than this, >= 1    */
+  float rel_tol;        /* target relative standard error of the pixel's mean     */
+                        /*   luminance; 0 = never retire                          */
+  float abs_eps;        /* luminance floor added to the mean in the test, >= 0    */
+} srr_adaptive_params;
+
+typedef struct srr_adaptive_stats {
+  uint32_t struct_size;    /* sizeof(srr_adaptive_stats) of the caller (set before the call) */
+  int32_t passes;          /* k_paths passes actually launched                    */
+  int64_t paths;           /* camera paths traced = sum of the per-pixel counts   */
+  int64_t world_rays;
+  int64_t pixels_retired;  /* pixels that met the tolerance before the budget     */
+  double total_ms;
+} srr_adaptive_stats;
+
+/* Render this shard adaptively: p->spp is the per-pixel budget, p->sample_begin
+ * must be 0.  d_mean: DEVICE pointer, n_shard_pixels*3 floats, pixel i's mean over
+ * its own n_i samples (sum * (float)(1.0 / (float)n_i), the division of a
+ * fixed-spp frame); d_count: DEVICE pointer, n_shard_pixels int32 (n_i), may be
+ * NULL; both in srr_shard_pixels() order.  Synchronous, one device, path engine
+ * only: SRR_EINVAL, before anything is enqueued, for a multi-device renderer, for
+ * SRR_FLAG_CONTINUE / KEEP_PATHS / COUNT_VISITS / WAVEFRONT / SUMS, for
+ * batch_spp < 1, min_spp < 1, a negative or NaN rel_tol or abs_eps, and for a
+ * struct_size smaller than the struct above.  The call invalidates the renderer's
+ * progressive running sums: no SRR_FLAG_CONTINUE render may follow it without a
+ * fresh render or srr_accum_set first. */
+int srr_render_adaptive(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, float* d_mean,
+                        int32_t* d_count, srr_adaptive_stats* stats);
+/* Host convenience, as srr_render is to srr_render_device: the shard's means
+ * (npix*3, may be NULL), counts (npix, may be NULL) and tone-mapped rgb8 (npix*3,
+ * may be NULL) in host buffers. */
+int srr_render_adaptive_host(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, float* mean,
+                             int32_t* count, unsigned char* rgb8, srr_adaptive_stats* stats);
+/* The convergence rule above on the host (no GPU): 1 converged, 0 not. */
+int srr_adaptive_converged(int32_t n, float s1, float s2, float rel_tol, float abs_eps);
+
 /* Progressive rendering with resume: the renderer's per-pixel running sums
  * (3 floats per shard pixel, in srr_shard_pixels order) and the samples per pixel
  * they hold.  get: sums may be NULL to query npix / samples.  set: restores a saved

@@ -472,6 +472,89 @@ int srr_render_device_async(srr_renderer* r, const srr_params* p, float* d_mean,
   return 0;
 }
 
+int srr_render_adaptive(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, float* d_mean,
+                        int32_t* d_count, srr_adaptive_stats* stats) {
+  if (!r || !p || !a || !d_mean) return fail(SRR_EINVAL, "null argument");
+  // every refusal comes before anything is staged or enqueued
+  if (a->struct_size < sizeof(srr_adaptive_params))
+    return fail(SRR_EINVAL, "srr_adaptive_params.struct_size " + std::to_string(a->struct_size) +
+                                " is smaller than the " + std::to_string(sizeof(srr_adaptive_params)) +
+                                " bytes this library reads");
+  if (stats && stats->struct_size < sizeof(srr_adaptive_stats))
+    return fail(SRR_EINVAL, "srr_adaptive_stats.struct_size " + std::to_string(stats->struct_size) +
+                                " is smaller than the " + std::to_string(sizeof(srr_adaptive_stats)) +
+                                " bytes this library writes");
+  if (r->multi) return fail(SRR_EINVAL, "srr_render_adaptive: one-device renderers only");
+  if (p->flags & (SRR_FLAG_CONTINUE | SRR_FLAG_KEEP_PATHS | SRR_FLAG_COUNT_VISITS | SRR_FLAG_WAVEFRONT | SRR_FLAG_SUMS))
+    return fail(SRR_EINVAL, "srr_render_adaptive: fresh path-engine frames only (no CONTINUE, KEEP_PATHS, "
+                            "COUNT_VISITS, WAVEFRONT, SUMS)");
+  if (p->spp < 1 || p->max_depth < 0 || p->max_depth > 64) return fail(SRR_EINVAL, "spp >= 1, 0 <= max_depth <= 64");
+  if (p->sample_begin != 0) return fail(SRR_EINVAL, "srr_render_adaptive: sample_begin must be 0");
+  if (a->batch_spp < 1 || a->min_spp < 1) return fail(SRR_EINVAL, "srr_render_adaptive: batch_spp >= 1, min_spp >= 1");
+  if (!(a->rel_tol >= 0.f) || !(a->abs_eps >= 0.f))  // (NaN fails both comparisons)
+    return fail(SRR_EINVAL, "srr_render_adaptive: rel_tol and abs_eps must be >= 0");
+  // the shard's pixel list is built and uploaded once per shard, as in srr_render_device
+  const int key[5] = {p->nx, p->ny, p->shard_index, p->shard_count, p->tile};
+  const bool held = std::equal(key, key + 5, r->pix_key);
+  int64_t npix = held ? r->pix_n : srr_shard_pixels(p, nullptr);
+  if (npix < 0) return (int)npix;
+  if (npix == 0) {  // a shard without pixels: no pass
+    if (stats) {
+      const uint32_t size = stats->struct_size;
+      *stats = srr_adaptive_stats{};
+      stats->struct_size = size;
+    }
+    return 0;
+  }
+  std::vector<int32_t> pix;
+  if (!held) {
+    pix.resize(npix);
+    srr_shard_pixels(p, pix.data());
+    r->pix_key[0] = -1;  // forgotten until the render succeeds
+  }
+  std::string err;
+  int rc = render_adaptive(r, p, a, held ? nullptr : pix.data(), npix, d_mean, d_count, stats, err);
+  if (rc < 0) return fail(rc, err);
+  if (!held) {
+    std::copy(key, key + 5, r->pix_key);
+    r->pix_n = npix;
+  }
+  return 0;
+}
+
+int srr_render_adaptive_host(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, float* mean,
+                             int32_t* count, unsigned char* rgb8, srr_adaptive_stats* stats) {
+  if (!r || !p || !a) return fail(SRR_EINVAL, "null argument");
+  if (r->multi) return fail(SRR_EINVAL, "srr_render_adaptive: one-device renderers only");
+  const int64_t npix = srr_shard_pixels(p, nullptr);
+  if (npix < 0) return (int)npix;
+  float* d = nullptr;
+  int32_t* dc = nullptr;
+  HIPCHK(hipSetDevice(r->device));
+  HIPCHK(hipMalloc((void**)&d, std::max<size_t>(16, 3 * npix * sizeof(float))));
+  if (hipMalloc((void**)&dc, std::max<size_t>(16, npix * sizeof(int32_t))) != hipSuccess) {
+    hipFree(d);
+    return fail(SRR_ENOMEM, "hipMalloc of the count buffer failed");
+  }
+  int rc = srr_render_adaptive(r, p, a, d, dc, stats);
+  std::vector<float> h(3 * npix);
+  if (rc == 0) {
+    hipError_t e = hipMemcpy(h.data(), d, h.size() * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && count) e = hipMemcpy(count, dc, npix * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(SRR_EIO, hipGetErrorString(e));
+  }
+  hipFree(d);
+  hipFree(dc);
+  if (rc < 0) return rc;
+  if (mean) std::memcpy(mean, h.data(), h.size() * sizeof(float));
+  if (rgb8) srr_tonemap(h.data(), npix, rgb8);
+  return 0;
+}
+
+int srr_adaptive_converged(int32_t n, float s1, float s2, float rel_tol, float abs_eps) {
+  return adaptive_converged_host(n, s1, s2, rel_tol, abs_eps);
+}
+
 int srr_render_wait(srr_renderer* r, int64_t ticket, srr_stats* stats) {
   if (!r) return fail(SRR_EINVAL, "null renderer");
   std::string err;

@@ -169,6 +169,36 @@ int launch_merl_lookup(const double* table, int64_t n, const double* angles, dou
 // (k_finish), or the raw sums when scale_ns == 0
 void launch_accumulate_window(const float* sample, int npix, int spp_w, float* acc, hipStream_t st, bool init = false,
                               float* out = nullptr, int scale_ns = 0);
+// ---- adaptive sampling (srr_render_adaptive, renderer.cpp render_adaptive)
+int paths_kernel_stack();  // the kernels' LDS traversal stack entries (kStack): launch_paths refuses a larger stack_cap
+// the convergence rule of include/srr_capi.h, evaluated by the code the kernel runs
+int adaptive_converged_host(int32_t n, float s1, float s2, float rel_tol, float abs_eps);
+// One sample window of a pass: row j of `sample` ([n_active][spp_w][3]) holds the
+// window's samples of slot active_slot[j] (nullptr: slot j), a slot being a position
+// in the shard's pixel list.  The fold adds them, in sample order, to the slot's rgb
+// sums and luminance moments (init: the state starts from 0).  decide (the pass's
+// last window, when a pixel may retire): the slot, now holding n_new samples,
+// retires if n_new >= budget or (rel_tol > 0 and the rule holds): keep[j] = 0 and
+// mean / count (may be nullptr) of the slot are written; else keep[j] = 1.
+struct AdaptiveFold {
+  const float* sample;
+  const int32_t* active_slot;
+  int n_active, spp_w;
+  float* sums;   // [slot][3]
+  float2* mom;   // [slot] (s1, s2)
+  int init, decide;
+  int n_new, budget;
+  float rel_tol, abs_eps;
+  uint8_t* keep;   // [n_active]
+  float* mean;     // [slot][3]
+  int32_t* count;  // [slot]
+};
+void launch_adaptive_fold(const AdaptiveFold& A, hipStream_t st);
+// Stable compaction of the rows with keep[j] != 0, in ascending j: slot_out[k] =
+// their slots, pixel_out[k] = pixels[slot] (nullptr: the slot itself), *n_out = how
+// many.  blk: scratch of (n_active + 255) / 256 ints.  The lists must not alias.
+void launch_adaptive_compact(const uint8_t* keep, const int32_t* active_slot, int n_active, const int32_t* pixels,
+                             int32_t* blk, int32_t* slot_out, int32_t* pixel_out, int32_t* n_out, hipStream_t st);
 void launch_raygen(const SceneView& S, const PathState& P, const BatchInfo& B, hipStream_t st);
 void launch_trace(const SceneView& S, const PathState& P, const int* active, const int* count, int max_n,
                   int* lists, int list_cap, int* fam_count, int* fetch, int max_depth, unsigned long long* ctr,

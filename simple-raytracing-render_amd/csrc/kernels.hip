@@ -3888,6 +3888,155 @@ __global__ void __launch_bounds__(256) k_accumulate_window16(const float4* sampl
   acc_write(acc, o, 3 * (size_t)lp, cx, cy, cz);
 }
 
+// ------------------------------------------------------------ adaptive sampling
+// The convergence rule of include/srr_capi.h: sem <= rel_tol * (mean + abs_eps) with
+// the divisions and the square root multiplied out, every operation in float32 in
+// the order written (the library is built with -ffp-contract=off).  One definition
+// for the fold kernel and srr_adaptive_converged.
+__host__ __device__ inline bool adaptive_converged(int n, float s1, float s2, float rel_tol, float abs_eps) {
+  const float nf = (float)n;
+  const float m = s1 + abs_eps * nf;
+  return (s2 * nf - s1 * s1) <= ((rel_tol * rel_tol) * (nf - 1.0f)) * (m * m);
+}
+
+// The moments fold of one sample window of an adaptive pass (kernels.h AdaptiveFold):
+// a block stages 256 rows x 16 samples through LDS as k_accumulate_window16 does --
+// 16-byte loads when spp_w % 4 == 0 (V4; every row and chunk is then 16-byte
+// aligned), scalar loads otherwise -- and each thread folds its row's samples, in
+// sample order, into its slot's rgb sums (the additions of k_accumulate_window) and
+// luminance moments.
+template <bool V4>
+__global__ void __launch_bounds__(256) k_adaptive_fold(AdaptiveFold A) {
+  __shared__ float tile[256 * (3 * kAccChunk + 1)];
+  const int j0 = blockIdx.x * 256;
+  const int j = j0 + threadIdx.x;
+  const int nr = min(256, A.n_active - j0);
+  const int spp_w = A.spp_w;
+  const bool mine = j < A.n_active;
+  const int slot = !mine ? 0 : A.active_slot ? A.active_slot[j] : j;
+  float cx = 0, cy = 0, cz = 0, s1 = 0, s2 = 0;
+  if (mine && !A.init) {
+    cx = A.sums[3 * (size_t)slot];
+    cy = A.sums[3 * (size_t)slot + 1];
+    cz = A.sums[3 * (size_t)slot + 2];
+    const float2 m = A.mom[slot];
+    s1 = m.x;
+    s2 = m.y;
+  }
+  for (int s0 = 0; s0 < spp_w; s0 += kAccChunk) {
+    const int n = min(kAccChunk, spp_w - s0);
+    if (V4) {
+      const float4* sample4 = (const float4*)A.sample;
+      const int qn = 3 * n / 4;  // float4 per row chunk (n is a multiple of 4)
+      for (int i = threadIdx.x; i < nr * qn; i += 256) {
+        const int px = i / qn, f4 = i - px * qn;
+        const float4 v = ntl(&sample4[((size_t)(j0 + px) * spp_w + s0) * 3 / 4 + f4]);
+        float* d = &tile[px * (3 * kAccChunk + 1) + 4 * f4];
+        d[0] = v.x;
+        d[1] = v.y;
+        d[2] = v.z;
+        d[3] = v.w;
+      }
+    } else {
+      const int row = 3 * n;
+      for (int i = threadIdx.x; i < nr * row; i += 256) {
+        const int px = i / row, f = i - px * row;
+        tile[px * (3 * kAccChunk + 1) + f] = ntl(&A.sample[((size_t)(j0 + px) * spp_w + s0) * 3 + f]);
+      }
+    }
+    __syncthreads();
+    if (mine) {
+      const float* t = &tile[threadIdx.x * (3 * kAccChunk + 1)];
+      for (int k = 0; k < n; ++k) {
+        const float r = t[3 * k], g = t[3 * k + 1], b = t[3 * k + 2];
+        cx += r;
+        cy += g;
+        cz += b;
+        const float y = (0.2126f * r + 0.7152f * g) + 0.0722f * b;
+        s1 += y;
+        s2 += y * y;
+      }
+    }
+    __syncthreads();
+  }
+  if (!mine) return;
+  A.sums[3 * (size_t)slot] = cx;
+  A.sums[3 * (size_t)slot + 1] = cy;
+  A.sums[3 * (size_t)slot + 2] = cz;
+  A.mom[slot] = make_float2(s1, s2);
+  if (!A.decide) return;
+  const bool retire =
+      A.n_new >= A.budget || (A.rel_tol > 0.f && adaptive_converged(A.n_new, s1, s2, A.rel_tol, A.abs_eps));
+  A.keep[j] = retire ? 0 : 1;
+  if (retire) {
+    const float k = 1.0 / (float)A.n_new;  // k_finish
+    A.mean[3 * (size_t)slot] = cx * k;
+    A.mean[3 * (size_t)slot + 1] = cy * k;
+    A.mean[3 * (size_t)slot + 2] = cz * k;
+    if (A.count) A.count[slot] = A.n_new;
+  }
+}
+
+// Stable compaction of the surviving rows in three kernels, none of which waits on
+// another block: per-block counts, one block's scan of them, then the scatter.
+// A row's rank in its block is its rank in its wave (ballot + mbcnt) plus the
+// survivors of the block's earlier waves (LDS).
+SRR_D int wave_rank(uint64_t mask) {  // set bits of `mask` below this lane
+  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+__global__ void __launch_bounds__(256) k_compact_count(const uint8_t* keep, int n, int32_t* blk) {
+  __shared__ int wc[4];
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  const uint64_t mask = __ballot(j < n && keep[j] != 0);
+  if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = __popcll(mask);
+  __syncthreads();
+  if (threadIdx.x == 0) blk[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
+}
+
+// blk[b] (counts) -> exclusive prefix sums, *n_out = the total; one block of 256
+__global__ void __launch_bounds__(256) k_compact_scan(int32_t* blk, int nb, int32_t* n_out) {
+  __shared__ int ws[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int carry = 0;
+  for (int base = 0; base < nb; base += 256) {
+    const int i = base + threadIdx.x;
+    const int v = i < nb ? blk[i] : 0;
+    int x = v;  // inclusive scan over the wave
+    for (int d = 1; d < 64; d <<= 1) {
+      const int y = __shfl_up(x, d);
+      if (lane >= d) x += y;
+    }
+    if (lane == 63) ws[wave] = x;
+    __syncthreads();
+    int woff = 0;
+    for (int k = 0; k < wave; ++k) woff += ws[k];
+    const int total = ws[0] + ws[1] + ws[2] + ws[3];
+    if (i < nb) blk[i] = carry + woff + x - v;
+    carry += total;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *n_out = carry;
+}
+
+__global__ void __launch_bounds__(256) k_compact_scatter(const uint8_t* keep, const int32_t* active_slot, int n,
+                                                         const int32_t* pixels, const int32_t* blk,
+                                                         int32_t* slot_out, int32_t* pixel_out) {
+  __shared__ int wc[4];
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  const bool pred = j < n && keep[j] != 0;
+  const uint64_t mask = __ballot(pred);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) wc[wave] = __popcll(mask);
+  __syncthreads();
+  if (!pred) return;
+  int dst = blk[blockIdx.x] + wave_rank(mask);
+  for (int k = 0; k < wave; ++k) dst += wc[k];
+  const int slot = active_slot ? active_slot[j] : j;
+  slot_out[dst] = slot;
+  pixel_out[dst] = pixels ? pixels[slot] : slot;
+}
+
 constexpr int kMaxRegions = 8;
 
 // Grid-stride over family F's list (sized on the device: no host readback);
@@ -4426,6 +4575,31 @@ void launch_accumulate_window(const float* sample, int npix, int spp_w, float* a
   else
     hipLaunchKernelGGL(dev::k_accumulate_window, dim3((npix + 255) / 256), dim3(256), 0, st, sample, npix, spp_w, acc,
                        init ? 1 : 0, o);
+}
+
+int paths_kernel_stack() { return dev::kStack; }
+
+int adaptive_converged_host(int32_t n, float s1, float s2, float rel_tol, float abs_eps) {
+  return dev::adaptive_converged(n, s1, s2, rel_tol, abs_eps) ? 1 : 0;
+}
+
+void launch_adaptive_fold(const AdaptiveFold& A, hipStream_t st) {
+  if (A.n_active <= 0 || A.spp_w <= 0) return;
+  const dim3 g((A.n_active + 255) / 256);
+  if (A.spp_w % 4 == 0 && ((uintptr_t)A.sample & 15) == 0)
+    hipLaunchKernelGGL(dev::k_adaptive_fold<true>, g, dim3(256), 0, st, A);
+  else
+    hipLaunchKernelGGL(dev::k_adaptive_fold<false>, g, dim3(256), 0, st, A);
+}
+
+void launch_adaptive_compact(const uint8_t* keep, const int32_t* active_slot, int n_active, const int32_t* pixels,
+                             int32_t* blk, int32_t* slot_out, int32_t* pixel_out, int32_t* n_out, hipStream_t st) {
+  if (n_active <= 0) return;
+  const int nb = (n_active + 255) / 256;
+  hipLaunchKernelGGL(dev::k_compact_count, dim3(nb), dim3(256), 0, st, keep, n_active, blk);
+  hipLaunchKernelGGL(dev::k_compact_scan, dim3(1), dim3(256), 0, st, blk, nb, n_out);
+  hipLaunchKernelGGL(dev::k_compact_scatter, dim3(nb), dim3(256), 0, st, keep, active_slot, n_active, pixels,
+                     (const int32_t*)blk, slot_out, pixel_out);
 }
 
 }  // namespace srr

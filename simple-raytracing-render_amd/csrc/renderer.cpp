@@ -400,14 +400,20 @@ static void release_window(FrameSlot& F) {
 // paths_enqueue puts a whole frame on slot F's stream (sums in `acc`, zeroed by
 // the first window when `zero_pending`); paths_finish waits for it and reads its
 // counters.  The caller has staged the pixel list and the Sobol set.
-static int paths_enqueue(srr_renderer* r, FrameSlot& F, const srr_params* p, bool identity, int64_t npix,
-                         float* acc, bool zero_pending, int64_t acc_total, float* d_mean, bool diagnostics,
-                         std::string& err) {
-  const bool keep = (p->flags & SRR_FLAG_KEEP_PATHS) != 0;
-  hipStream_t st = F.st;
+// What the k_paths launches of one frame share: paths_prepare sizes the slot's bounce
+// records and traversal-stack extension and reads the per-frame environment knobs.
+struct PathsSetup {
+  int gst_cap = 0;     // global stack extension entries per lane (0: none)
+  int walk_q = 0;      // suspendable mesh walks (PathWork::walk_q before the gstack condition)
+  int deep_tries = 32; // coop_mixture threshold
+  int stack_cap = kPathsLdsStack;
+  size_t budget = 0;   // sample-window bytes (SRR_WINDOW_MB over the renderers sharing the device)
+};
+
+static int paths_prepare(srr_renderer* r, FrameSlot& F, int max_depth, PathsSetup& ps, std::string& err) {
   // persistent lanes and their bounce records
   if (!r->pw_lanes) r->pw_lanes = paths_lanes_per_device(r->view, r->device);
-  const size_t rec_need = (size_t)r->pw_lanes * std::max(1, p->max_depth);
+  const size_t rec_need = (size_t)r->pw_lanes * std::max(1, max_depth);
   if (rec_need > F.rec_cap) {
     (void)hipFree(F.rec);
     F.rec = nullptr;
@@ -418,34 +424,45 @@ static int paths_enqueue(srr_renderer* r, FrameSlot& F, const srr_params* p, boo
   // global extension of the BVH4 traversal stack, for meshes deep enough to need it
   // (SRR_GSTACK=0 disables it: every deeper traversal then re-walks the BVH2)
   const char* gs_env = getenv("SRR_GSTACK");
-  const int gst_cap = (r->has_meshes && !(gs_env && !atoi(gs_env))) ? kPathsGlobalStack : 0;
+  ps.gst_cap = (r->has_meshes && !(gs_env && !atoi(gs_env))) ? kPathsGlobalStack : 0;
   // ... followed by the save area of suspended mesh walks (3 float4 per lane)
-  if (gst_cap && !F.gstack)
-    RCHK(hipMalloc((void**)&F.gstack, (size_t)gst_cap * r->pw_lanes * sizeof(int2) + 3 * (size_t)r->pw_lanes * sizeof(float4)));
+  if (ps.gst_cap && !F.gstack)
+    RCHK(hipMalloc((void**)&F.gstack, (size_t)ps.gst_cap * r->pw_lanes * sizeof(int2) + 3 * (size_t)r->pw_lanes * sizeof(float4)));
   // suspendable mesh walks: a walk still running when at most SRR_WALK_Q / 64
   // of its wave's lanes walk continues in the next wave-iteration (default: the scene's
   // walk_q_default, 8 or 0); SRR_WALK_Q=0 never suspends and launches the kernel variant
   // without the feature (read per frame: tests switch it between renders)
   const char* wq_env = getenv("SRR_WALK_Q");
-  const int walk_q = wq_env ? std::max(0, std::min(64, atoi(wq_env))) : r->walk_q_default;
+  ps.walk_q = wq_env ? std::max(0, std::min(64, atoi(wq_env))) : r->walk_q_default;
   // sample window: all pixels x W samples, buffer within SRR_WINDOW_MB (default 16384: a
   // 1080p frame of 1,024 spp in 2 windows, not 3 -- one drain and one serial accumulation
   // fewer)
-  size_t budget = (size_t)16384 << 20;
-  if (const char* e = getenv("SRR_WINDOW_MB")) budget = (size_t)std::max(1, atoi(e)) << 20;
-  budget /= (size_t)std::max(1, r->window_share);
-  // (k_paths numbers a window's paths in 32 bits: npix * W < 2^31)
+  ps.budget = (size_t)16384 << 20;
+  if (const char* e = getenv("SRR_WINDOW_MB")) ps.budget = (size_t)std::max(1, atoi(e)) << 20;
+  ps.budget /= (size_t)std::max(1, r->window_share);
+  // attempts after which a pending resampling loop takes every free lane of its
+  // wave (kernels.hip coop_mixture); SRR_DEEP_TRIES=0 forces that branch (tests)
+  const char* dt_env = getenv("SRR_DEEP_TRIES");
+  ps.deep_tries = dt_env ? std::max(0, atoi(dt_env)) : 32;
+  ps.stack_cap = kPathsLdsStack;  // kernels.hip kStack
+  if (const char* e = getenv("SRR_STACK_CAP")) ps.stack_cap = std::max(1, std::min(kPathsLdsStack, atoi(e)));
+  return 0;
+}
+
+// Samples per window for `npix` pixels that still need `spp` samples: within the
+// window budget and k_paths' 32-bit path numbering (npix * W < 2^31).
+static int window_samples(const PathsSetup& ps, int64_t npix, int spp) {
   const int64_t w_max = std::max<int64_t>(1, (((int64_t)1 << 31) - 1) / std::max<int64_t>(1, npix));
   int W = (int)std::max<int64_t>(
-      1, std::min<int64_t>(std::min<int64_t>(p->spp, w_max), (int64_t)(budget / (12 * (size_t)npix))));
+      1, std::min<int64_t>(std::min<int64_t>(spp, w_max), (int64_t)(ps.budget / (12 * (size_t)npix))));
   // a window of a multiple of 4 samples is summed with 16-byte loads (k_accumulate_window16;
   // 1080p: 345 -> 344 samples, still 3 windows of 1,024); the sums do not depend on W
-  if (W < p->spp && W >= 16) W &= ~3;
-  if ((int64_t)npix * W >= ((int64_t)1 << 31)) {
-    err = "frame too large for one sample window (npix >= 2^31)";
-    return SRR_EINVAL;
-  }
-  const size_t win_paths = (size_t)npix * W;
+  if (W < spp && W >= 16) W &= ~3;
+  return W;
+}
+
+// The slot's sample window holds at least win_paths paths.
+static int ensure_window(srr_renderer* r, FrameSlot& F, size_t win_paths, std::string& err) {
   if (win_paths > F.sample_cap) {
     (void)hipFree(F.sample);
     F.sample = nullptr;
@@ -466,6 +483,60 @@ static int paths_enqueue(srr_renderer* r, FrameSlot& F, const srr_params* p, boo
     }
     RCHK(e);
     F.sample_cap = win_paths;
+  }
+  return 0;
+}
+
+// One k_paths launch over `npix` pixels (list `pixels`, nullptr = identity) x the Wn
+// samples whose first global index is s_first; no kept paths, no diagnostics.
+static PathWork paths_work(srr_renderer* r, FrameSlot& F, const srr_params* p, const PathsSetup& ps,
+                           const int32_t* pixels, int64_t npix, int s_first, int Wn) {
+  PathWork w{};
+  w.pixels = pixels;
+  w.sobol = r->sobol + 2 * (size_t)s_first;
+  w.npix = (int)npix;
+  w.spp_w = Wn;
+  w.s_base = s_first;
+  w.nx = p->nx;
+  w.ny = p->ny;
+  w.div_spp = make_udiv31((uint32_t)Wn);
+  w.div_nx = make_udiv31((uint32_t)p->nx);
+  w.base_seed = p->base_seed;
+  w.n_paths = (int64_t)npix * Wn;
+  w.max_depth = p->max_depth;
+  w.cursor = F.ctr + 1;
+  w.counters = F.ctr;
+  w.sample = F.sample;
+  w.rec = F.rec;
+  w.err = (int*)(F.ctr + 2);
+  const int64_t bl = paths_block_lanes(r->view);  // whole blocks of the launch's size
+  w.lanes = (int)std::min<int64_t>(r->pw_lanes, ((w.n_paths + bl - 1) / bl) * bl);
+  w.stack_cap = ps.stack_cap;
+  w.gstack = ps.gst_cap ? F.gstack : nullptr;
+  w.gstack_cap = ps.gst_cap;
+  w.deep_tries = ps.deep_tries;
+  w.walk_q = ps.gst_cap ? ps.walk_q : 0;  // (the save area follows the global stack extension)
+  return w;
+}
+
+static int paths_enqueue(srr_renderer* r, FrameSlot& F, const srr_params* p, bool identity, int64_t npix,
+                         float* acc, bool zero_pending, int64_t acc_total, float* d_mean, bool diagnostics,
+                         std::string& err) {
+  const bool keep = (p->flags & SRR_FLAG_KEEP_PATHS) != 0;
+  hipStream_t st = F.st;
+  PathsSetup ps;
+  {
+    const int rc = paths_prepare(r, F, p->max_depth, ps, err);
+    if (rc < 0) return rc;
+  }
+  const int W = window_samples(ps, npix, p->spp);
+  if ((int64_t)npix * W >= ((int64_t)1 << 31)) {
+    err = "frame too large for one sample window (npix >= 2^31)";
+    return SRR_EINVAL;
+  }
+  {
+    const int rc = ensure_window(r, F, (size_t)npix * W, err);
+    if (rc < 0) return rc;
   }
   RCHK(hipMemsetAsync(F.ctr, 0, kCtrWords * sizeof(unsigned long long), st));
   const bool want_sums = (p->flags & SRR_FLAG_SUMS) != 0;
@@ -488,10 +559,6 @@ static int paths_enqueue(srr_renderer* r, FrameSlot& F, const srr_params* p, boo
     wave_times = r->pw_wave_times;
     RCHK(hipMemsetAsync(wave_times, 0, 4 * (size_t)n_waves * sizeof(unsigned long long), st));
   }
-  // attempts after which a pending resampling loop takes every free lane of its
-  // wave (kernels.hip coop_mixture); SRR_DEEP_TRIES=0 forces that branch (tests)
-  const char* dt_env = getenv("SRR_DEEP_TRIES");
-  const int deep_tries = dt_env ? std::max(0, atoi(dt_env)) : 32;
 #ifdef SRR_SLOW_RAYS
   if (!r->pw_slow) RCHK(hipMalloc((void**)&r->pw_slow, (16 * 65536 + 16) * sizeof(float)));
   RCHK(hipMemsetAsync(r->pw_slow + 16 * 65536, 0, 16 * sizeof(float), st));
@@ -499,37 +566,12 @@ static int paths_enqueue(srr_renderer* r, FrameSlot& F, const srr_params* p, boo
   RCHK(hipEventRecord(F.ev_beg, st));
   for (int s0 = 0; s0 < p->spp; s0 += W) {
     const int Wn = std::min(W, p->spp - s0);
-    PathWork w{};
-    w.pixels = identity ? nullptr : r->pixels;
-    w.sobol = r->sobol + 2 * (size_t)(p->sample_begin + s0);
-    w.npix = (int)npix;
-    w.spp_w = Wn;
-    w.s_base = p->sample_begin + s0;
-    w.nx = p->nx;
-    w.ny = p->ny;
-    w.div_spp = make_udiv31((uint32_t)Wn);
-    w.div_nx = make_udiv31((uint32_t)p->nx);
-    w.base_seed = p->base_seed;
-    w.n_paths = (int64_t)npix * Wn;
-    w.max_depth = p->max_depth;
-    w.cursor = F.ctr + 1;
-    w.counters = F.ctr;
-    w.sample = F.sample;
+    PathWork w = paths_work(r, F, p, ps, identity ? nullptr : r->pixels, npix, p->sample_begin + s0, Wn);
     w.raw = keep ? r->raw_all : nullptr;
     w.rays = keep ? r->rays_all : nullptr;
     w.keep_spp = p->spp;
     w.keep_s0 = s0;
-    w.rec = F.rec;
-    w.err = (int*)(F.ctr + 2);
-    const int64_t bl = paths_block_lanes(r->view);  // whole blocks of the launch's size
-    w.lanes = (int)std::min<int64_t>(r->pw_lanes, ((w.n_paths + bl - 1) / bl) * bl);
-    w.stack_cap = kPathsLdsStack;  // kernels.hip kStack
-    if (const char* e = getenv("SRR_STACK_CAP")) w.stack_cap = std::max(1, std::min(kPathsLdsStack, atoi(e)));
-    w.gstack = gst_cap ? F.gstack : nullptr;
-    w.gstack_cap = gst_cap;
     w.wave_times = wave_times;
-    w.deep_tries = deep_tries;
-    w.walk_q = gst_cap ? walk_q : 0;  // (the save area follows the global stack extension)
     w.slow_rays = diagnostics ? r->pw_slow : nullptr;
     w.slow_count = w.slow_rays ? (unsigned*)(r->pw_slow + 16 * 65536) : nullptr;
     const int wi = s0 / W;
@@ -733,6 +775,176 @@ static int render_paths(srr_renderer* r, const srr_params* p, const int32_t* pix
   r->acc_samples = acc_total;
   commit.ok = true;
   return 0;
+}
+
+// ---- adaptive sampling (include/srr_capi.h srr_render_adaptive)
+void free_adaptive(AdaptiveState& A) {
+  (void)hipFree(A.mom);
+  for (int k = 0; k < 2; ++k) {
+    (void)hipFree(A.slot[k]);
+    (void)hipFree(A.pixel[k]);
+  }
+  (void)hipFree(A.keep);
+  (void)hipFree(A.blk);
+  if (A.n_host) (void)hipHostFree(A.n_host);
+  A = AdaptiveState{};
+}
+
+static int ensure_adaptive(AdaptiveState& A, size_t npix, std::string& err) {
+  if (npix <= A.cap) return 0;
+  free_adaptive(A);
+  RCHK(hipMalloc((void**)&A.mom, npix * sizeof(float2)));
+  for (int k = 0; k < 2; ++k) {
+    RCHK(hipMalloc((void**)&A.slot[k], npix * sizeof(int32_t)));
+    RCHK(hipMalloc((void**)&A.pixel[k], npix * sizeof(int32_t)));
+  }
+  RCHK(hipMalloc((void**)&A.keep, npix));
+  RCHK(hipMalloc((void**)&A.blk, ((npix + 255) / 256 + 1) * sizeof(int32_t)));
+  RCHK(hipHostMalloc((void**)&A.n_host, sizeof(int32_t)));
+  A.cap = npix;
+  return 0;
+}
+
+// The pass loop: everything that can refuse the frame has been checked and every
+// buffer sized (render_adaptive), so from here on only HIP itself can fail.
+// win_cap: paths the slot's sample window holds.
+static int adaptive_passes(srr_renderer* r, FrameSlot& F, const srr_params* p, const srr_adaptive_params* a,
+                           const PathsSetup& ps, bool identity, int64_t npix, size_t win_cap, float* d_mean,
+                           int32_t* d_count, srr_adaptive_stats* stats, std::string& err) {
+  AdaptiveState& A = r->adaptive;
+  hipStream_t st = F.st;
+  const int budget = p->spp;
+  const int32_t* shard_pixels = identity ? nullptr : r->pixels;
+  int32_t* n_dev = A.blk + (A.cap + 255) / 256;
+  srr_adaptive_stats s{};
+  RCHK(hipMemsetAsync(F.ctr, 0, kCtrWords * sizeof(unsigned long long), st));
+  RCHK(hipEventRecord(F.ev_beg, st));
+  int n = 0;     // samples every active pixel holds
+  int cur = -1;  // the active lists are A.slot / A.pixel[cur]; -1: every slot, in order
+  int64_t n_act = npix;
+  bool first_launch = true;
+  while (n_act > 0 && n < budget) {
+    const int w = std::min(a->batch_spp, budget - n), n_new = n + w;
+    // can a pixel retire after this pass?  (if none can, no flags, no compaction, no read-back)
+    const bool decide = n_new >= budget || (n_new >= a->min_spp && a->rel_tol > 0.f);
+    const int32_t* slots = cur < 0 ? nullptr : A.slot[cur];
+    const int32_t* pixels = cur < 0 ? shard_pixels : A.pixel[cur];
+    // the pass in sample windows that fit the slot's buffer (one, unless the frame is huge)
+    int W = (int)std::min<int64_t>(window_samples(ps, n_act, w), (int64_t)(win_cap / (size_t)n_act));
+    if (W < w && W >= 16) W &= ~3;
+    for (int s0 = 0; s0 < w; s0 += W) {
+      const int Wn = std::min(W, w - s0);
+      const PathWork pw = paths_work(r, F, p, ps, pixels, n_act, n + s0, Wn);
+      if (!first_launch) RCHK(hipMemsetAsync(pw.cursor, 0, sizeof(unsigned long long), st));  // first: zeroed with ctr
+      first_launch = false;
+      if (launch_paths(r->view, pw, r->diffuse_only ? 0 : 1, st) != 0) {
+        err = "k_paths refused the launch";  // (stack_cap was checked before the first pass)
+        return SRR_EINVAL;
+      }
+      AdaptiveFold f{};
+      f.sample = F.sample;
+      f.active_slot = slots;
+      f.n_active = (int)n_act;
+      f.spp_w = Wn;
+      f.sums = r->acc;
+      f.mom = A.mom;
+      f.init = n + s0 == 0;
+      f.decide = decide && s0 + Wn >= w;
+      f.n_new = n_new;
+      f.budget = budget;
+      f.rel_tol = a->rel_tol;
+      f.abs_eps = a->abs_eps;
+      f.keep = A.keep;
+      f.mean = d_mean;
+      f.count = d_count;
+      launch_adaptive_fold(f, st);
+    }
+    n = n_new;
+    s.passes += 1;
+    s.paths += n_act * w;
+    if (n >= budget) break;  // the fold retired every active pixel at the budget
+    if (!decide) continue;
+    const int nxt = cur < 0 ? 0 : cur ^ 1;
+    launch_adaptive_compact(A.keep, slots, (int)n_act, shard_pixels, A.blk, A.slot[nxt], A.pixel[nxt], n_dev, st);
+    // the one host round trip of a pass: the next launch is sized by the survivors
+    RCHK(hipMemcpyAsync(A.n_host, n_dev, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    RCHK(hipStreamSynchronize(st));
+    const int64_t n_next = *A.n_host;
+    if (n_next < 0 || n_next > n_act) {
+      err = "adaptive compaction returned " + std::to_string(n_next) + " of " + std::to_string(n_act) + " pixels";
+      return SRR_EIO;
+    }
+    s.pixels_retired += n_act - n_next;
+    n_act = n_next;
+    cur = nxt;
+  }
+  RCHK(hipMemcpyAsync(F.ctr_host, F.ctr, kCtrWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  RCHK(hipEventRecord(F.ev_end, st));
+  RCHK(hipStreamSynchronize(st));
+  RCHK(hipGetLastError());
+  if (F.ctr_host[2]) {
+    err = "k_paths index guard tripped (bits " + std::to_string(F.ctr_host[2]) + ")";
+    return SRR_EIO;
+  }
+  float total = 0;
+  RCHK(hipEventElapsedTime(&total, F.ev_beg, F.ev_end));
+  s.world_rays = (int64_t)F.ctr_host[0];
+  s.total_ms = total;
+  if (stats) {
+    s.struct_size = stats->struct_size;
+    *stats = s;
+  }
+  return 0;
+}
+
+int render_adaptive(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, const int32_t* pix,
+                    int64_t npix, float* d_mean, int32_t* d_count, srr_adaptive_stats* stats, std::string& err) {
+  if (const char* e = getenv("SRR_ENGINE"); e && !strcmp(e, "wave")) {
+    err = "srr_render_adaptive: path engine only (SRR_ENGINE=wave is set)";
+    return SRR_EINVAL;
+  }
+  RCHK(hipSetDevice(r->device));
+  // the rgb sums of the pass loop live in the progressive accumulator: whatever it
+  // held is gone, and what this frame leaves (pixels of different sample counts) is
+  // nothing a SRR_FLAG_CONTINUE render may build on
+  r->acc_npix = 0;
+  bool identity = false;
+  {
+    const int rc = paths_stage(r, p, pix, npix, identity, err);
+    if (rc < 0) return rc;
+  }
+  FrameSlot& F = r->sync_slot;
+  {
+    const int rc = slot_init(F, r->acc_st, err);
+    if (rc < 0) return rc;
+  }
+  PathsSetup ps;
+  {
+    const int rc = paths_prepare(r, F, p->max_depth, ps, err);
+    if (rc < 0) return rc;
+  }
+  if (ps.stack_cap > paths_kernel_stack()) {
+    err = "k_paths refused: stack_cap " + std::to_string(ps.stack_cap) +
+          " exceeds the kernel build's LDS stack (a host and kernels built with different SRR_KSTACK)";
+    return SRR_EINVAL;
+  }
+  // the first pass has the most paths: its window serves every later one
+  const size_t win_cap = (size_t)npix * window_samples(ps, npix, std::min(a->batch_spp, p->spp));
+  if (win_cap >= ((size_t)1 << 31)) {
+    err = "frame too large for one sample window (npix >= 2^31)";
+    return SRR_EINVAL;
+  }
+  {
+    const int rc = ensure_window(r, F, win_cap, err);
+    if (rc < 0) return rc;
+  }
+  {
+    const int rc = ensure_adaptive(r->adaptive, (size_t)npix, err);
+    if (rc < 0) return rc;
+  }
+  const int rc = adaptive_passes(r, F, p, a, ps, identity, npix, win_cap, d_mean, d_count, stats, err);
+  if (rc < 0) (void)hipStreamSynchronize(F.st);  // passes already enqueued must not outlive the error
+  return rc;
 }
 
 // srr_render_device_async: a fresh frame (no CONTINUE, KEEP_PATHS, COUNT_VISITS or
@@ -1073,6 +1285,7 @@ srr_renderer::~srr_renderer() {
   if (ev_async_in) (void)hipEventDestroy(ev_async_in);
   (void)hipFree(pw_wave_times);
   (void)hipFree(pw_slow);
+  srr::free_adaptive(adaptive);
   for (auto& L : lanes) {
     srr::free_lane_paths(L);
     (void)hipFree(L.cnt);

@@ -82,6 +82,18 @@ struct DoneTicket {  // an async frame finished before its srr_render_wait
   std::string err;
 };
 
+// Per-slot state and active lists of srr_render_adaptive (renderer.cpp render_adaptive);
+// a slot is a position in the shard's pixel list.  The rgb sums are srr_renderer::acc.
+struct AdaptiveState {
+  size_t cap = 0;               // slots the buffers hold
+  float2* mom = nullptr;        // [slot] luminance moments (s1, s2)
+  int32_t* slot[2] = {};        // active slots, ping-pong over the compactions
+  int32_t* pixel[2] = {};       // their image pixels (PathWork::pixels)
+  uint8_t* keep = nullptr;      // [active row] survives the pass
+  int32_t* blk = nullptr;       // compaction scratch: per-block counts / offsets, then [nb] the new active count
+  int32_t* n_host = nullptr;    // pinned mirror of the new active count
+};
+
 struct Multi;  // multi.h
 }  // namespace srr
 
@@ -134,6 +146,7 @@ struct srr_renderer {
   uint8_t* rays_all = nullptr;
   size_t keep_cap = 0;
   int64_t kept_paths = 0;
+  srr::AdaptiveState adaptive;
   ~srr_renderer();
 };
 
@@ -147,6 +160,9 @@ int render_device(srr_renderer* r, const srr_params* p, const int32_t* pix, int6
                   srr_stats* stats, std::string& err);
 int render_device_async(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t npix, float* d_mean,
                         int64_t* ticket, std::string& err);
+// srr_render_adaptive on a one-device renderer, its arguments already validated (capi.cpp)
+int render_adaptive(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, const int32_t* pix,
+                    int64_t npix, float* d_mean, int32_t* d_count, srr_adaptive_stats* stats, std::string& err);
 int render_wait(srr_renderer* r, int64_t ticket, srr_stats* stats, std::string& err);
 void drain_async(srr_renderer* r);  // finish every async frame in flight (results kept for render_wait)
 // the event recorded after async frame `ticket`'s last operation (its slot's frame end),

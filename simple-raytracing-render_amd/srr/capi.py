@@ -43,6 +43,19 @@ class Stats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AdaptiveParams(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("batch_spp", ctypes.c_int), ("min_spp", ctypes.c_int),
+                ("rel_tol", ctypes.c_float), ("abs_eps", ctypes.c_float)]
+
+
+class AdaptiveStats(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("passes", ctypes.c_int32), ("paths", ctypes.c_int64),
+                ("world_rays", ctypes.c_int64), ("pixels_retired", ctypes.c_int64), ("total_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
 def lib():
     global _LIB
     if _LIB is None:
@@ -95,6 +108,13 @@ def lib():
         i64p = ctypes.POINTER(ctypes.c_int64)
         L.srr_accum_get.argtypes = [vp, vp, i64p, i64p]
         L.srr_accum_set.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int64]
+        if hasattr(L, "srr_render_adaptive"):  # (an older A/B library under SRR_LIB lacks it: calls then fail by name)
+            L.srr_render_adaptive.argtypes = [vp, ctypes.POINTER(Params), ctypes.POINTER(AdaptiveParams), vp, vp,
+                                              ctypes.POINTER(AdaptiveStats)]
+            L.srr_render_adaptive_host.argtypes = [vp, ctypes.POINTER(Params), ctypes.POINTER(AdaptiveParams), vp,
+                                                   vp, vp, ctypes.POINTER(AdaptiveStats)]
+            L.srr_adaptive_converged.argtypes = [ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                                 ctypes.c_float]
         _LIB = L
     return _LIB
 
@@ -240,6 +260,34 @@ class Renderer:
             out.update(paths=paths, rays=rays)
         return out
 
+    def render_adaptive(self, nx, ny, max_spp, max_depth=50, batch_spp=16, min_spp=16, rel_tol=0.02, abs_eps=1e-3,
+                        **kw):
+        """Adaptive sampling (srr_render_adaptive): every pixel gets samples in
+        passes of batch_spp until its luminance's relative standard error is at
+        most rel_tol (not before min_spp samples) or it holds max_spp.  Returns
+        dict(mean[n,3], count[n], img8[n,3], stats); kw: shard, tile, base_seed,
+        flags, and struct_size (the srr_adaptive_params size the caller claims)."""
+        size = kw.pop("struct_size", ctypes.sizeof(AdaptiveParams))
+        p = make_params(nx, ny, max_spp, max_depth, **kw)
+        a = AdaptiveParams(size, batch_spp, min_spp, rel_tol, abs_eps)
+        n = nx * ny if self.transport != "none" else shard_pixels(p).size
+        mean = np.zeros((n, 3), np.float32)
+        count = np.zeros(n, np.int32)
+        img8 = np.zeros((n, 3), np.uint8)
+        st = AdaptiveStats(ctypes.sizeof(AdaptiveStats))
+        _check(lib().srr_render_adaptive_host(self.h, ctypes.byref(p), ctypes.byref(a), _ptr(mean), _ptr(count),
+                                              _ptr(img8), ctypes.byref(st)))
+        return dict(mean=mean, count=count, img8=img8, stats=st.as_dict())
+
+    def render_adaptive_device(self, params: Params, adaptive: AdaptiveParams, d_mean_ptr: int,
+                               d_count_ptr: int = 0) -> dict:
+        """srr_render_adaptive into device buffers (e.g. torch tensors' data_ptr())."""
+        st = AdaptiveStats(ctypes.sizeof(AdaptiveStats))
+        _check(lib().srr_render_adaptive(self.h, ctypes.byref(params), ctypes.byref(adaptive),
+                                         ctypes.c_void_p(d_mean_ptr), ctypes.c_void_p(d_count_ptr or None),
+                                         ctypes.byref(st)))
+        return st.as_dict()
+
     def render_device(self, params: Params, d_mean_ptr: int) -> dict:
         """Render into a device buffer (e.g. a torch tensor's data_ptr())."""
         st = Stats()
@@ -259,6 +307,11 @@ class Renderer:
         st = Stats()
         _check(lib().srr_render_wait(self.h, ctypes.c_int64(ticket), ctypes.byref(st)))
         return st.as_dict()
+
+
+def adaptive_converged(n, s1, s2, rel_tol, abs_eps) -> bool:
+    """The convergence rule of srr_render_adaptive (srr_adaptive_converged; host, no GPU)."""
+    return bool(lib().srr_adaptive_converged(int(n), float(s1), float(s2), float(rel_tol), float(abs_eps)))
 
 
 def tonemap(mean: np.ndarray) -> np.ndarray:

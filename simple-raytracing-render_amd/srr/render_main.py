@@ -7,6 +7,8 @@ format of Raytracing_n.cpp:850-886).
 
     python -m srr.render_main [--sceneid 2] [--nx 1000] [--ny 1000] [--ns 50] [--max-depth 50] [--out out.ppm]
                               [--gpus N]   (srr_renderer_create_multi: one RCCL gather at frame end)
+                              [--adaptive REL_TOL [--batch-spp 16] [--min-spp 16] [--count-map FILE]]
+                                           (srr_render_adaptive: --ns is the per-pixel budget; one GPU)
 
 Defaults are the reference's globals (Raytracing_n.cpp:39-43).  Differences, all
 forced by the reference: its 8 render threads race on shared state
@@ -38,7 +40,21 @@ def parse(argv=None):
                     help="render on devices device .. device+gpus-1 (pixels dealt round-robin, one RCCL gather)")
     ap.add_argument("--contents", default=None, help="the reference's contents/ directory (assets)")
     ap.add_argument("--out", default="out.ppm")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="REL_TOL",
+                    help="adaptive sampling: --ns is the per-pixel budget; a pixel stops once the relative "
+                         "standard error of its mean luminance is at most REL_TOL (one GPU)")
+    ap.add_argument("--batch-spp", type=int, default=16, help="adaptive: samples per pixel and pass")
+    ap.add_argument("--min-spp", type=int, default=16, help="adaptive: no pixel stops with fewer samples")
+    ap.add_argument("--count-map", default=None, metavar="FILE",
+                    help="adaptive: PNG of the samples each pixel took, as grey level count / ns")
     return ap.parse_args(argv)
+
+
+def count_map(count, max_spp):
+    """Per-pixel sample counts as 8-bit grey rgb: 255 * count / max_spp, rounded down."""
+    import numpy as np
+    g = (np.asarray(count, np.int64) * 255 // max(1, max_spp)).clip(0, 255).astype(np.uint8)
+    return np.repeat(g[:, None], 3, axis=1)
 
 
 def main(argv=None) -> int:
@@ -46,12 +62,24 @@ def main(argv=None) -> int:
     sc = ref_scenes.BY_SCENEID[a.sceneid](float(a.nx) / float(a.ny), contents=a.contents)  # :894-919
     r = (capi.Renderer(sc.text(), device=a.device) if a.gpus == 1 else
          capi.Renderer(sc.text(), devices=list(range(a.device, a.device + a.gpus))))
+    if a.adaptive is None and a.count_map:
+        print("--count-map needs --adaptive", file=sys.stderr)
+        return 2
     t0 = time.perf_counter()
-    out = r.render(a.nx, a.ny, a.ns, a.max_depth, tile=1)
+    if a.adaptive is not None:
+        out = r.render_adaptive(a.nx, a.ny, a.ns, a.max_depth, batch_spp=a.batch_spp, min_spp=a.min_spp,
+                                rel_tol=a.adaptive, tile=1)
+    else:
+        out = r.render(a.nx, a.ny, a.ns, a.max_depth, tile=1)
     ms = (time.perf_counter() - t0) * 1e3
     print(f"{int(ms)}ms")  # :944-947
     capi.write_ppm(a.out, a.nx, a.ny, out["img8"])
     st = out["stats"]
+    if a.adaptive is not None:
+        print(f"adaptive: {st['paths']} of {a.nx * a.ny * a.ns} samples in {st['passes']} passes, "
+              f"{st['pixels_retired']} pixels stopped early", file=sys.stderr)
+        if a.count_map:
+            capi.write_png(a.count_map, a.nx, a.ny, count_map(out["count"], a.ns))
     print(f"{SCENE_NAMES[a.sceneid]}: {a.nx}x{a.ny}x{a.ns}, {st['world_rays']} world rays, "
           f"{st['world_rays'] / max(ms, 1e-3) / 1e3:.1f} Msamples/s -> {a.out}", file=sys.stderr)
     return 0
