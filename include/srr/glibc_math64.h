@@ -1,6 +1,6 @@
 // SPDX-License-Identifier: LGPL-2.1-or-later
 // Derived from the GNU C Library 2.35 (sysdeps/ieee754/dbl-64: s_sin.c, s_sincos.c,
-// e_asin.c, e_atan2.c, and their data tables) -- IBM Accurate Mathematical Library,
+// e_asin.c, e_atan2.c, e_log.c, and their data tables) -- IBM Accurate Mathematical Library,
 // written by International Business Machines Corp.;
 // Copyright (C) 2001-2022 Free Software Foundation, Inc.
 // The GNU C Library is free software; you can redistribute it and/or modify it
@@ -29,9 +29,13 @@
 // (glibc_math64_tables.inc, extracted from libm-2.35.a by tools/gen_glibc_math64.py).
 // tools/check_glibc_math64.cpp compares them with the host libm.
 //
+// log (e_log.c, __ieee754_log_fma) is the medium's hit distance,
+// -(1 / density) * log(drand) (constant_medium.h:36): of the 2^32 draws, the device's
+// own log moved two across a float rounding tie (DESIGN, GPU numerics).
+//
 // Domain: sin / cos take |x| < 105414350 (the reference's angles are within
 // [-2pi, 2pi]); beyond that glibc's __branred reduction is not restated and the
-// functions return NaN.  acos / atan2 cover every input.
+// functions return NaN.  acos / atan2 / log cover every input.
 #pragma once
 #include <cstdint>
 
@@ -500,6 +504,63 @@ GM64_FN double atan2(double y, double x) {
     }
   }
   return copysign_(z, y);
+}
+
+// ---------------------------------------------------------------- e_log.c
+// kLogData is struct log_data: ln2hi, ln2lo, poly A[0..4] at 2, poly1 B[0..10] at 7,
+// then 128 rows {invc, logc} at 18.  The fused multiply-adds are those of the FMA
+// build (__FP_FAST_FMA: r = fma(z, invc, -1); the rest contracted by the compiler).
+
+GM64_FN double log(double x) {
+  uint64_t ix = bits(x);
+  const uint32_t top = (uint32_t)(ix >> 48);
+  const uint64_t* const A = kLogData + 2;
+  const uint64_t* const B = kLogData + 7;
+  if (ix - 0x3fee000000000000ULL < 0x0003090000000000ULL) {  // 1 - 2^-4 <= x < 1 + 0x1.09p-4
+    if (ix == 0x3ff0000000000000ULL) return 0.0;
+    const double r = x - 1.0;
+    const double r2 = r * r;
+    const double r3 = r * r2;
+    const double p1 = GM64_FMA(r2, dbl(B[3]), GM64_FMA(r, dbl(B[2]), dbl(B[1])));
+    const double p2 = GM64_FMA(r2, dbl(B[6]), GM64_FMA(r, dbl(B[5]), dbl(B[4])));
+    double p3 = GM64_FMA(r2, dbl(B[9]), GM64_FMA(r, dbl(B[8]), dbl(B[7])));
+    p3 = GM64_FMA(r3, dbl(B[10]), p3);
+    const double p = GM64_FMA(GM64_FMA(p3, r3, p2), r3, p1);
+    // r = rhi + rlo, rhi to 26 bits; hi + lo = r - rhi^2 / 2 (B[0] is -0.5)
+    const double two27 = 134217728.0;
+    const double rhi = GM64_FMA(-two27, r, GM64_FMA(r, two27, r));
+    const double rlo = r - rhi;
+    const double hh = rhi * rhi;
+    const double hi = GM64_FMA(hh, dbl(B[0]), r);
+    double lo = GM64_FMA(hh, dbl(B[0]), r - hi);
+    lo = GM64_FMA(dbl(B[0]) * rlo, r + rhi, lo);
+    return GM64_FMA(p, r3, lo) + hi;
+  }
+  if (top - 0x0010 >= 0x7ff0 - 0x0010) {  // x < 2^-1022, infinite or NaN
+    if (ix * 2 == 0) return dbl(0xfff0000000000000ULL);       // log(+-0) = -inf
+    if (ix == 0x7ff0000000000000ULL) return x;               // log(inf) = inf
+    if ((top & 0x8000) || (top & 0x7ff0) == 0x7ff0) {        // negative or NaN
+      const double d = x - x;
+      return d / d;
+    }
+    ix = bits(x * 4503599627370496.0);  // subnormal: scale by 2^52
+    ix -= 52ULL << 52;
+  }
+  // x = 2^k z, z in [0x1.6p-1, 0x1.6p0), row i holds 1/c and log(c) of a c near z
+  const uint64_t tmp = ix - 0x3fe6000000000000ULL;
+  const int i = (int)((tmp >> 45) & 127);
+  const int k = (int)((int64_t)tmp >> 52);
+  const double z = dbl(ix - (tmp & 0xfff0000000000000ULL));
+  const double invc = tab(kLogData, 18 + 2 * i), logc = tab(kLogData, 19 + 2 * i);
+  const double r = GM64_FMA(z, invc, -1.0);
+  const double kd = (double)k;
+  const double w = GM64_FMA(kd, tab(kLogData, 0), logc);
+  const double hi = w + r;
+  double lo = GM64_FMA(kd, tab(kLogData, 1), (w - hi) + r);
+  const double r2 = r * r;
+  lo = GM64_FMA(r2, dbl(A[0]), lo);
+  const double p = GM64_FMA(GM64_FMA(r, dbl(A[4]), dbl(A[3])), r2, GM64_FMA(r, dbl(A[2]), dbl(A[1])));
+  return GM64_FMA(r * r2, p, lo) + hi;
 }
 
 }  // namespace gm64

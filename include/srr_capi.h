@@ -364,6 +364,19 @@ void srr_image_free(unsigned char* pixels);
  * "triangle", "aabb"; and "sqrt" (records x, sqrtf(x)).  Needs a GPU. */
 int srr_device_kat(const char* name, int n, int width, float* records);
 
+/* Test infrastructure: one math routine of the device build over n elements
+ * (host buffers; one thread per element).  float elements: the wrappers the
+ * kernels call, "rsin", "rcos", "rexp", "rlog", "rpow" (x, y), "racos", "rasin",
+ * "ratan2" (y = x[], x = y[]: out0 = atan2f(x[i], y[i])), "rdiv" (x / y),
+ * "atanf", and "sincosf" (out0 = sine, out1 = cosine).  double elements: the
+ * MERL lookup's "sin64", "cos64", "sincos64" (two outputs), "acos64", "atan2_64"
+ * (out0 = atan2(x[i], y[i])), the medium's "log64", and the device libm's raw
+ * results, "ocml_sin", "ocml_cos", "ocml_pow5" (pow(x, 5.0)) behind the path
+ * kernels' three double calls that use it, and "ocml_log".  y / out1 may be NULL
+ * where the routine has one operand / one result.  Unknown names and bad
+ * arguments: SRR_EINVAL, decided before the GPU is touched.  Otherwise needs a GPU. */
+int srr_device_libm(const char* fn, int64_t n, const void* x, const void* y, void* out0, void* out1);
+
 /* Sobol (0,2)-points of Raytracing_n.cpp:721-812, out[n][2]. */
 int srr_sobol_points(int n, double* out);
 

@@ -25,6 +25,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -1580,6 +1581,58 @@ int oracle_teapot(float scale, int divs, float* out) {  // p0 p1 p2 normal per t
       for (int c = 0; c < 3; ++c) out[k++] = (*v)[c];
   }
   return (int)tris.size();
+}
+
+// The host's libm over an array (the libm every oracle path above runs on): the
+// reference of the device libm sweeps (tests/test_device_libm.py).  name: "expf",
+// "logf", "powf" (x, y), "sinf", "cosf", "sincosf" (two outputs), "acosf", "asinf",
+// "atanf", "atan2f" (atan2f(x[i], y[i])) on floats; "sin", "cos", "sincos" (two
+// outputs), "acos", "atan2" (atan2(x[i], y[i])), "log", "pow" (x, y) on doubles.
+// The array is split over `threads` threads (1..16).
+int oracle_libm(const char* name, long long n, const void* x, const void* y, void* out0, void* out1, int threads) {
+  if (!name || !x || !out0 || n < 0 || threads < 1 || threads > 16) {
+    orc::g_err = "oracle_libm: bad arguments";
+    return -1;
+  }
+  const std::string f = name;
+  const float *xf = (const float*)x, *yf = (const float*)y;
+  float *of = (float*)out0, *pf = (float*)out1;
+  const double *xd = (const double*)x, *yd = (const double*)y;
+  double *od = (double*)out0, *pd = (double*)out1;
+  std::function<void(long long)> one;
+  bool two_in = false, two_out = false;
+  if (f == "expf") one = [=](long long i) { of[i] = ::expf(xf[i]); };
+  else if (f == "logf") one = [=](long long i) { of[i] = ::logf(xf[i]); };
+  else if (f == "powf") two_in = true, one = [=](long long i) { of[i] = ::powf(xf[i], yf[i]); };
+  else if (f == "sinf") one = [=](long long i) { of[i] = ::sinf(xf[i]); };
+  else if (f == "cosf") one = [=](long long i) { of[i] = ::cosf(xf[i]); };
+  else if (f == "sincosf") two_out = true, one = [=](long long i) { ::sincosf(xf[i], &of[i], &pf[i]); };
+  else if (f == "acosf") one = [=](long long i) { of[i] = ::acosf(xf[i]); };
+  else if (f == "asinf") one = [=](long long i) { of[i] = ::asinf(xf[i]); };
+  else if (f == "atanf") one = [=](long long i) { of[i] = ::atanf(xf[i]); };
+  else if (f == "atan2f") two_in = true, one = [=](long long i) { of[i] = ::atan2f(xf[i], yf[i]); };
+  else if (f == "sin") one = [=](long long i) { od[i] = ::sin(xd[i]); };
+  else if (f == "cos") one = [=](long long i) { od[i] = ::cos(xd[i]); };
+  else if (f == "sincos") two_out = true, one = [=](long long i) { ::sincos(xd[i], &od[i], &pd[i]); };
+  else if (f == "acos") one = [=](long long i) { od[i] = ::acos(xd[i]); };
+  else if (f == "atan2") two_in = true, one = [=](long long i) { od[i] = ::atan2(xd[i], yd[i]); };
+  else if (f == "log") one = [=](long long i) { od[i] = ::log(xd[i]); };
+  else if (f == "pow") two_in = true, one = [=](long long i) { od[i] = ::pow(xd[i], yd[i]); };
+  else {
+    orc::g_err = "oracle_libm: no function named " + f;
+    return -1;
+  }
+  if ((two_in && !y) || (two_out && !out1)) {
+    orc::g_err = "oracle_libm: " + f + " needs a second operand or output";
+    return -1;
+  }
+  std::vector<std::thread> th;
+  for (int t = 0; t < threads; ++t)
+    th.emplace_back([&, t] {
+      for (long long i = n * t / threads, e = n * (t + 1) / threads; i < e; ++i) one(i);
+    });
+  for (auto& w : th) w.join();
+  return 0;
 }
 
 }  // extern "C"

@@ -841,6 +841,34 @@ int srr_device_kat(const char* name, int n, int width, float* records) {
   return rc;
 }
 
+int srr_device_libm(const char* fn, int64_t n, const void* x, const void* y, void* out0, void* out1) {
+  // every argument is checked before the first HIP call, so a refusal needs no GPU
+  // (tests/test_device_libm.py test_unknown_names_are_refused runs without one)
+  if (!fn || !x || !out0 || n <= 0 || n > (int64_t)1 << 30) return fail(SRR_EINVAL, "bad libm sweep arguments");
+  int k = -1;
+  for (int i = 0; i < kLibmFnCount; ++i)
+    if (!strcmp(fn, kLibmFns[i].name)) k = i;
+  if (k < 0) return fail(SRR_EINVAL, std::string("no device libm routine named ") + fn);
+  const LibmFn& f = kLibmFns[k];
+  if ((f.n_in == 2 && !y) || (f.n_out == 2 && !out1))
+    return fail(SRR_EINVAL, std::string("libm routine ") + fn + ": missing second operand or output");
+  const size_t b = (size_t)n * (f.f64 ? sizeof(double) : sizeof(float));
+  void* d[4] = {nullptr, nullptr, nullptr, nullptr};  // x, y, out0, out1
+  const bool use[4] = {true, f.n_in == 2, true, f.n_out == 2};
+  int rc = 0;
+  for (int i = 0; i < 4 && !rc; ++i)
+    if (use[i] && hipMalloc(&d[i], b) != hipSuccess) rc = fail(SRR_ENOMEM, "device allocation failed");
+  if (!rc && (hipMemcpy(d[0], x, b, hipMemcpyHostToDevice) != hipSuccess ||
+              (use[1] && hipMemcpy(d[1], y, b, hipMemcpyHostToDevice) != hipSuccess)))
+    rc = fail(SRR_EIO, "copy to device failed");
+  if (!rc && launch_libm(k, n, d[0], d[1], d[2], d[3]) < 0) rc = fail(SRR_EIO, "libm kernel launch failed");
+  if (!rc && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out0, d[2], b, hipMemcpyDeviceToHost) != hipSuccess ||
+              (use[3] && hipMemcpy(out1, d[3], b, hipMemcpyDeviceToHost) != hipSuccess)))
+    rc = fail(SRR_EIO, "libm kernel failed");
+  for (void* p : d) (void)hipFree(p);
+  return rc;
+}
+
 // ---- MERL tables (brdf.h)
 struct srr_merl {
   int device = 0;

@@ -8,7 +8,13 @@
 //  * the reference's float libm calls run glibc's own algorithms and tables
 //    (glibc_mathf.h: sinf, cosf, expf, logf, powf, acosf, asinf, atan2f --
 //    bit-exact with the host's libm);
-//  * double libm calls (sin/cos/log/pow of double) use the device double libm.
+//  * the medium's double log is glibc's own algorithm too (glibc_math64.h gm64::log):
+//    the device libm's log moved two of the 2^32 draws across a float rounding tie;
+//  * the other double libm calls (sin / cos of the Beckmann samplers, pow(x, 5.0) of the
+//    dielectric) use the device double libm.  Its doubles differ from glibc's in the
+//    last bit on 3.1 % (sin, cos) and 24 % (pow(x, 5.0)) of the inputs; the float each
+//    call site stores is the same on every sampled input and, for sin / cos, on every
+//    draw near a float rounding tie (tests/test_device_libm.py, DESIGN "GPU numerics").
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -33,7 +33,9 @@
 // asinf / atanf / atan2f are glibc's fdlibm float routines, restated.
 //
 // Special powf operands (zero / inf / nan / negative or subnormal x, results
-// beyond 2^+-126) take the double-precision route; the reference never meets them.
+// beyond 2^+-126) follow e_powf.c's own branches too: rounding a double pow() there
+// differed from libm's powf by 1 ulp on a few results per million above 2^126
+// (tests/test_device_libm.py).  The reference's own calls never meet them.
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -116,12 +118,53 @@ GM_FN float logf_(float x) {
   return (float)y;
 }
 
-// e_powf.c: exp2(y * log2(x)), both in double, x > 0 normal and y finite non-zero
+// e_powf.c checkint: 0 = y is not an integer, 1 = odd, 2 = even
+GM_FN int powf_checkint(uint32_t iy) {
+  const int e = iy >> 23 & 0xff;
+  if (e < 0x7f) return 0;
+  if (e > 0x7f + 23) return 2;
+  if (iy & ((1u << (0x7f + 23 - e)) - 1)) return 0;
+  if (iy & (1u << (0x7f + 23 - e))) return 1;
+  return 2;
+}
+GM_FN bool powf_zeroinfnan(uint32_t i) { return 2 * i - 1 >= 2u * 0x7f800000 - 1; }
+GM_FN bool powf_signaling(uint32_t i) { return 2 * (i ^ 0x00400000) > 2u * 0x7fc00000; }
+
+// e_powf.c: exp2(y * log2(x)), both in double; the special operands (zero, inf, NaN,
+// negative and subnormal x; y zero, inf, NaN) and the overflow / underflow range as
+// glibc handles them, so every operand pair gives libm's float
 GM_FN float powf_(float x, float y) {
-  const uint32_t ix = asuint(x), iy = asuint(y);
-  const bool y_zeroinfnan = 2 * iy - 1 >= 2u * 0x7f800000 - 1;
-  if (ix - 0x00800000 >= 0x7f800000 - 0x00800000 || y_zeroinfnan)
-    return (float)pow((double)x, (double)y);  // special operands, negative / subnormal x
+  uint32_t ix = asuint(x);
+  const uint32_t iy = asuint(y);
+  uint64_t sign_bias = 0;
+  if (ix - 0x00800000 >= 0x7f800000 - 0x00800000 || powf_zeroinfnan(iy)) {
+    if (powf_zeroinfnan(iy)) {
+      if (2 * iy == 0) return powf_signaling(ix) ? x + y : 1.0f;
+      if (ix == 0x3f800000) return powf_signaling(iy) ? x + y : 1.0f;
+      if (2 * ix > 2u * 0x7f800000 || 2 * iy > 2u * 0x7f800000) return x + y;
+      if (2 * ix == 2 * 0x3f800000u) return 1.0f;
+      if ((2 * ix < 2 * 0x3f800000u) == !(iy & 0x80000000)) return 0.0f;  // |x| < 1, y = inf or |x| > 1, y = -inf
+      return y * y;
+    }
+    if (powf_zeroinfnan(ix)) {
+      float x2 = x * x;
+      bool neg = false;
+      if ((ix & 0x80000000) && powf_checkint(iy) == 1) x2 = -x2, neg = true;
+      if (2 * ix == 0 && (iy & 0x80000000)) return neg ? -INFINITY : INFINITY;
+      return (iy & 0x80000000) ? 1 / x2 : x2;
+    }
+    if (ix & 0x80000000) {  // finite x < 0
+      const int yint = powf_checkint(iy);
+      if (yint == 0) return (x - x) / (x - x);
+      if (yint == 1) sign_bias = 1u << 16;
+      ix &= 0x7fffffff;
+    }
+    if (ix < 0x00800000) {  // subnormal x: normalise
+      ix = asuint(x * 0x1p23f);
+      ix &= 0x7fffffff;
+      ix -= 23 << 23;
+    }
+  }
   // log2_inline
   const uint32_t tmp = ix - 0x3f330000;
   const int i = (tmp >> (23 - 4)) % 16;
@@ -140,15 +183,19 @@ GM_FN float powf_(float x, float y) {
   q = GM_FMA(p, r2, q);
   const double logx = GM_FMA(yy, r4, q);
   const double ylogx = (double)y * logx;
-  if ((asuint64(ylogx) >> 47 & 0xffff) >= asuint64(126.0) >> 47)
-    return (float)pow((double)x, (double)y);  // |y log2 x| >= 126: over/underflow range
-  // exp2_inline (sign_bias 0)
+  if ((asuint64(ylogx) >> 47 & 0xffff) >= asuint64(126.0) >> 47) {  // |y log2 x| >= 126
+    const bool neg = sign_bias != 0;
+    if (ylogx > 0x1.fffffffd1d571p+6) return neg ? -INFINITY : INFINITY;  // |x^y| > 0x1.ffffffp127
+    if (ylogx <= -150.0) return neg ? -0.0f : 0.0f;
+    if (ylogx < -149.0) return neg ? -0x1p-149f : 0x1p-149f;  // __math_may_uflowf: 0x1.4p-75f squared
+  }
+  // exp2_inline
   double kd = ylogx + kExp2fShiftScaled;
   const uint64_t ki = asuint64(kd);
   kd -= kExp2fShiftScaled;
   const double rr = ylogx - kd;
   uint64_t t = kExp2fTab[ki % 32];
-  t += ki << (52 - 5);
+  t += (ki + sign_bias) << (52 - 5);
   const double s = asdouble(t);
   const double zz = GM_FMA(kExp2fPoly[0], rr, kExp2fPoly[1]);
   const double rr2 = rr * rr;

@@ -162,6 +162,36 @@ struct KatTables {
 };
 int launch_kat(int kind, int n, int w, float* d_rec, const float* d_aux, const DStandaloneTri* d_tris,
                const KatTables& kt);
+// device libm sweeps (srr_device_libm): routine kLibmFns[fn] over n elements, one per
+// thread; device pointers (d_y / d_out1 unused unless n_in / n_out is 2).  The switches
+// of kernels.hip k_libm_f32 / k_libm_f64 go by LibmId, and row i of the table is id i
+// (checked below); an id without a case writes NaN.
+enum LibmId : int {
+  kLibmRsin, kLibmRcos, kLibmRexp, kLibmRlog, kLibmRpow, kLibmRacos, kLibmRasin, kLibmRatan2, kLibmRdiv,
+  kLibmSincosf, kLibmAtanf, kLibmSin64, kLibmCos64, kLibmSincos64, kLibmAcos64, kLibmAtan2_64, kLibmLog64,
+  kLibmOcmlLog, kLibmOcmlSin, kLibmOcmlCos, kLibmOcmlPow5
+};
+struct LibmFn {
+  LibmId id;
+  const char* name;
+  int f64, n_in, n_out;
+};
+constexpr LibmFn kLibmFns[] = {
+    {kLibmRsin, "rsin", 0, 1, 1},          {kLibmRcos, "rcos", 0, 1, 1},         {kLibmRexp, "rexp", 0, 1, 1},
+    {kLibmRlog, "rlog", 0, 1, 1},          {kLibmRpow, "rpow", 0, 2, 1},         {kLibmRacos, "racos", 0, 1, 1},
+    {kLibmRasin, "rasin", 0, 1, 1},        {kLibmRatan2, "ratan2", 0, 2, 1},     {kLibmRdiv, "rdiv", 0, 2, 1},
+    {kLibmSincosf, "sincosf", 0, 1, 2},    {kLibmAtanf, "atanf", 0, 1, 1},       {kLibmSin64, "sin64", 1, 1, 1},
+    {kLibmCos64, "cos64", 1, 1, 1},        {kLibmSincos64, "sincos64", 1, 1, 2}, {kLibmAcos64, "acos64", 1, 1, 1},
+    {kLibmAtan2_64, "atan2_64", 1, 2, 1},  {kLibmLog64, "log64", 1, 1, 1},       {kLibmOcmlLog, "ocml_log", 1, 1, 1},
+    {kLibmOcmlSin, "ocml_sin", 1, 1, 1},   {kLibmOcmlCos, "ocml_cos", 1, 1, 1},  {kLibmOcmlPow5, "ocml_pow5", 1, 1, 1}};
+constexpr int kLibmFnCount = (int)(sizeof(kLibmFns) / sizeof(kLibmFns[0]));
+constexpr bool libm_table_in_id_order() {
+  for (int i = 0; i < kLibmFnCount; ++i)
+    if ((int)kLibmFns[i].id != i) return false;
+  return true;
+}
+static_assert(kLibmFnCount == kLibmOcmlPow5 + 1 && libm_table_in_id_order(), "kLibmFns[i] must be LibmId i");
+int launch_libm(int fn, int64_t n, const void* d_x, const void* d_y, void* d_out0, void* d_out1);
 // MERL table lookup (merl.h) for n queries; device pointers
 int launch_merl_lookup(const double* table, int64_t n, const double* angles, double* rgb, int32_t* cell);
 // acc[pixel] (+)= the window's samples in order; init: acc starts at 0 (no

@@ -1540,7 +1540,7 @@ SRR_D bool medium_hit(const SceneView& S, const DMedium& md, const Ray& r, float
   if (t1 < 0) t1 = 0;
   float len = length(r.d);
   float inside = (t2 - t1) * len;
-  float hit_distance = -(1 / md.density) * ::log(drand(rng));
+  float hit_distance = -(1 / md.density) * gm64::log(drand(rng));
   if (hit_distance < inside) {
     t = t1 + hit_distance / len;
     return true;
@@ -4302,6 +4302,67 @@ __global__ void k_kat(int kind, int n, int w, float* rec, const float* aux, cons
   }
 }
 
+// Test infrastructure (srr_device_libm): one libm routine of the device build over
+// an array, one element per thread.  fn is a LibmId (kernels.h).  The f32 entries are
+// the devmath.h wrappers the kernels call; the f64 ones the restatement of glibc's
+// double routines (glibc_math64.h: the MERL lookup's, and the medium's log) and the
+// device libm's raw double results (the three double calls of the path kernels that
+// still go to it, and its log for comparison).  An id without a case writes NaN.
+__global__ void __launch_bounds__(256) k_libm_f32(int fn, int64_t n, const float* __restrict__ x,
+                                                  const float* __restrict__ y, float* __restrict__ o0,
+                                                  float* __restrict__ o1) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float a = x[i];
+  switch (fn) {
+    case kLibmRsin: o0[i] = rsin(a); break;
+    case kLibmRcos: o0[i] = rcos(a); break;
+    case kLibmRexp: o0[i] = rexp(a); break;
+    case kLibmRlog: o0[i] = rlog(a); break;
+    case kLibmRpow: o0[i] = rpow(a, y[i]); break;
+    case kLibmRacos: o0[i] = racos(a); break;
+    case kLibmRasin: o0[i] = rasin(a); break;
+    case kLibmRatan2: o0[i] = ratan2(a, y[i]); break;
+    case kLibmRdiv: o0[i] = rdiv(a, y[i]); break;
+    case kLibmSincosf: {
+      float s, c;
+      gm::sincosf_(a, s, c);
+      o0[i] = s;
+      o1[i] = c;
+      break;
+    }
+    case kLibmAtanf: o0[i] = gm::atanf_(a); break;
+    default: o0[i] = __int_as_float(0x7fc00000); break;
+  }
+}
+
+__global__ void __launch_bounds__(256) k_libm_f64(int fn, int64_t n, const double* __restrict__ x,
+                                                  const double* __restrict__ y, double* __restrict__ o0,
+                                                  double* __restrict__ o1) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double a = x[i];
+  switch (fn) {
+    case kLibmSin64: o0[i] = gm64::sin(a); break;
+    case kLibmCos64: o0[i] = gm64::cos(a); break;
+    case kLibmSincos64: {
+      double s, c;
+      gm64::sincos(a, s, c);
+      o0[i] = s;
+      o1[i] = c;
+      break;
+    }
+    case kLibmAcos64: o0[i] = gm64::acos(a); break;
+    case kLibmAtan2_64: o0[i] = gm64::atan2(a, y[i]); break;
+    case kLibmLog64: o0[i] = gm64::log(a); break;  // constant_medium's hit distance
+    case kLibmOcmlLog: o0[i] = ::log(a); break;    // (what the hit distance used before)
+    case kLibmOcmlSin: o0[i] = ::sin(a); break;    // beckmann_sample11 / sample_wh at normal incidence
+    case kLibmOcmlCos: o0[i] = ::cos(a); break;
+    case kLibmOcmlPow5: o0[i] = ::pow(a, 5.0); break;  // schlick
+    default: o0[i] = __longlong_as_double(0x7ff8000000000000LL); break;
+  }
+}
+
 }  // namespace dev
 
 // ------------------------------------------------------------ launch shims
@@ -4562,6 +4623,18 @@ int launch_merl_lookup(const double* table, int64_t n, const double* angles, dou
 int launch_kat(int kind, int n, int w, float* d_rec, const float* d_aux, const DStandaloneTri* d_tris,
                const KatTables& kt) {
   hipLaunchKernelGGL(dev::k_kat, dim3((n + 63) / 64), dim3(64), 0, 0, kind, n, w, d_rec, d_aux, d_tris, kt);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+int launch_libm(int fn, int64_t n, const void* d_x, const void* d_y, void* d_out0, void* d_out1) {
+  if (fn < 0 || fn >= kLibmFnCount || n <= 0 || n > (int64_t)1 << 30) return -1;
+  const dim3 g((unsigned)((n + 255) / 256));
+  if (kLibmFns[fn].f64)
+    hipLaunchKernelGGL(dev::k_libm_f64, g, dim3(256), 0, 0, fn, n, (const double*)d_x, (const double*)d_y,
+                       (double*)d_out0, (double*)d_out1);
+  else
+    hipLaunchKernelGGL(dev::k_libm_f32, g, dim3(256), 0, 0, fn, n, (const float*)d_x, (const float*)d_y,
+                       (float*)d_out0, (float*)d_out1);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

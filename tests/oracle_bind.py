@@ -31,6 +31,9 @@ def lib():
         L.oracle_last_error.restype = ctypes.c_char_p
         L.oracle_sobol.argtypes = [ctypes.c_int, ctypes.c_void_p]
         L.oracle_teapot.argtypes = [ctypes.c_float, ctypes.c_int, ctypes.c_void_p]
+        L.oracle_libm.restype = ctypes.c_int
+        L.oracle_libm.argtypes = [ctypes.c_char_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
+                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         _LIB = L
     return _LIB
 
@@ -72,6 +75,25 @@ def replay_kat(name: str, rec: np.ndarray) -> np.ndarray:
     if rc != 0:
         raise RuntimeError(lib().oracle_last_error().decode())
     return out
+
+
+LIBM_F32 = ("expf", "logf", "powf", "sinf", "cosf", "sincosf", "acosf", "asinf", "atanf", "atan2f")
+LIBM_F64 = ("sin", "cos", "sincos", "acos", "atan2", "log", "pow")
+
+
+def libm(name: str, x, y=None, threads: int = 8):
+    """The host's libm (glibc), one call per element: the array(s) of results of
+    `name` (LIBM_F32 on float32, LIBM_F64 on float64; a pair for sincosf / sincos)."""
+    dt = np.float32 if name in LIBM_F32 else np.float64
+    x = np.ascontiguousarray(x, dtype=dt)
+    y = None if y is None else np.ascontiguousarray(y, dtype=dt)
+    assert y is None or y.shape == x.shape
+    out0 = np.empty_like(x)
+    out1 = np.empty_like(x) if name in ("sincosf", "sincos") else None
+    rc = lib().oracle_libm(name.encode(), x.size, _p(x), _p(y), _p(out0), _p(out1), threads)
+    if rc != 0:
+        raise RuntimeError(lib().oracle_last_error().decode())
+    return out0 if out1 is None else (out0, out1)
 
 
 def sobol(n: int) -> np.ndarray:

@@ -63,6 +63,11 @@ def test_criterion_matches_the_float32_restatement():
     want = [ar.converged(*c) for c in cases]
     assert got == want, [c for c, g, w in zip(cases, got, want) if g != w]
     assert any(want) and not all(want)
+    # the array form the pass loop uses decides each case as the scalar form does
+    for n, tol, eps in {(c[0], c[3], c[4]) for c in cases}:
+        sel = [c for c in cases if (c[0], c[3], c[4]) == (n, tol, eps)]
+        many = ar.converged_many(n, F([c[1] for c in sel]), F([c[2] for c in sel]), tol, eps)
+        assert many.tolist() == [ar.converged(*c) for c in sel], (n, tol, eps)
 
 
 @pytest.mark.parametrize("n,s1,tol,eps", [(16, 0.0, 0.1, 0.5), (64, 0.0, 0.02, 1e-3), (4, 0.5, 0.3, 1.0)])
@@ -107,6 +112,16 @@ def test_parity_frame_exercises_every_branch():
     assert np.unique(count).size >= 3
     assert count.min() >= ar.MIN_SPP and count.max() == ar.BUDGET
     assert ((count - ar.MIN_SPP) % ar.BATCH == 0).all()
+
+
+@pytest.mark.parametrize("ny", ar.BIG_NYS)
+def test_scan_chunk_frame_meets_its_precondition(ny):
+    """Condition on the inputs of the GPU scan-chunk test (tests/test_gpu_adaptive.py),
+    from the restatement alone: see adaptive_ref.check_big_frame."""
+    count, passes = ar.big_expected_counts(ny)
+    ar.check_big_frame(count, ny)
+    assert passes == 3
+    print("retired at 4 / 8 / 12 samples:", [int((count == c).sum()) for c in (4, 8, 12)])
 
 
 def test_pass_loop_restatement_limits():

@@ -111,6 +111,35 @@ def test_sample_windows_do_not_change_an_adaptive_frame(monkeypatch):
         np.testing.assert_array_equal(_bits(one["mean"][sel]), _bits(fixed[sel]))
 
 
+@pytest.mark.parametrize("ny", ar.BIG_NYS)
+def test_compaction_carries_across_scan_chunks(text, ny):
+    """300 x 220 = 66,000 pixels: 258 blocks of 256 rows, so the compaction's block
+    scan runs two chunks of 256 block counts and the second starts from the first
+    one's carry; the last block holds 208 rows.  300 x 440 = 132,000 pixels: 516
+    blocks in three chunks, and 18,824 rows of the second chunk survive the first
+    decision (adaptive_ref.check_big_frame), so a carry missing from a block's row
+    offset scatters them over the first chunk's and the later passes trace the wrong
+    pixels.  Counts are the restatement's, each pixel is bitwise the fixed-spp frame
+    of its own count, and the rays are the oracle's over each pixel's first n_i paths."""
+    nx, budget = ar.BIG_NX, ar.BIG_BUDGET
+    want, passes = ar.big_expected_counts(ny)
+    ar.check_big_frame(want, ny)
+    out = capi.Renderer(text).render_adaptive(nx, ny, budget, 50, batch_spp=ar.BIG_BATCH, min_spp=ar.BIG_MIN_SPP,
+                                              rel_tol=ar.BIG_REL_TOL, abs_eps=ar.ABS_EPS)
+    count, mean, st = out["count"], out["mean"], out["stats"]
+    np.testing.assert_array_equal(count, want)
+    for c in (4, 8, 12):
+        fixed = capi.Renderer(text).render(nx, ny, c, 50)["mean"]
+        sel = want == c
+        assert sel.any()
+        np.testing.assert_array_equal(_bits(mean[sel]), _bits(fixed[sel]), err_msg=f"pixels with {c} samples")
+    assert st["paths"] == int(want.sum())
+    assert st["passes"] == passes
+    assert st["pixels_retired"] == int((want < budget).sum())
+    taken = np.arange(budget)[None, :] < want[:, None]
+    assert st["world_rays"] == int(ar.big_oracle_frame(ny)["rays"].astype(np.int64)[taken].sum())
+
+
 def test_refusals_leave_the_renderer_usable(text):
     nx, ny = 16, 12
     want = capi.Renderer(text).render(nx, ny, 6, 50)["mean"]

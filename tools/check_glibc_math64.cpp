@@ -1,9 +1,10 @@
 // Bit-exactness check of include/srr/glibc_math64.h (glibc's dbl-64 sin / cos / acos /
-// atan2, restated) against the host libm, which the reference's brdf.h calls.
+// atan2 / log, restated) against the host libm, which the reference's brdf.h calls.
 // Sampled, since the inputs are 64-bit: uniform over each function's whole
 // domain by bit pattern, uniform by value over the reference's angle ranges,
 // every branch boundary of the restatement +-4096 ulps, and the MERL lookup's
-// own near-degenerate atan2 arguments (residues ~1e-17 against ~1).
+// own near-degenerate atan2 arguments (residues ~1e-17 against ~1).  log also runs
+// over its whole domain in the kernels: the 2^32 values k / 2^32 of the medium's draw.
 //   g++ -std=c++17 -O2 -mfma -ffp-contract=off -pthread tools/check_glibc_math64.cpp -o /tmp/chk64 && /tmp/chk64 [M]
 // (M: millions of samples per family, default 20)
 #include <atomic>
@@ -144,6 +145,28 @@ int main(int argc, char** argv) {
   run1("acos bit patterns", M, anyd, acosf_, racos);
   run1("acos near +-1", M, near1, acosf_, racos);
   run1("acos branch edges", M / 4, edge(acos_edges, 9), acosf_, racos);
+
+  // log: all bit patterns, the near-1 window, and every draw k / 2^32 of the medium (exhaustive)
+  auto log_ = [](double x) { return g::log(x); };
+  auto rlog = [](double x) { return ::log(x); };
+  auto win = [](std::mt19937_64& r) { return std::uniform_real_distribution<double>(0.93, 1.07)(r); };
+  run1("log  bit patterns", M, anyd, log_, rlog);
+  run1("log  near-1 window", M, win, log_, rlog);
+  {
+    const int T = std::max(1u, std::thread::hardware_concurrency());
+    std::atomic<unsigned long long> nbad{0};
+    std::vector<std::thread> th;
+    for (int k = 0; k < T; ++k)
+      th.emplace_back([&, k] {
+        for (uint64_t u = k; u < (1ull << 32); u += T) {
+          const double x = (double)u / 4294967296.0;
+          if (!same(g::log(x), ::log(x))) ++nbad;
+        }
+      });
+    for (auto& x : th) x.join();
+    printf("%-34s %12llu samples  %llu differ\n", "log  every drand k / 2^32", 1ull << 32, nbad.load());
+    if (nbad) return 1;
+  }
 
   // atan2: unit-circle directions (the half vector), all bit patterns, ratio edges,
   // and brdf's degenerate difference vectors: (residue, residue) with residues ~1e-17
