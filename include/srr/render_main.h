@@ -32,6 +32,14 @@
  *   --batch-spp 16 --min-spp 16  its samples per pass / fewest samples per pixel
  *   --count-map FILE             its per-pixel sample counts as a PNG of grey
  *                                levels 255 * count / ns
+ *   --denoise                    one GPU, with fixed spp or --adaptive: filter the
+ *                                frame with srr_denoise (its defaults) over the
+ *                                first-hit AOVs of srr_render_aov; --out is then
+ *                                the tone-mapped denoised frame
+ *   --aov-spp N                  samples of the AOVs (default min(ns, 16))
+ *   --aov-out PREFIX             write PREFIX_albedo.png (255.99 * albedo, clamped),
+ *                                PREFIX_normal.png (255.99 * (n / 2 + 1/2)) and
+ *                                PREFIX_depth.png (grey 255 * depth / max depth)
  * Differences, all forced by the reference: its render threads race on shared
  * state and its pixel mapping scrambles non-square frames (Q12);
  * srr renders every (pixel, sample) path with its per-path seed.  Exit codes:
@@ -69,10 +77,14 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
   double adaptive = -1;  // --adaptive REL_TOL (< 0: fixed spp)
   int batch_spp = 16, min_spp = 16;
   std::string count_map;
+  bool denoise = false;
+  int aov_spp = 0;  // 0: min(ns, 16)
+  std::string aov_out;
   auto usage = [&]() {
     std::fprintf(stderr, "usage: %s [--sceneid N | --scene NAME] [--nx N] [--ny N] [--ns N] [--max-depth N] "
                          "[--device N] [--gpus N | --devices a,b,..] [--tile N] [--out FILE] [--dry-run] "
-                         "[--adaptive REL_TOL [--batch-spp N] [--min-spp N] [--count-map FILE]]\nscenes:",
+                         "[--adaptive REL_TOL [--batch-spp N] [--min-spp N] [--count-map FILE]] "
+                         "[--denoise] [--aov-spp N] [--aov-out PREFIX]\nscenes:",
                  argv[0]);
     for (int k = 0; k < n_scenes; ++k) std::fprintf(stderr, " %d:%s", scenes[k].sceneid, scenes[k].name);
     std::fprintf(stderr, "\n");
@@ -107,6 +119,9 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
     else if (a == "--batch-spp") ok = num(batch_spp) && batch_spp >= 1;
     else if (a == "--min-spp") ok = num(min_spp) && min_spp >= 1;
     else if (a == "--count-map" && i + 1 < argc) count_map = argv[++i];
+    else if (a == "--denoise") denoise = true;
+    else if (a == "--aov-spp") ok = num(aov_spp) && aov_spp >= 1;
+    else if (a == "--aov-out" && i + 1 < argc) aov_out = argv[++i];
     else ok = false;
     if (!ok) return usage();
   }
@@ -115,6 +130,8 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
     if (name.empty() ? scenes[k].sceneid == sceneid : name == scenes[k].name) e = &scenes[k];
   if ((!e && text_path.empty()) || nx < 1 || ny < 1 || ns < 1) return usage();
   if (adaptive < 0 && !count_map.empty()) return usage();
+  if ((denoise || !aov_out.empty()) && (gpus > 1 || !devices.empty())) return usage();  // one GPU
+  if (aov_spp == 0) aov_spp = ns < 16 ? ns : 16;
   const char* scene_name = text_path.empty() ? e->name : text_path.c_str();
 
   srr_scene* s = nullptr;
@@ -171,7 +188,10 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
   p.max_depth = max_depth;
   p.tile = tile;
   p.shard_count = 1;
-  std::vector<unsigned char> rgb8(3 * (size_t)nx * ny);
+  const size_t npix = (size_t)nx * ny;
+  std::vector<unsigned char> rgb8(3 * npix);
+  const bool want_aov = denoise || !aov_out.empty();
+  std::vector<float> mean(want_aov ? 3 * npix : 0);
   srr_stats st{};
   const auto t0 = std::chrono::steady_clock::now();
   int rc;
@@ -186,13 +206,48 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
     ap.abs_eps = 1e-3f;
     ast.struct_size = sizeof ast;
     count.resize((size_t)nx * ny);
-    rc = srr_render_adaptive_host(r, &p, &ap, nullptr, count.data(), rgb8.data(), &ast);
+    rc = srr_render_adaptive_host(r, &p, &ap, want_aov ? mean.data() : nullptr, count.data(), rgb8.data(), &ast);
     st.world_rays = ast.world_rays;
   } else {
-    rc = srr_render(r, &p, nullptr, rgb8.data(), &st);
+    rc = srr_render(r, &p, want_aov ? mean.data() : nullptr, rgb8.data(), &st);
+  }
+  std::vector<float> albedo, normal, depth;
+  if (rc == 0 && want_aov) {
+    albedo.resize(3 * npix);
+    normal.resize(3 * npix);
+    depth.resize(npix);
+    srr_params pa = p;
+    pa.spp = aov_spp;
+    rc = srr_render_aov_host(r, &pa, SRR_AOV_ALBEDO | SRR_AOV_NORMAL | SRR_AOV_DEPTH, albedo.data(), normal.data(),
+                             depth.data());
+  }
+  if (rc == 0 && denoise) {
+    srr_denoise_params dp{};
+    std::vector<float> den(3 * npix);
+    rc = srr_denoise_defaults(&dp);
+    if (rc == 0)
+      rc = srr_denoise_host(devices[0], nx, ny, &dp, mean.data(), albedo.data(), normal.data(), depth.data(),
+                            den.data());
+    if (rc == 0) rc = srr_tonemap(den.data(), (int64_t)npix, rgb8.data());
   }
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (rc == 0) rc = srr_write_ppm(out.c_str(), nx, ny, rgb8.data());
+  if (rc == 0 && !aov_out.empty()) {
+    std::vector<unsigned char> img(3 * npix);
+    auto byte = [](float v) {  // 255.99 * v, clamped (the tone map's conversion without its sqrt)
+      const int k = (int)(255.99f * v);
+      return (unsigned char)(k < 0 ? 0 : k > 255 ? 255 : k);
+    };
+    for (size_t i = 0; i < 3 * npix; ++i) img[i] = byte(albedo[i]);
+    rc = srr_write_png((aov_out + "_albedo.png").c_str(), nx, ny, img.data());
+    for (size_t i = 0; i < 3 * npix; ++i) img[i] = byte(normal[i] * 0.5f + 0.5f);
+    if (rc == 0) rc = srr_write_png((aov_out + "_normal.png").c_str(), nx, ny, img.data());
+    float zmax = 0.f;
+    for (size_t i = 0; i < npix; ++i) zmax = depth[i] > zmax ? depth[i] : zmax;
+    for (size_t i = 0; i < npix; ++i)
+      img[3 * i] = img[3 * i + 1] = img[3 * i + 2] = byte(zmax > 0.f ? depth[i] / zmax : 0.f);
+    if (rc == 0) rc = srr_write_png((aov_out + "_depth.png").c_str(), nx, ny, img.data());
+  }
   if (rc == 0 && !count_map.empty()) {  // grey level 255 * count / ns, rounded down
     std::vector<unsigned char> grey(3 * count.size());
     for (size_t i = 0; i < count.size(); ++i) {

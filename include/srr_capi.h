@@ -314,6 +314,82 @@ int srr_render_adaptive_host(srr_renderer* r, const srr_params* p, const srr_ada
 /* The convergence rule above on the host (no GPU): 1 converged, 0 not. */
 int srr_adaptive_converged(int32_t n, float s1, float s2, float rel_tol, float abs_eps);
 
+/* ---- First-hit feature buffers (AOVs) for a denoiser (no reference counterpart).
+ * For every shard pixel and every sample of [p->sample_begin, p->sample_begin +
+ * p->spp) the PRIMARY ray of the beauty frame is traced (the same per-path seed,
+ * Sobol point, lens draw and time as that sample of srr_render_device) and tested
+ * with world->hit(r, 0.001, FLT_MAX).  Per sample:
+ *   albedo  by the hit's material: lambertian, orennayar, beckmann, diffuse_light,
+ *           isotropic: the material's texture at the hit's (u, v, p); metal: its
+ *           colour; dielectric: (1, 1, 1); a null material or a miss: (0, 0, 0).
+ *           It does not depend on the face that was hit.
+ *   normal  the hit record's normal as color() sees it (after the instance
+ *           transforms and flip_normals); (0, 0, 0) for a miss and for a
+ *           constant_medium hit (whose normal the reference sets arbitrarily).
+ *   depth   sqrtf(dot(p - o, p - o)), o the ray origin, p the hit point; 0 for a miss.
+ * Every component is de_nan'd and summed per pixel in sample order in float32;
+ * the result is sum * (float)(1.0 / (float)spp), the fold of the beauty frame: a
+ * buffer is a pure function of (scene, pixel, sample range).
+ * d_albedo, d_normal: DEVICE pointers of n_shard_pixels*3 floats; d_depth: DEVICE
+ * pointer of n_shard_pixels floats; all in srr_shard_pixels() order; a buffer may
+ * be NULL when its bit in `which` is clear.  p->max_depth and p->batch_paths
+ * (paths per batch, 0 = auto) are read as by srr_render_device.  Synchronous.
+ * SRR_EINVAL, before anything is allocated or enqueued, for a multi-device
+ * renderer, for SRR_FLAG_CONTINUE / KEEP_PATHS / COUNT_VISITS / SUMS, for which ==
+ * 0 or unknown bits in it, and for a needed pointer that is NULL.  The call uses
+ * buffers and a stream of its own: the renderer's progressive running sums, held
+ * pixel list and async frames are untouched (a SRR_FLAG_CONTINUE render after it
+ * continues as if it had not happened). */
+#define SRR_AOV_ALBEDO 1
+#define SRR_AOV_NORMAL 2
+#define SRR_AOV_DEPTH 4
+int srr_render_aov(srr_renderer* r, const srr_params* p, int which, float* d_albedo, float* d_normal,
+                   float* d_depth);
+/* The same with host buffers. */
+int srr_render_aov_host(srr_renderer* r, const srr_params* p, int which, float* albedo, float* normal, float* depth);
+
+/* ---- Feature-guided denoiser: an edge-avoiding a-trous wavelet filter (Dammertz,
+ * Sewtz, Hanika, Lensch 2010) over a colour image and the AOVs above.  Nothing of it
+ * is the reference's.  Inputs and the output are whole images in PPM order on HIP
+ * device `device`: nx*ny*3 floats (colour, albedo, normal, output), nx*ny floats
+ * (depth).  d_out must not overlap an input.
+ *
+ * Definition: every operation in float32, in exactly this order, without fused
+ * multiply-add; rdiv is IEEE division, rexp the float exponential of the host libm
+ * (expf), both as srr_device_libm exposes them.  c colour, a albedo, n normal, z depth.
+ *   Demodulate (SRR_DENOISE_DEMODULATE): per channel x = rdiv(c, a + 1e-3f); else x = c.
+ *   Iteration k = 0 .. iterations-1, step s = 1 << k, kc = k_c * 4^k (the factor is a
+ *   power of two: exact).  For pixel p visit the taps (dy, dx), dy = -2..2 outer,
+ *   dx = -2..2 inner, q = p + s*(dx, dy); a tap outside the image is skipped.
+ *     h  = B[|dx|] * B[|dy|],  B = {0.375f, 0.25f, 0.0625f}  (exact products)
+ *     dc = ((xq.r-xp.r)^2 + (xq.g-xp.g)^2) + (xq.b-xp.b)^2   (x of this iteration's input)
+ *     dn = the same form on the normals
+ *     dz = rdiv((zp-zq)*(zp-zq), (zp*zp + zq*zq) + 1e-20f)
+ *     w  = h * rexp(-((dc*kc + dn*k_n) + dz*k_z))
+ *     sum.ch += w * xq.ch per channel (r, g, b);  wsum += w      (both start at 0)
+ *   x'p.ch = rdiv(sum.ch, wsum)   (the centre tap makes wsum >= 9/64)
+ *   Remodulate (SRR_DENOISE_DEMODULATE): out = x * (a + 1e-3f); else out = x.
+ * tests/denoise_ref.py restates this in numpy, bit for bit.
+ * SRR_EINVAL, before the GPU is touched, for nx or ny outside 1..65536 or nx*ny > 2^28,
+ * iterations outside 1..6, a negative or non-finite k_c / k_n / k_z, unknown flags,
+ * a struct_size smaller than the struct below, a NULL buffer, and an output that
+ * overlaps an input. */
+#define SRR_DENOISE_DEMODULATE 1
+typedef struct srr_denoise_params {
+  uint32_t struct_size; /* sizeof(srr_denoise_params) of the caller */
+  int iterations;       /* 1..6 */
+  float k_c, k_n, k_z;  /* edge-stopping strengths of colour, normal, depth: >= 0, finite */
+  int flags;            /* SRR_DENOISE_DEMODULATE */
+} srr_denoise_params;
+/* The defaults (the sweep of DESIGN.md §4.2): struct_size, 3 iterations, k_c 256, k_n 32,
+ * k_z 64, no flags (SRR_DENOISE_DEMODULATE wins at 64 spp and loses at 16: see there). */
+int srr_denoise_defaults(srr_denoise_params* dp);
+int srr_denoise(int device, int nx, int ny, const srr_denoise_params* dp, const float* d_color,
+                const float* d_albedo, const float* d_normal, const float* d_depth, float* d_out);
+/* The same with host buffers. */
+int srr_denoise_host(int device, int nx, int ny, const srr_denoise_params* dp, const float* color,
+                     const float* albedo, const float* normal, const float* depth, float* out);
+
 /* Progressive rendering with resume: the renderer's per-pixel running sums
  * (3 floats per shard pixel, in srr_shard_pixels order) and the samples per pixel
  * they hold.  get: sums may be NULL to query npix / samples.  set: restores a saved

@@ -9,10 +9,12 @@
 #include <cstring>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/srr_capi.h"
+#include "denoise.h"
 #include "imageio.h"
 #include "meshio.h"
 #include "../../include/srr/merl.h"
@@ -553,6 +555,175 @@ int srr_render_adaptive_host(srr_renderer* r, const srr_params* p, const srr_ada
 
 int srr_adaptive_converged(int32_t n, float s1, float s2, float rel_tol, float abs_eps) {
   return adaptive_converged_host(n, s1, s2, rel_tol, abs_eps);
+}
+
+// ---- first-hit AOVs
+static int aov_check(const srr_renderer* r, const srr_params* p, int which, const void* a, const void* n,
+                     const void* z) {
+  if (!r || !p) return fail(SRR_EINVAL, "null argument");
+  if (r->multi) return fail(SRR_EINVAL, "srr_render_aov: one-device renderers only");
+  if (p->flags & (SRR_FLAG_CONTINUE | SRR_FLAG_KEEP_PATHS | SRR_FLAG_COUNT_VISITS | SRR_FLAG_SUMS))
+    return fail(SRR_EINVAL, "srr_render_aov: no CONTINUE, KEEP_PATHS, COUNT_VISITS, SUMS");
+  if (which == 0 || (which & ~(SRR_AOV_ALBEDO | SRR_AOV_NORMAL | SRR_AOV_DEPTH)))
+    return fail(SRR_EINVAL, "srr_render_aov: which must be a non-empty set of SRR_AOV_* bits");
+  if (((which & SRR_AOV_ALBEDO) && !a) || ((which & SRR_AOV_NORMAL) && !n) || ((which & SRR_AOV_DEPTH) && !z))
+    return fail(SRR_EINVAL, "srr_render_aov: a buffer selected in `which` is NULL");
+  if (p->spp < 1 || p->max_depth < 0 || p->max_depth > 64) return fail(SRR_EINVAL, "spp >= 1, 0 <= max_depth <= 64");
+  if (p->sample_begin < 0 || p->sample_begin > INT32_MAX - p->spp)
+    return fail(SRR_EINVAL, "sample_begin must be >= 0 and sample_begin + spp must fit in int32");
+  if (p->batch_paths < 0) return fail(SRR_EINVAL, "batch_paths must be >= 0");
+  return 0;
+}
+
+int srr_render_aov(srr_renderer* r, const srr_params* p, int which, float* d_albedo, float* d_normal,
+                   float* d_depth) {
+  // every refusal comes before anything is allocated or enqueued
+  if (const int rc = aov_check(r, p, which, d_albedo, d_normal, d_depth)) return rc;
+  const int64_t npix = srr_shard_pixels(p, nullptr);
+  if (npix < 0) return (int)npix;
+  if (npix == 0) return 0;
+  std::vector<int32_t> pix(npix);
+  srr_shard_pixels(p, pix.data());
+  std::string err;
+  const int rc = render_aov(r, p, pix.data(), npix, (which & SRR_AOV_ALBEDO) ? d_albedo : nullptr,
+                            (which & SRR_AOV_NORMAL) ? d_normal : nullptr, (which & SRR_AOV_DEPTH) ? d_depth : nullptr,
+                            err);
+  return rc < 0 ? fail(rc, err) : 0;
+}
+
+int srr_render_aov_host(srr_renderer* r, const srr_params* p, int which, float* albedo, float* normal, float* depth) {
+  if (const int rc = aov_check(r, p, which, albedo, normal, depth)) return rc;
+  const int64_t npix = srr_shard_pixels(p, nullptr);
+  if (npix < 0) return (int)npix;
+  if (npix == 0) return 0;
+  float* d = nullptr;  // albedo [3 npix], normal [3 npix], depth [npix]
+  HIPCHK(hipSetDevice(r->device));
+  HIPCHK(hipMalloc((void**)&d, 7 * npix * sizeof(float)));
+  int rc = srr_render_aov(r, p, which, d, d + 3 * npix, d + 6 * npix);
+  if (rc == 0) {
+    hipError_t e = hipSuccess;
+    if (which & SRR_AOV_ALBEDO) e = hipMemcpy(albedo, d, 3 * npix * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && (which & SRR_AOV_NORMAL))
+      e = hipMemcpy(normal, d + 3 * npix, 3 * npix * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && (which & SRR_AOV_DEPTH))
+      e = hipMemcpy(depth, d + 6 * npix, npix * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(SRR_EIO, hipGetErrorString(e));
+  }
+  hipFree(d);
+  return rc;
+}
+
+// ---- the a-trous denoiser (denoise.hip)
+static int denoise_check(int device, int nx, int ny, const srr_denoise_params* dp, const float* color,
+                         const float* albedo, const float* normal, const float* depth, const float* out) {
+  if (!dp) return fail(SRR_EINVAL, "srr_denoise: null params");
+  if (dp->struct_size < sizeof(srr_denoise_params))
+    return fail(SRR_EINVAL, "srr_denoise_params.struct_size " + std::to_string(dp->struct_size) +
+                                " is smaller than the " + std::to_string(sizeof(srr_denoise_params)) +
+                                " bytes this library reads");
+  if (device < 0) return fail(SRR_EINVAL, "srr_denoise: bad device");
+  if (nx < 1 || ny < 1 || nx > 65536 || ny > 65536 || (int64_t)nx * ny > ((int64_t)1 << 28))
+    return fail(SRR_EINVAL, "srr_denoise: 1 <= nx, ny <= 65536 and nx*ny <= 2^28");
+  if (dp->iterations < 1 || dp->iterations > 6) return fail(SRR_EINVAL, "srr_denoise: iterations must be 1..6");
+  for (const float k : {dp->k_c, dp->k_n, dp->k_z})
+    if (!(k >= 0.f) || !(k <= 3.402823466e38f))  // (NaN fails both comparisons)
+      return fail(SRR_EINVAL, "srr_denoise: k_c, k_n, k_z must be finite and >= 0");
+  if (dp->flags & ~SRR_DENOISE_DEMODULATE) return fail(SRR_EINVAL, "srr_denoise: unknown flags");
+  if (!color || !albedo || !normal || !depth || !out) return fail(SRR_EINVAL, "srr_denoise: null buffer");
+  const size_t n = (size_t)nx * ny * sizeof(float);
+  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + 3 * n;
+  const std::pair<const float*, size_t> in[] = {{color, 3 * n}, {albedo, 3 * n}, {normal, 3 * n}, {depth, n}};
+  for (const auto& b : in)
+    if ((uintptr_t)b.first < o1 && o0 < (uintptr_t)b.first + b.second)
+      return fail(SRR_EINVAL, "srr_denoise: the output overlaps an input");
+  return 0;
+}
+
+int srr_denoise_defaults(srr_denoise_params* dp) {
+  if (!dp) return fail(SRR_EINVAL, "null argument");
+  // chosen by the sweep of DESIGN.md §4.2 (profiles/r08/denoise.txt)
+  *dp = srr_denoise_params{(uint32_t)sizeof(srr_denoise_params), 3, 256.0f, 32.0f, 64.0f, 0};
+  return 0;
+}
+
+namespace {
+// scratch of srr_denoise, kept per device between calls: two colour images and
+// the guides, float4 per pixel each
+struct DenoiseScratch {
+  float4* buf = nullptr;
+  size_t cap = 0;  // pixels
+};
+std::mutex g_dn_mu;
+std::map<int, DenoiseScratch> g_dn_scratch;
+}  // namespace
+
+int srr_denoise(int device, int nx, int ny, const srr_denoise_params* dp, const float* d_color,
+                const float* d_albedo, const float* d_normal, const float* d_depth, float* d_out) {
+  // every refusal comes before the GPU is touched
+  if (const int rc = denoise_check(device, nx, ny, dp, d_color, d_albedo, d_normal, d_depth, d_out)) return rc;
+  static const int variant = [] {  // SRR_DENOISE_VARIANT: measurements only
+    const char* e = getenv("SRR_DENOISE_VARIANT");
+    if (e && !strcmp(e, "tile")) return (int)kDnTile;
+    if (e && !strcmp(e, "gather")) return (int)kDnGather;
+    return (int)kDnAuto;
+  }();
+  const size_t n = (size_t)nx * ny;
+  std::lock_guard<std::mutex> lock(g_dn_mu);
+  HIPCHK(hipSetDevice(device));
+  DenoiseScratch& W = g_dn_scratch[device];
+  if (n > W.cap) {
+    (void)hipFree(W.buf);
+    W.buf = nullptr;
+    W.cap = 0;
+    if (hipMalloc((void**)&W.buf, 3 * n * sizeof(float4)) != hipSuccess)
+      return fail(SRR_ENOMEM, "srr_denoise: hipMalloc of the scratch images failed");
+    W.cap = n;
+  }
+  float4* x[2] = {W.buf, W.buf + n};
+  float4* guide = W.buf + 2 * n;
+  const bool demod = (dp->flags & SRR_DENOISE_DEMODULATE) != 0;
+  hipStream_t st = nullptr;  // the caller's inputs were written on the legacy stream or are complete
+  launch_denoise_pack((int64_t)n, d_color, demod ? d_albedo : nullptr, d_normal, d_depth, x[0], guide, st);
+  for (int k = 0; k < dp->iterations; ++k) {
+    const bool last = k + 1 == dp->iterations;
+    DnIter I{};
+    I.nx = nx;
+    I.ny = ny;
+    I.step = 1 << k;
+    I.kc = dp->k_c * (float)(1 << (2 * k));
+    I.kn = dp->k_n;
+    I.kz = dp->k_z;
+    I.x_in = x[k & 1];
+    I.guide = guide;
+    I.x_out = last ? nullptr : x[(k & 1) ^ 1];
+    I.out = last ? d_out : nullptr;
+    I.albedo = last && demod ? d_albedo : nullptr;
+    launch_denoise_iter(I, variant, st);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+int srr_denoise_host(int device, int nx, int ny, const srr_denoise_params* dp, const float* color,
+                     const float* albedo, const float* normal, const float* depth, float* out) {
+  if (const int rc = denoise_check(device, nx, ny, dp, color, albedo, normal, depth, out)) return rc;
+  const size_t n = (size_t)nx * ny;
+  float* d = nullptr;  // colour, albedo, normal [3n each], depth [n], output [3n]
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(hipMalloc((void**)&d, 13 * n * sizeof(float)));
+  float *dc = d, *da = d + 3 * n, *dn = d + 6 * n, *dz = d + 9 * n, *dout = d + 10 * n;
+  hipError_t e = hipMemcpy(dc, color, 3 * n * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(da, albedo, 3 * n * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dn, normal, 3 * n * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dz, depth, n * sizeof(float), hipMemcpyHostToDevice);
+  int rc = e == hipSuccess ? srr_denoise(device, nx, ny, dp, dc, da, dn, dz, dout) : fail(SRR_EIO, hipGetErrorString(e));
+  if (rc == 0) {
+    e = hipMemcpy(out, dout, 3 * n * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(SRR_EIO, hipGetErrorString(e));
+  }
+  hipFree(d);
+  return rc;
 }
 
 int srr_render_wait(srr_renderer* r, int64_t ticket, srr_stats* stats) {

@@ -238,6 +238,23 @@ void launch_shade(const SceneView& S, const PathState& P, const int* lists, int 
                   hipStream_t st);
 void launch_accumulate(const PathState& P, const BatchInfo& B, float* acc, hipStream_t st);
 void launch_finish(const float* acc, float* mean, int64_t n, int ns, hipStream_t st);
+// ---- first-hit AOVs (srr_render_aov, renderer.cpp render_aov)
+// After launch_raygen (slot0 = act0 = 0) and launch_trace of a batch of n primary rays:
+// val[2p] = (albedo.rgb, depth), val[2p + 1] = (normal.xyz, 0) of path p, de_nan'd.
+void launch_aov_eval(const SceneView& S, const PathState& P, int n, float4* val, hipStream_t st);
+// acc[8 lp + c] (+)= the batch's spp_b samples of pixel lp in sample order (init: the
+// sums start from 0); finish: also the means sum * (float)(1.0 / (float)ns) to the
+// caller's buffers (nullptr: not asked for) at shard pixel p0 + lp.
+struct AovFold {
+  const float* val;  // [np][spp_b][8]
+  int np, spp_b;
+  float* acc;        // [np][8]
+  int init, finish, ns, p0;
+  float* albedo;
+  float* normal;
+  float* depth;
+};
+void launch_aov_fold(const AovFold& A, hipStream_t st);
 // image[index[i]] = packed[i] (float3 per pixel) for i < n: multi-device frame assembly
 void launch_scatter_pixels(const float* packed, const int32_t* index, int64_t n, float* image, hipStream_t st);
 

@@ -2890,6 +2890,91 @@ __global__ void __launch_bounds__(256) k_record(SceneView S, PathState P, const 
   }
 }
 
+// First-hit AOVs (srr_render_aov, include/srr_capi.h).  One thread per primary ray
+// of a batch that k_raygen laid out pixel-major in slots 0 .. n-1 and k_trace /
+// k_record resolved: val[2p] = (albedo.rgb, depth), val[2p + 1] = (normal.xyz, 0),
+// de_nan'd.  k_record writes no record for a null material, so that hit's record
+// is recomputed here with the same world_record.
+__global__ void __launch_bounds__(256) k_aov_eval(SceneView S, PathState P, int n, float4* __restrict__ val) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const int4 hw = ntl(&P.hit_w[p]);
+  V3 alb = v3(0.f), nrm = v3(0.f);
+  float depth = 0.f;
+  if (hw.x >= 0) {
+    const float4 ro = ntl(&P.ray_o[p]);
+    V3 hp, hn;
+    float hu, hv;
+    if (hw.w >= 0) {
+      const float4 a = ntl(&P.hit_p[p]), b = ntl(&P.hit_n[p]);
+      hp = v3(a.x, a.y, a.z);
+      hn = v3(b.x, b.y, b.z);
+      hu = a.w;
+      hv = b.w;
+    } else {
+      const float4 rdv = ntl(&P.ray_d[p]);
+      const Ray r{v3(ro.x, ro.y, ro.z), v3(rdv.x, rdv.y, rdv.z), ro.w};
+      const HitRec h = world_record(S, r, WorldHit{hw.x, hw.y, __int_as_float(hw.z)});
+      hp = h.p;
+      hn = h.n;
+      hu = h.u;
+      hv = h.v;
+    }
+    DObj ob = S.objs[hw.x];  // the primitive that was hit (hit_material)
+    if (ob.kind == OBJ_OBVH) ob = S.objs[hw.y];
+    else if (ob.kind == OBJ_SGROUP) ob = S.objs[S.sg_items[hw.y].obj];
+    if (ob.kind != OBJ_MEDIUM) nrm = hn;
+    const V3 d = hp - v3(ro.x, ro.y, ro.z);
+    depth = rsqrt_exact(dot(d, d));
+    if (hw.w >= 0) {
+      const DMat M = S.mats[hw.w];
+      if (M.kind == MAT_METAL) alb = v3(M.p[0], M.p[1], M.p[2]);
+      else if (M.kind == MAT_DIELECTRIC) alb = v3(1.f);
+      else alb = tex_value(S, M.tex, hu, hv, hp);
+    }
+  }
+  // de_nan (Raytracing_n.cpp:47-53)
+  if (!(alb.x == alb.x)) alb.x = 0;
+  if (!(alb.y == alb.y)) alb.y = 0;
+  if (!(alb.z == alb.z)) alb.z = 0;
+  if (!(nrm.x == nrm.x)) nrm.x = 0;
+  if (!(nrm.y == nrm.y)) nrm.y = 0;
+  if (!(nrm.z == nrm.z)) nrm.z = 0;
+  if (!(depth == depth)) depth = 0;
+  nts(&val[2 * (size_t)p], make_float4(alb.x, alb.y, alb.z, depth));
+  nts(&val[2 * (size_t)p + 1], make_float4(nrm.x, nrm.y, nrm.z, 0.f));
+}
+
+// The AOV fold: thread (pixel lp, word c of the pixel's 8) adds the batch's spp_b
+// samples of that word, in sample order, to acc[8 lp + c] (init: from 0); eight
+// neighbouring lanes read one path's 32 contiguous bytes.  finish: the frame's last
+// sample batch of these pixels; the means go out as sum * (float)(1.0 / (float)ns)
+// (k_finish) to the buffers that were asked for (words: albedo 0..2, depth 3,
+// normal 4..6), at shard pixel p0 + lp.
+__global__ void __launch_bounds__(256) k_aov_fold(const float* __restrict__ val, int np, int spp_b, float* acc,
+                                                  int init, int finish, int ns, int p0, float* albedo, float* normal,
+                                                  float* depth) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 8 * np) return;
+  const int lp = i >> 3, c = i & 7;
+  if (c == 7) return;
+  float s = init ? 0.f : acc[i];
+  const float* v = val + (size_t)lp * spp_b * 8 + c;
+  for (int k = 0; k < spp_b; ++k) s += v[(size_t)k * 8];
+  acc[i] = s;
+  if (!finish) return;
+  const float kinv = 1.0 / (float)ns;
+  const float m = s * kinv;
+  const size_t gp = (size_t)p0 + lp;
+  if (c < 3) {
+    if (albedo) albedo[3 * gp + c] = m;
+  } else if (c == 3) {
+    if (depth) depth[gp] = m;
+  } else if (normal) {
+    normal[3 * gp + (c - 4)] = m;
+  }
+}
+
 // Diagnostic probes (SRR_PROBE=1, timing attribution only): the trace kernel's
 // stages re-run over the same active rays with their results discarded.
 // MODE 0: load the ray; 1: + world list without meshes; 4: + mesh instance
@@ -4490,6 +4575,15 @@ void launch_accumulate(const PathState& P, const BatchInfo& B, float* acc, hipSt
 void launch_finish(const float* acc, float* mean, int64_t n, int ns, hipStream_t st) {
   int64_t g = (3 * n + 255) / 256;
   hipLaunchKernelGGL(dev::k_finish, dim3((unsigned)g), dim3(256), 0, st, acc, mean, n, ns);
+}
+
+void launch_aov_eval(const SceneView& S, const PathState& P, int n, float4* val, hipStream_t st) {
+  hipLaunchKernelGGL(dev::k_aov_eval, dim3((n + 255) / 256), dim3(256), 0, st, S, P, n, val);
+}
+void launch_aov_fold(const AovFold& A, hipStream_t st) {
+  const int64_t g = (8 * (int64_t)A.np + 255) / 256;
+  hipLaunchKernelGGL(dev::k_aov_fold, dim3((unsigned)g), dim3(256), 0, st, A.val, A.np, A.spp_b, A.acc, A.init,
+                     A.finish, A.ns, A.p0, A.albedo, A.normal, A.depth);
 }
 
 void launch_scatter_pixels(const float* packed, const int32_t* index, int64_t n, float* image, hipStream_t st) {

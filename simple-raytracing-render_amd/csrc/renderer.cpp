@@ -1269,6 +1269,136 @@ int render_device(srr_renderer* r, const srr_params* p, const int32_t* pix, int6
   return 0;
 }
 
+// ---- first-hit AOVs
+void free_aov(AovState& A) {
+  for (void* b : A.bufs) (void)hipFree(b);
+  A.bufs.clear();
+  (void)hipFree(A.acc);
+  (void)hipFree(A.pixels);
+  (void)hipFree(A.sobol);
+  if (A.st) (void)hipStreamDestroy(A.st);
+  A = AovState{};
+}
+
+template <class T>
+static hipError_t aov_alloc(AovState& A, T** p, size_t n) {
+  const hipError_t e = hipMalloc((void**)p, std::max<size_t>(n * sizeof(T), 16));
+  if (e == hipSuccess) A.bufs.push_back(*p);
+  return e;
+}
+
+// Per path in flight: PathState's depth-0 members (rays 32 B, RNG 16 B, depth 4 B, spec
+// 8 B, hit record 48 B), the active list (4 B), the family lists (16 B) and the values
+// (32 B): 160 B, 160 MiB at the default batch of 2^20 paths.
+static int ensure_aov(AovState& A, size_t n, size_t pix_chunk, size_t npix, int n_sobol, std::string& err) {
+  if (!A.st) RCHK(hipStreamCreateWithFlags(&A.st, hipStreamNonBlocking));
+  if (n > A.cap) {
+    for (void* b : A.bufs) (void)hipFree(b);
+    A.bufs.clear();
+    A.cap = 0;
+    PathState& P = A.P;
+    P = PathState{};
+    RCHK(aov_alloc(A, &P.ray_o, n));
+    RCHK(aov_alloc(A, &P.ray_d, n));
+    RCHK(aov_alloc(A, &P.lcg, n));
+    RCHK(aov_alloc(A, &P.pcg, n));
+    RCHK(aov_alloc(A, &P.depth, n));
+    RCHK(aov_alloc(A, &P.spec, n));
+    RCHK(aov_alloc(A, &P.hit_w, n));
+    RCHK(aov_alloc(A, &P.hit_p, n));
+    RCHK(aov_alloc(A, &P.hit_n, n));
+    RCHK(aov_alloc(A, &A.active, n));
+    RCHK(aov_alloc(A, &A.lists, 4 * n));
+    RCHK(aov_alloc(A, &A.cnt, 8));
+    RCHK(aov_alloc(A, &A.val, 2 * n));
+    A.cap = n;
+  }
+  if (npix > A.pix_cap) {
+    (void)hipFree(A.pixels);
+    (void)hipFree(A.acc);
+    A.pixels = nullptr;
+    A.acc = nullptr;
+    A.pix_cap = 0;
+    RCHK(hipMalloc((void**)&A.pixels, npix * sizeof(int32_t)));
+    RCHK(hipMalloc((void**)&A.acc, 8 * npix * sizeof(float)));
+    A.pix_cap = npix;
+  }
+  (void)pix_chunk;
+  if (n_sobol > A.sobol_n) {
+    (void)hipFree(A.sobol);
+    A.sobol = nullptr;
+    A.sobol_n = 0;
+    RCHK(hipMalloc((void**)&A.sobol, 2 * (size_t)n_sobol * sizeof(double)));
+    std::vector<double> sp(2 * (size_t)n_sobol);
+    sobol2((unsigned)n_sobol, sp.data());
+    RCHK(hipMemcpy(A.sobol, sp.data(), sp.size() * sizeof(double), hipMemcpyHostToDevice));
+    A.sobol_n = n_sobol;
+  }
+  return 0;
+}
+
+int render_aov(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t npix, float* d_albedo,
+               float* d_normal, float* d_depth, std::string& err) {
+  RCHK(hipSetDevice(r->device));
+  // batches as in render_device: a pixel chunk x a sample chunk of at most N paths;
+  // a pixel chunk sees all its sample chunks, in order, before the next one starts
+  const int64_t N = p->batch_paths > 0 ? p->batch_paths : (int64_t)1 << 20;
+  const int64_t pix_chunk = std::min<int64_t>(npix, N);
+  const int S = (int)std::max<int64_t>(1, std::min<int64_t>(p->spp, N / pix_chunk));
+  const int64_t region = pix_chunk * S;
+  if (region > INT32_MAX / 8) {
+    err = "batch_paths too large";
+    return SRR_EINVAL;
+  }
+  AovState& A = r->aov;
+  {  // every allocation comes before the first launch
+    const int rc = ensure_aov(A, (size_t)region, (size_t)pix_chunk, (size_t)npix, p->sample_begin + p->spp, err);
+    if (rc < 0) return rc;
+  }
+  RCHK(hipMemcpyAsync(A.pixels, pix, npix * sizeof(int32_t), hipMemcpyHostToDevice, A.st));
+  for (int64_t p0 = 0; p0 < npix; p0 += pix_chunk) {
+    const int np = (int)std::min<int64_t>(pix_chunk, npix - p0);
+    for (int s0 = 0; s0 < p->spp; s0 += S) {
+      BatchInfo B{};
+      B.active = A.active;
+      B.count = A.cnt;
+      B.act0 = 0;
+      B.slot0 = 0;
+      B.pixels = A.pixels;
+      B.sobol = A.sobol + 2 * (size_t)p->sample_begin;
+      B.s_base = p->sample_begin;
+      B.p0 = (int)p0;
+      B.spp_batch = std::min(S, p->spp - s0);
+      B.n_paths = np * B.spp_batch;
+      B.s0 = s0;
+      B.nx = p->nx;
+      B.ny = p->ny;
+      B.base_seed = p->base_seed;
+      RCHK(hipMemsetAsync(A.cnt, 0, 8 * sizeof(int32_t), A.st));
+      launch_raygen(r->view, A.P, B, A.st);
+      launch_trace(r->view, A.P, A.active, A.cnt, B.n_paths, A.lists, (int)A.cap, A.cnt + 1, A.cnt + 5, p->max_depth,
+                   nullptr, A.st);
+      launch_aov_eval(r->view, A.P, B.n_paths, A.val, A.st);
+      AovFold F{};
+      F.val = (const float*)A.val;
+      F.np = np;
+      F.spp_b = B.spp_batch;
+      F.acc = A.acc;
+      F.init = s0 == 0;
+      F.finish = s0 + B.spp_batch == p->spp;
+      F.ns = p->spp;
+      F.p0 = (int)p0;
+      F.albedo = d_albedo;
+      F.normal = d_normal;
+      F.depth = d_depth;
+      launch_aov_fold(F, A.st);
+    }
+  }
+  RCHK(hipGetLastError());
+  RCHK(hipStreamSynchronize(A.st));
+  return 0;
+}
+
 }  // namespace srr
 
 srr_renderer::~srr_renderer() {
@@ -1286,6 +1416,7 @@ srr_renderer::~srr_renderer() {
   (void)hipFree(pw_wave_times);
   (void)hipFree(pw_slow);
   srr::free_adaptive(adaptive);
+  srr::free_aov(aov);
   for (auto& L : lanes) {
     srr::free_lane_paths(L);
     (void)hipFree(L.cnt);

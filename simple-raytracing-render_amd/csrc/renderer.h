@@ -94,6 +94,25 @@ struct AdaptiveState {
   int32_t* n_host = nullptr;    // pinned mirror of the new active count
 };
 
+// Buffers of srr_render_aov (renderer.cpp render_aov): a stream, a pixel list, Sobol
+// points and depth-0 path state of its own, so the call leaves the frame state alone.
+struct AovState {
+  hipStream_t st = nullptr;
+  size_t cap = 0;       // paths the batch buffers hold
+  size_t pix_cap = 0;   // pixels the list and the sums hold
+  PathState P{};        // depth-0 state only: rays, RNG, depth, spec, hit record
+  int32_t* active = nullptr;
+  int32_t* lists = nullptr;  // launch_trace's 4 material-family lists [4][cap]
+  int32_t* cnt = nullptr;    // [0] active count, [1..4] family counts, [5] fetch
+  float4* val = nullptr;     // [cap][2] per-path values
+  float* acc = nullptr;      // [pixels of a chunk][8]
+  int32_t* pixels = nullptr;
+  double* sobol = nullptr;
+  int sobol_n = 0;
+  std::vector<void*> bufs;   // the batch buffers
+};
+void free_aov(AovState& A);
+
 struct Multi;  // multi.h
 }  // namespace srr
 
@@ -147,6 +166,7 @@ struct srr_renderer {
   size_t keep_cap = 0;
   int64_t kept_paths = 0;
   srr::AdaptiveState adaptive;
+  srr::AovState aov;
   ~srr_renderer();
 };
 
@@ -163,6 +183,10 @@ int render_device_async(srr_renderer* r, const srr_params* p, const int32_t* pix
 // srr_render_adaptive on a one-device renderer, its arguments already validated (capi.cpp)
 int render_adaptive(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, const int32_t* pix,
                     int64_t npix, float* d_mean, int32_t* d_count, srr_adaptive_stats* stats, std::string& err);
+// srr_render_aov on a one-device renderer, its arguments already validated (capi.cpp);
+// a nullptr buffer is not asked for
+int render_aov(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t npix, float* d_albedo,
+               float* d_normal, float* d_depth, std::string& err);
 int render_wait(srr_renderer* r, int64_t ticket, srr_stats* stats, std::string& err);
 void drain_async(srr_renderer* r);  // finish every async frame in flight (results kept for render_wait)
 // the event recorded after async frame `ticket`'s last operation (its slot's frame end),

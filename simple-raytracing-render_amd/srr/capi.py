@@ -19,6 +19,10 @@ FLAG_COUNT_VISITS = 4
 FLAG_WAVEFRONT = 8
 FLAG_CONTINUE = 16
 FLAG_SUMS = 32
+AOV_ALBEDO = 1
+AOV_NORMAL = 2
+AOV_DEPTH = 4
+DENOISE_DEMODULATE = 1
 
 
 class SrrError(RuntimeError):
@@ -54,6 +58,20 @@ class AdaptiveStats(ctypes.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
+class DenoiseParams(ctypes.Structure):
+    """srr_denoise_params; ``DenoiseParams.defaults()`` is srr_denoise_defaults."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("iterations", ctypes.c_int), ("k_c", ctypes.c_float),
+                ("k_n", ctypes.c_float), ("k_z", ctypes.c_float), ("flags", ctypes.c_int)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "DenoiseParams":
+        dp = cls()
+        _check(lib().srr_denoise_defaults(ctypes.byref(dp)))
+        for k, v in kw.items():
+            setattr(dp, k, v)
+        return dp
 
 
 def lib():
@@ -115,6 +133,13 @@ def lib():
                                                    vp, vp, ctypes.POINTER(AdaptiveStats)]
             L.srr_adaptive_converged.argtypes = [ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                                  ctypes.c_float]
+        if hasattr(L, "srr_denoise"):  # (as above)
+            dpp = ctypes.POINTER(DenoiseParams)
+            L.srr_render_aov.argtypes = [vp, ctypes.POINTER(Params), ip, vp, vp, vp]
+            L.srr_render_aov_host.argtypes = [vp, ctypes.POINTER(Params), ip, vp, vp, vp]
+            L.srr_denoise_defaults.argtypes = [dpp]
+            L.srr_denoise.argtypes = [ip, ip, ip, dpp, vp, vp, vp, vp, vp]
+            L.srr_denoise_host.argtypes = [ip, ip, ip, dpp, vp, vp, vp, vp, vp]
         _LIB = L
     return _LIB
 
@@ -288,6 +313,29 @@ class Renderer:
                                          ctypes.byref(st)))
         return st.as_dict()
 
+    def render_aov(self, nx, ny, spp, which=AOV_ALBEDO | AOV_NORMAL | AOV_DEPTH, max_depth=50, **kw):
+        """First-hit feature buffers (srr_render_aov_host) of the samples
+        [sample_begin, sample_begin + spp): dict(albedo[n,3], normal[n,3], depth[n])
+        with the buffers selected in `which`; kw as make_params."""
+        p = make_params(nx, ny, spp, max_depth, **kw)
+        n = shard_pixels(p).size
+        out = {}
+        if which & AOV_ALBEDO:
+            out["albedo"] = np.zeros((n, 3), np.float32)
+        if which & AOV_NORMAL:
+            out["normal"] = np.zeros((n, 3), np.float32)
+        if which & AOV_DEPTH:
+            out["depth"] = np.zeros(n, np.float32)
+        _check(lib().srr_render_aov_host(self.h, ctypes.byref(p), which, _ptr(out.get("albedo")),
+                                         _ptr(out.get("normal")), _ptr(out.get("depth"))))
+        return out
+
+    def render_aov_device(self, params: Params, which: int, d_albedo_ptr: int = 0, d_normal_ptr: int = 0,
+                          d_depth_ptr: int = 0) -> None:
+        """srr_render_aov into device buffers (e.g. torch tensors' data_ptr())."""
+        _check(lib().srr_render_aov(self.h, ctypes.byref(params), which, ctypes.c_void_p(d_albedo_ptr or None),
+                                    ctypes.c_void_p(d_normal_ptr or None), ctypes.c_void_p(d_depth_ptr or None)))
+
     def render_device(self, params: Params, d_mean_ptr: int) -> dict:
         """Render into a device buffer (e.g. a torch tensor's data_ptr())."""
         st = Stats()
@@ -312,6 +360,25 @@ class Renderer:
 def adaptive_converged(n, s1, s2, rel_tol, abs_eps) -> bool:
     """The convergence rule of srr_render_adaptive (srr_adaptive_converged; host, no GPU)."""
     return bool(lib().srr_adaptive_converged(int(n), float(s1), float(s2), float(rel_tol), float(abs_eps)))
+
+
+def denoise(color, albedo, normal, depth, params: DenoiseParams = None, device: int = 0) -> np.ndarray:
+    """The a-trous denoiser (srr_denoise_host) over whole images in PPM order:
+    color, albedo, normal [ny, nx, 3], depth [ny, nx] -> the filtered [ny, nx, 3]."""
+    color = np.ascontiguousarray(color, np.float32)
+    if color.ndim != 3 or color.shape[2] != 3:
+        raise SrrError("denoise needs color[ny, nx, 3]")
+    ny, nx = color.shape[:2]
+    albedo = np.ascontiguousarray(albedo, np.float32)
+    normal = np.ascontiguousarray(normal, np.float32)
+    depth = np.ascontiguousarray(depth, np.float32)
+    if albedo.size != color.size or normal.size != color.size or depth.size * 3 != color.size:
+        raise SrrError("denoise: albedo and normal need ny*nx*3 floats, depth ny*nx")
+    dp = params if params is not None else DenoiseParams.defaults()
+    out = np.zeros_like(color)
+    _check(lib().srr_denoise_host(device, nx, ny, ctypes.byref(dp), _ptr(color), _ptr(albedo), _ptr(normal),
+                                  _ptr(depth), _ptr(out)))
+    return out
 
 
 def tonemap(mean: np.ndarray) -> np.ndarray:

@@ -7,6 +7,10 @@ per-pixel running sums in sample order -- and its state saved and resumed in
 another process.  Per-path seeds and Sobol points depend only on (pixel, global
 sample index), so any chunking gives bitwise the image of one render of all the
 samples (tests/test_progressive.py).
+
+With ``denoise`` set, step() returns the a-trous filtered frame (srr_denoise over
+the first-hit AOVs, rendered once at ``aov_spp`` samples); the running sums and
+``mean`` stay the undenoised ones, so the filter never feeds back into the frame.
 """
 from __future__ import annotations
 
@@ -19,13 +23,21 @@ from . import capi
 
 
 class Progressive:
-    def __init__(self, renderer: "capi.Renderer", nx: int, ny: int, max_depth: int = 50, flags: int = 0, **params):
+    def __init__(self, renderer: "capi.Renderer", nx: int, ny: int, max_depth: int = 50, flags: int = 0,
+                 denoise=None, aov_spp: int = 16, **params):
         self.r = renderer
         self.nx, self.ny, self.max_depth = nx, ny, max_depth
         self.flags = flags  # engine flags (e.g. capi.FLAG_WAVEFRONT)
         self.params = params  # shard / tile / base_seed ... (capi.make_params keywords)
         self.samples = 0
         self.mean = None
+        # denoise: None / False (off), True (srr_denoise_defaults) or a capi.DenoiseParams
+        self.denoise = capi.DenoiseParams.defaults() if denoise is True else (denoise or None)
+        self.aov_spp = aov_spp
+        self.denoised = None
+        self._aov = None
+        if self.denoise is not None and params.get("shard", (0, 1))[1] > 1:
+            raise capi.SrrError("a denoised progressive frame is the whole image: no shard")
 
     def step(self, spp: int) -> np.ndarray:
         """Render the next `spp` samples of every pixel; returns the mean over all
@@ -35,7 +47,16 @@ class Progressive:
                             **self.params)
         self.samples += spp
         self.mean = out["mean"]
-        return self.mean
+        if self.denoise is None:
+            return self.mean
+        if self._aov is None:  # the AOV call leaves the running sums alone
+            kw = {k: v for k, v in self.params.items() if k in ("base_seed", "batch_paths")}
+            self._aov = self.r.render_aov(self.nx, self.ny, self.aov_spp, max_depth=self.max_depth, **kw)
+        shape = (self.ny, self.nx, 3)
+        a = self._aov
+        self.denoised = capi.denoise(self.mean.reshape(shape), a["albedo"].reshape(shape), a["normal"].reshape(shape),
+                                     a["depth"].reshape(self.ny, self.nx), self.denoise).reshape(-1, 3)
+        return self.denoised
 
     def image8(self) -> np.ndarray:
         return capi.tonemap(self.mean)

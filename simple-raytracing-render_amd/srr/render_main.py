@@ -9,6 +9,10 @@ format of Raytracing_n.cpp:850-886).
                               [--gpus N]   (srr_renderer_create_multi: one RCCL gather at frame end)
                               [--adaptive REL_TOL [--batch-spp 16] [--min-spp 16] [--count-map FILE]]
                                            (srr_render_adaptive: --ns is the per-pixel budget; one GPU)
+                              [--denoise [--aov-spp N] [--aov-out PREFIX]]
+                                           (srr_denoise over the first-hit AOVs of srr_render_aov; one GPU;
+                                            --out is the tone-mapped denoised frame; PREFIX_albedo.png,
+                                            PREFIX_normal.png, PREFIX_depth.png)
 
 Defaults are the reference's globals (Raytracing_n.cpp:39-43).  Differences, all
 forced by the reference: its 8 render threads race on shared state
@@ -47,7 +51,25 @@ def parse(argv=None):
     ap.add_argument("--min-spp", type=int, default=16, help="adaptive: no pixel stops with fewer samples")
     ap.add_argument("--count-map", default=None, metavar="FILE",
                     help="adaptive: PNG of the samples each pixel took, as grey level count / ns")
+    ap.add_argument("--denoise", action="store_true",
+                    help="filter the frame with the a-trous denoiser over its first-hit AOVs (one GPU)")
+    ap.add_argument("--aov-spp", type=int, default=None, help="samples of the AOVs (default min(ns, 16))")
+    ap.add_argument("--aov-out", default=None, metavar="PREFIX",
+                    help="write PREFIX_albedo.png, PREFIX_normal.png, PREFIX_depth.png")
     return ap.parse_args(argv)
+
+
+def aov_images(aov):
+    """The AOVs as 8-bit rgb: 255.99 * albedo, 255.99 * (normal / 2 + 1/2), grey 255.99 * depth / max."""
+    import numpy as np
+
+    def byte(v):
+        return (np.float32(255.99) * v.astype(np.float32)).astype(np.int64).clip(0, 255).astype(np.uint8)
+    z = aov["depth"]
+    zmax = z.max() if z.size else np.float32(0)
+    grey = byte(z / zmax if zmax > 0 else np.zeros_like(z))
+    return dict(albedo=byte(aov["albedo"]), normal=byte(aov["normal"] * np.float32(0.5) + np.float32(0.5)),
+                depth=np.repeat(grey[:, None], 3, axis=1))
 
 
 def count_map(count, max_spp):
@@ -65,12 +87,25 @@ def main(argv=None) -> int:
     if a.adaptive is None and a.count_map:
         print("--count-map needs --adaptive", file=sys.stderr)
         return 2
+    if (a.denoise or a.aov_out) and a.gpus != 1:
+        print("--denoise and --aov-out need one GPU", file=sys.stderr)
+        return 2
     t0 = time.perf_counter()
     if a.adaptive is not None:
         out = r.render_adaptive(a.nx, a.ny, a.ns, a.max_depth, batch_spp=a.batch_spp, min_spp=a.min_spp,
                                 rel_tol=a.adaptive, tile=1)
     else:
         out = r.render(a.nx, a.ny, a.ns, a.max_depth, tile=1)
+    if a.denoise or a.aov_out:
+        aov = r.render_aov(a.nx, a.ny, a.aov_spp or min(a.ns, 16), max_depth=a.max_depth)
+        if a.denoise:
+            shape = (a.ny, a.nx, 3)
+            den = capi.denoise(out["mean"].reshape(shape), aov["albedo"].reshape(shape), aov["normal"].reshape(shape),
+                               aov["depth"].reshape(a.ny, a.nx), device=a.device)
+            out["img8"] = capi.tonemap(den.reshape(-1, 3))
+        if a.aov_out:
+            for k, img in aov_images(aov).items():
+                capi.write_png(f"{a.aov_out}_{k}.png", a.nx, a.ny, img)
     ms = (time.perf_counter() - t0) * 1e3
     print(f"{int(ms)}ms")  # :944-947
     capi.write_ppm(a.out, a.nx, a.ny, out["img8"])
