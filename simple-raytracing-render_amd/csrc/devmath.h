@@ -52,7 +52,7 @@ SRR_D float rsqrt_exact(float x) {
 namespace srr {
 namespace dev {
 
-#ifndef SRR_LIBM_DOUBLE  // (A/B builds only: -DSRR_LIBM_DOUBLE rounds double libm results instead)
+// the reference's float libm calls: glibc's algorithms (glibc_mathf.h)
 SRR_D float rsin(float x) { return gm::sinf_(x); }
 SRR_D float rcos(float x) { return gm::cosf_(x); }
 SRR_D float rexp(float x) { return gm::expf_(x); }
@@ -61,16 +61,6 @@ SRR_D float rpow(float x, float y) { return gm::powf_(x, y); }
 SRR_D float racos(float x) { return gm::acosf_(x); }
 SRR_D float rasin(float x) { return gm::asinf_(x); }
 SRR_D float ratan2(float y, float x) { return gm::atan2f_(y, x); }
-#else
-SRR_D float rsin(float x) { return (float)::sin((double)x); }
-SRR_D float rcos(float x) { return (float)::cos((double)x); }
-SRR_D float rexp(float x) { return (float)::exp((double)x); }
-SRR_D float rlog(float x) { return (float)::log((double)x); }
-SRR_D float rpow(float x, float y) { return (float)::pow((double)x, (double)y); }
-SRR_D float racos(float x) { return (float)::acos((double)x); }
-SRR_D float rasin(float x) { return (float)::asin((double)x); }
-SRR_D float ratan2(float y, float x) { return (float)::atan2((double)y, (double)x); }
-#endif
 SRR_D float rdiv(float a, float b) { return __fdiv_rn(a, b); }
 
 static constexpr double kPi = 3.14159265358979323846;  // mathf.h:10

@@ -51,8 +51,8 @@ SRR_D bool sphere_hit(const DSphere& s, bool moving, const Ray& r, float tmin, f
   return false;
 }
 
-// rect_hit with the plane axis a compile-time constant (xy: 2, xz: 1, yz: 0), for the
-// world list's hit test (t only), dispatched on the rect's (uniform) axis
+// aarect.h:96-147 with the plane axis a compile-time constant (xy: 2, xz: 1, yz: 0): the
+// hit test (t only; rect_rec has u, v), dispatched on the rect's (uniform) axis
 template <int KAX>
 SRR_D bool rect_hit_t(const DRect& q, const Ray& r, float tmin, float tmax, float& t) {
   constexpr int A0 = KAX == 0 ? 1 : 0, A1 = KAX == 2 ? 1 : 2;
@@ -61,26 +61,6 @@ SRR_D bool rect_hit_t(const DRect& q, const Ray& r, float tmin, float tmax, floa
   const float x = r.o[A0] + tt * r.d[A0];
   const float y = r.o[A1] + tt * r.d[A1];
   if (x < q.lo0 || x > q.hi0 || y < q.lo1 || y > q.hi1) return false;
-  t = tt;
-  return true;
-}
-
-#ifndef SRR_RECTAX
-#define SRR_RECTAX 1  // rect tests specialised on the plane axis (A/B: -DSRR_RECTAX=0)
-#endif
-// aarect.h:96-147
-SRR_D bool rect_hit(const DRect& q, const Ray& r, float tmin, float tmax, float& t, float& u, float& v) {
-#ifdef SRR_EXP_FASTRECT  // timing probe only (not the reference's quotient)
-  float tt = (q.k - r.o[q.kax]) * __builtin_amdgcn_rcpf(r.d[q.kax]);
-#else
-  float tt = (q.k - r.o[q.kax]) / r.d[q.kax];
-#endif
-  if (tt < tmin || tt > tmax) return false;
-  float x = r.o[q.a0] + tt * r.d[q.a0];
-  float y = r.o[q.a1] + tt * r.d[q.a1];
-  if (x < q.lo0 || x > q.hi0 || y < q.lo1 || y > q.hi1) return false;
-  u = (x - q.lo0) / (q.hi0 - q.lo0);
-  v = (y - q.lo1) / (q.hi1 - q.lo1);
   t = tt;
   return true;
 }
@@ -253,10 +233,9 @@ SRR_D T wload(const T* p, int i) {
 // World-list tables are read at wave-uniform addresses (every active lane is at
 // the same object), but the compiler cannot know the loaded words are uniform:
 // uni() moves them to scalar registers, so the dispatch on object / transform
-// kinds becomes scalar branches instead of exec-mask regions (SRR_UNIFORM)
-#ifndef SRR_UNIFORM
-#define SRR_UNIFORM 1
-#endif
+// kinds becomes scalar branches instead of exec-mask regions.  The world list and
+// a medium's boundary list read this way (U = true); an object BVH's leaves and the
+// wavefront engine's per-lane object tests, whose lanes diverge, do not
 template <class T>
 SRR_D T uni(T v) {
   static_assert(sizeof(T) % 4 == 0, "uni: whole words");
@@ -414,43 +393,21 @@ SRR_D void mesh_scan_nan(const SceneView& S, const DMesh& m, const Ray& r, bool 
 
 // A slab's running entry / exit over the axes, from -inf / +inf (never NaN): the
 // reference's `t0 > tmin ? t0 : tmin` keeps tmin for a NaN t0, as fmaxf does (and a
-// +-0 difference compares equal everywhere the entry is used), so with SRR_FMINMAX the
-// compare + select pairs become single v_max_f32 / v_min_f32
-#ifndef SRR_FMINMAX
-#define SRR_FMINMAX 1  // (A/B: -DSRR_FMINMAX=0)
-#endif
-#if SRR_FMINMAX
-#define SRR_SMAX(n, acc) fmaxf((n), (acc))
-#define SRR_SMIN(f, acc) fminf((f), (acc))
-#else
-#define SRR_SMAX(n, acc) ((n) > (acc) ? (n) : (acc))
-#define SRR_SMIN(f, acc) ((f) < (acc) ? (f) : (acc))
-#endif
-
-// SRR_SLIM: in mesh_hit4's walk (whose lanes never carry a NaN bound: those took
-// the fold over all triangles), a child's [max(entry, tmin), min(exit, tmax)] by
-// fmaxf / fminf, and the child sort's swap test on the entries alone (a child not
-// taken has entry +inf and node -1; a taken child's entry is finite or -inf)
-#ifndef SRR_SLIM
-#define SRR_SLIM 1  // (A/B: -DSRR_SLIM=0)
-#endif
-#if SRR_SLIM
-#define SRR_CMAX(x, t) fmaxf((x), (t))
-#define SRR_CMIN(x, t) fminf((x), (t))
-#define SRR_CSWAP_IF(a, b) (kt[b] < kt[a])
-#else
-#define SRR_CMAX(x, t) ((x) > (t) ? (x) : (t))
-#define SRR_CMIN(x, t) ((x) < (t) ? (x) : (t))
-#define SRR_CSWAP_IF(a, b) (kn[b] >= 0 && (kn[a] < 0 || kt[b] < kt[a]))
-#endif
+// +-0 difference compares equal everywhere the entry is used), so the compare +
+// select pairs are written as fmaxf / fminf: single v_max_f32 / v_min_f32.
+//
+// In mesh_hit4's walk (whose lanes never carry a NaN bound: those took the fold
+// over all triangles) a child's [max(entry, tmin), min(exit, tmax)] is taken by
+// fmaxf / fminf too, and the child sort's swap test reads the entries alone (a child
+// not taken has entry +inf and node -1; a taken child's entry is finite or -inf)
 
 // one axis of a slab test on the whole line (as SRR_CHILD's): entry / exit
 SRR_D void slab_axis(float L, float H, float O, float I, float& lo, float& hi) {
   const float t0 = (L - O) * I, t1 = (H - O) * I;
   const bool sw = I < 0.0f;
   const float n = sw ? t1 : t0, f = sw ? t0 : t1;
-  lo = SRR_SMAX(n, lo);
-  hi = SRR_SMIN(f, hi);
+  lo = fmaxf(n, lo);
+  hi = fminf(f, hi);
 }
 
 // A compressed node's box bound (device_scene.h kNode4qWords): o + q * s with
@@ -465,23 +422,10 @@ SRR_D float q_bound(float o, float s, uint32_t w, int c) { return o + (float)((w
 // exact box, recomputed from the leaf's 1-2 triangles (ffmin / ffmax of the
 // vertices: the reference's triangle / bvh_node box, triangle.h:53-68) with the
 // reference's slab arithmetic -- the same leaf set as the 128-B nodes.
-#ifndef SRR_LEAFQ
-#define SRR_LEAFQ 1
-#endif
-constexpr bool LEAFQ = SRR_LEAFQ != 0;  // mesh_hit4's leaf-triangle queue (A/B: -DSRR_LEAFQ=0)
-#ifndef SRR_TRIPF
-#define SRR_TRIPF 1
-#endif
-#ifndef SRR_TOPREG
-#define SRR_TOPREG 1  // the stack's top entry kept in registers (A/B: -DSRR_TOPREG=0)
-#endif
-#ifndef SRR_EDGEREC
-#define SRR_EDGEREC 1  // leaf pairs from packed p0 / e1 / e2 records (A/B: -DSRR_EDGEREC=0)
-#endif
-#ifndef SRR_LEAFPAIR
-#define SRR_LEAFPAIR 1  // one leaf (both triangles) per pass of the leaf queue (A/B: -DSRR_LEAFPAIR=0)
-#endif
-
+// The 128-B walk (!Q) gathers the leaf children a step hit into a queue and tests
+// one leaf -- both its triangles, from the packed p0 / e1 / e2 record -- per pass;
+// the stack's top entry is kept in registers.
+//
 // SUSP: the walk may stop part-way (TraceCtx::walk_thr) and continue in a later
 // call with TraceCtx::resume; its state at the loop top -- next node, stack depth
 // and top entry (the deeper entries stay in the lane's LDS stack and global
@@ -489,7 +433,7 @@ constexpr bool LEAFQ = SRR_LEAFQ != 0;  // mesh_hit4's leaf-triangle queue (A/B:
 template <bool PRUNE, bool TIMING = false, bool Q = false, int STRIDE = kTraceBlock, bool SUSP = false>
 SRR_D bool mesh_hit4(const SceneView& S, const DMesh& m, const Ray& r, float tmin, float tmax, bool is_medium,
                      MeshHit& out, const TraceCtx& cx) {
-  static_assert(!SUSP || (SRR_TOPREG && !Q), "suspendable walks: the register top entry, 128-B nodes");
+  static_assert(!SUSP || !Q, "suspendable walks: 128-B nodes");
   if (const uint64_t nanm = __ballot(!(tmax == tmax))) {  // NaN bound: the fold over all triangles
     bool f = false;
     float bt = 0;
@@ -520,10 +464,8 @@ SRR_D bool mesh_hit4(const SceneView& S, const DMesh& m, const Ray& r, float tmi
   // (step-part stamps; per lane: the longest walk's lane was in every step of the wave)
   uint64_t ts = TIMING ? __builtin_amdgcn_s_memtime() : 0, sp0 = 0, sp1 = 0, sp2 = 0, slf = 0;
   int spass = 0;
-#if SRR_TOPREG
   int top_n = -1;
   float top_t = 0.f;
-#endif
   if constexpr (SUSP) {
     if (cx.resume) {  // the walk this lane suspended in an earlier wave-iteration, if it is this object's
       const float4 b = *walk_save(cx, 1);
@@ -597,7 +539,7 @@ SRR_D bool mesh_hit4(const SceneView& S, const DMesh& m, const Ray& r, float tmi
     SRR_SLAB_AX(LX.C, HX.C, r.o.x, inv.x) SRR_SLAB_AX(LY.C, HY.C, r.o.y, inv.y)          \
     SRR_SLAB_AX(LZ.C, HZ.C, r.o.z, inv.z)                                                \
     near[c] = lo_;                                                                       \
-    const float a_ = SRR_CMAX(lo_, tmin), b_ = SRR_CMIN(hi_, tmax);                      \
+    const float a_ = fmaxf(lo_, tmin), b_ = fminf(hi_, tmax);                            \
     hit[c] = !(b_ <= a_) && !(PRUNE && lo_ > bound);                                     \
   }
 #define SRR_SLAB_AX(L, H, O, I)                      \
@@ -605,14 +547,14 @@ SRR_D bool mesh_hit4(const SceneView& S, const DMesh& m, const Ray& r, float tmi
     float t0 = (L - O) * I, t1 = (H - O) * I;        \
     bool sw = I < 0.0f;                              \
     float n_ = sw ? t1 : t0, f_ = sw ? t0 : t1;      \
-    lo_ = SRR_SMAX(n_, lo_);                         \
-    hi_ = SRR_SMIN(f_, hi_);                         \
+    lo_ = fmaxf(n_, lo_);                            \
+    hi_ = fminf(f_, hi_);                            \
   }
     SRR_CHILD(0, x) SRR_CHILD(1, y) SRR_CHILD(2, z) SRR_CHILD(3, w)
 #undef SRR_SLAB_AX
 #undef SRR_CHILD
     const int ch[4] = {CH.x, CH.y, CH.z, CH.w};
-    if constexpr (!Q && LEAFQ) {
+    if constexpr (!Q) {
       // The leaf children this step hit, as a queue of (leaf, triangle) work: one
       // pass of the loop tests one triangle of every lane that has one, whatever
       // child slot its leaves sit in (slot by slot, a wave ran the triangle test
@@ -631,21 +573,17 @@ SRR_D bool mesh_hit4(const SceneView& S, const DMesh& m, const Ray& r, float tmi
         else if (q2 < 0) q2 = leaf;
         else q3 = leaf;
       }
-      int sub = 0;  // triangle of leaf q0 under test
       if (TIMING) asm volatile("" ::"v"(q0), "v"(q3), "v"(near[0]), "v"(near[3]));
       const uint64_t tl_enter = TIMING ? __builtin_amdgcn_s_memtime() : 0;
       if (TIMING) sp1 += tl_enter - ts;
       int npass = 0;
-#if SRR_LEAFPAIR
       // one pass per leaf: both its triangles' vertices are loaded together (a
       // one-triangle leaf loads its triangle twice, from L1) and tested, so a pass
       // waits for one round trip per leaf, not one per triangle
-      (void)sub;
       while (q0 >= 0) {
         if (TIMING) ++npass;
         const int t0 = q0 >> 1;
         const bool two = (q0 & 1) != 0;
-#if SRR_EDGEREC
         if (!is_medium) {  // the packed edge record of t0: p0, e1, e2 of t0 and t0 + 1
           const float4* lp = S.tri_edge + 8 * (size_t)t0;
           const float4 w0 = lp[0], w1 = lp[1], w2 = lp[2], w3 = lp[3];
@@ -671,7 +609,6 @@ SRR_D bool mesh_hit4(const SceneView& S, const DMesh& m, const Ray& r, float tmi
           q3 = -1;
           continue;
         }
-#endif
         const float4* tp = S.tri_pos + kTriStride * (size_t)t0;
         const float4* tq = tp + (two ? kTriStride : 0);
         const float4 a0 = tp[0], b0 = tp[1], c0 = tp[2];
@@ -699,55 +636,6 @@ SRR_D bool mesh_hit4(const SceneView& S, const DMesh& m, const Ray& r, float tmi
         q2 = q3;
         q3 = -1;
       }
-#else
-#if SRR_TRIPF
-      // software pipelined: the next triangle's vertices are in flight while
-      // this one is tested (one L2 / Infinity Cache latency per pass, not two)
-      float4 na{}, nb{}, nc{};
-      if (q0 >= 0) {
-        const float4* tp = S.tri_pos + kTriStride * (size_t)(q0 >> 1);
-        na = tp[0], nb = tp[1], nc = tp[2];
-      }
-#endif
-      while (q0 >= 0) {
-        if (TIMING) ++npass;
-        const int ti = (q0 >> 1) + sub;
-#if SRR_TRIPF
-        const float4 a = na, b = nb, cc = nc;
-        {
-          const int nti = (sub == 0 && (q0 & 1)) ? ti + 1 : (q1 >= 0 ? (q1 >> 1) : -1);
-          if (nti >= 0) {
-            const float4* tp = S.tri_pos + kTriStride * (size_t)nti;
-            na = tp[0], nb = tp[1], nc = tp[2];
-          }
-        }
-#else
-        const float4* tp = S.tri_pos + kTriStride * (size_t)ti;
-        const float4 a = tp[0], b = tp[1], cc = tp[2];
-#endif
-        const V3 p0 = v3(a.x, a.y, a.z), p1 = v3(b.x, b.y, b.z), p2 = v3(cc.x, cc.y, cc.z);
-        float t, u, v;
-        bool h = tri_hit(p0, p1, p2, true, r.o, dir, t, u, v);
-        if (!h && is_medium) h = tri_hit(p0, p1, p2, false, r.o, dir, t, u, v);
-        if (h && (!found || wins(t, ti, best_t, best_i))) {
-          found = true;
-          best_t = t;
-          best_i = ti;
-        }
-        // shrink only with ordered compares: a NaN bound (the reference passes
-        // every box then) or a NaN best keeps the bound as it is
-        if (PRUNE && found && best_t * to_param < bound) bound = best_t * to_param;
-        if (sub == 0 && (q0 & 1)) {
-          sub = 1;
-        } else {
-          sub = 0;
-          q0 = q1;
-          q1 = q2;
-          q2 = q3;
-          q3 = -1;
-        }
-      }
-#endif
       if (TIMING) {
         spass += npass;
         ts = __builtin_amdgcn_s_memtime();
@@ -806,13 +694,12 @@ SRR_D bool mesh_hit4(const SceneView& S, const DMesh& m, const Ray& r, float tmi
       kn[c] = take ? ch[c] : -1;
     }
 #define SRR_CSWAP(a, b)                                          \
-  if (SRR_CSWAP_IF(a, b)) {                                      \
+  if (kt[b] < kt[a]) {                                           \
     float tt_ = kt[a]; kt[a] = kt[b]; kt[b] = tt_;               \
     int nn_ = kn[a]; kn[a] = kn[b]; kn[b] = nn_;                 \
   }
     SRR_CSWAP(0, 1) SRR_CSWAP(2, 3) SRR_CSWAP(0, 2) SRR_CSWAP(1, 3) SRR_CSWAP(1, 2)
 #undef SRR_CSWAP
-#if SRR_TOPREG
     // the stack's top entry is also kept in registers (top_n, top_t: entry sp - 1
     // whenever sp > 0), so a pop has its node at once and reads the entry below it
     // from LDS while the next step runs
@@ -867,43 +754,6 @@ SRR_D bool mesh_hit4(const SceneView& S, const DMesh& m, const Ray& r, float tmi
       node = nx;
       continue;
     }
-#else
-    if (kn[0] >= 0) {
-      node = kn[0];
-#pragma unroll
-      for (int c = 3; c >= 1; --c) {
-        if (kn[c] < 0) continue;
-        if (sp < cx.st_cap) {
-          cx.st_node[sp * STRIDE] = kn[c];
-          cx.st_t[sp * STRIDE] = kt[c];
-          ++sp;
-        } else if (sp < cx.st_cap + cx.gst_cap) {
-          cx.gst[(size_t)(sp - cx.st_cap) * cx.gst_stride + cx.slot] = make_int2(kn[c], __float_as_int(kt[c]));
-          ++sp;
-          deep = true;
-        } else {
-          overflow = true;
-        }
-      }
-      continue;
-    }
-    // pop the nearest pending subtree that may still hold a closer hit
-    int nx = -1;
-    while (sp > 0) {
-      --sp;
-      int cand;
-      float ct;
-      if (sp < cx.st_cap) {
-        cand = cx.st_node[sp * STRIDE];
-        ct = cx.st_t[sp * STRIDE];
-      } else {
-        const int2 e = cx.gst[(size_t)(sp - cx.st_cap) * cx.gst_stride + cx.slot];
-        cand = e.x;
-        ct = __int_as_float(e.y);
-      }
-      if (!(PRUNE && ct > bound)) { nx = cand; break; }
-    }
-#endif
     if (nx < 0) break;
     node = nx;
   }
@@ -1087,8 +937,8 @@ SRR_D bool mesh_hit4_quad(const SceneView& S, const DMesh& m, const Ray& r, floa
     float t0 = (L - O) * I, t1 = (H - O) * I;    \
     bool sw = I < 0.0f;                          \
     float n_ = sw ? t1 : t0, f_ = sw ? t0 : t1;  \
-    lo_ = SRR_SMAX(n_, lo_);                     \
-    hi_ = SRR_SMIN(f_, hi_);                     \
+    lo_ = fmaxf(n_, lo_);                        \
+    hi_ = fminf(f_, hi_);                        \
   }
         SRR_QAX(lx, hx, o.x, iv.x) SRR_QAX(ly, hy, o.y, iv.y) SRR_QAX(lz, hz, o.z, iv.z)
 #undef SRR_QAX
@@ -1207,10 +1057,9 @@ SRR_D bool mesh_hit4_quad(const SceneView& S, const DMesh& m, const Ray& r, floa
   return found_me;
 }
 
-#ifndef SRR_XFAX
-#define SRR_XFAX 1  // rotations, record rects and light corners specialised on their axis (A/B: -DSRR_XFAX=0)
-#endif
-template <int IA>  // rotate_y (IA 0) / rotate_x (IA 1), the ray going in: the arithmetic of chain_in's generic branch
+// Rotations, record rects and light corners are specialised on their axis: the axis
+// is a compile-time constant in each branch (no run-time indexing)
+template <int IA>  // rotate_y (IA 0) / rotate_x (IA 1), the ray going in (hitable.h:109-116, 180-188)
 SRR_D void rot_in(const DXform& x, Ray& r) {
   const float s = x.a, c = x.b;
   V3 o = r.o, d = r.d;
@@ -1241,22 +1090,8 @@ SRR_D Ray chain_in(const SceneView& S, const DObj& ob, Ray r) {
   for (int k = 0; k < n; ++k) {
     DXform x = maybe_uni<U>(wload<TR>(S.xforms, ob.xf_begin + k));
     if (x.kind == XF_TRANSLATE) r.o = r.o - v3(x.a, x.b, x.c);
-#if SRR_XFAX  // the rotation's axis a compile-time constant in each branch (no run-time indexing)
     else if (x.kind == XF_ROTY) rot_in<0>(x, r);
     else if (x.kind == XF_ROTX) rot_in<1>(x, r);
-#else
-    else if (x.kind == XF_ROTY || x.kind == XF_ROTX) {
-      int ia = x.kind == XF_ROTY ? 0 : 1;
-      float s = x.a, c = x.b;
-      V3 o = r.o, d = r.d;
-      o.set(ia, c * r.o[ia] - s * r.o.z);
-      o.z = s * r.o[ia] + c * r.o.z;
-      d.set(ia, c * r.d[ia] - s * r.d.z);
-      d.z = s * r.d[ia] + c * r.d.z;
-      r.o = o;
-      r.d = d;
-    }
-#endif
   }
   return r;
 }
@@ -1266,22 +1101,8 @@ SRR_D void chain_out(const SceneView& S, const DObj& ob, V3& p, V3& n) {
   for (int k = (ob.xf_count & kXfCountMask) - 1; k >= 0; --k) {
     DXform x = S.xforms[ob.xf_begin + k];
     if (x.kind == XF_TRANSLATE) p = p + v3(x.a, x.b, x.c);
-#if SRR_XFAX
     else if (x.kind == XF_ROTY) rot_out<0>(x, p, n);
     else rot_out<1>(x, p, n);
-#else
-    else {
-      int ia = x.kind == XF_ROTY ? 0 : 1;
-      float s = x.a, c = x.b;
-      V3 pp = p, nn = n;
-      pp.set(ia, c * p[ia] + s * p.z);
-      pp.z = -s * p[ia] + c * p.z;
-      nn.set(ia, c * n[ia] + s * n.z);
-      nn.z = -s * n[ia] + c * n.z;
-      p = pp;
-      n = nn;
-    }
-#endif
   }
   if (ob.xf_count & kXfFlipBit) n = -n;  // flip_normals (aarect.h:149-171), exact in any order
 }
@@ -1301,17 +1122,12 @@ SRR_D bool prim_hit(const SceneView& S, const DObj& ob, const Ray& lr, float tmi
     case OBJ_MSPHERE:
       return sphere_hit(maybe_uni<U>(wload<TR>(S.spheres, ob.idx)), ob.kind == OBJ_MSPHERE, lr, tmin, tmax, t);
     case OBJ_RECT: {
-#if SRR_RECTAX
       const DRect q = maybe_uni<U>(wload<TR>(S.rects, ob.idx));
       switch (q.kax) {
         case 0: return rect_hit_t<0>(q, lr, tmin, tmax, t);
         case 1: return rect_hit_t<1>(q, lr, tmin, tmax, t);
         default: return rect_hit_t<2>(q, lr, tmin, tmax, t);
       }
-#else
-      float u, v;
-      return rect_hit(maybe_uni<U>(wload<TR>(S.rects, ob.idx)), lr, tmin, tmax, t, u, v);
-#endif
     }
     case OBJ_TRI: {
       const DStandaloneTri T = maybe_uni<U>(wload<TR>(S.stris, ob.idx));
@@ -1403,8 +1219,8 @@ SRR_D bool sgroup_hit(const SceneView& S, const DSGroup& g, const Ray& r, float 
     const float t1 = (hi.A + pad - r.o.A) * inv.A;        \
     const bool sw = inv.A < 0.0f;                         \
     const float n_ = sw ? t1 : t0, f_ = sw ? t0 : t1;     \
-    tn = SRR_SMAX(n_, tn);                                \
-    tf = SRR_SMIN(f_, tf);                                \
+    tn = fmaxf(n_, tn);                                   \
+    tf = fminf(f_, tf);                                   \
   }
     SRR_AX(x) SRR_AX(y) SRR_AX(z)
 #undef SRR_AX
@@ -1450,9 +1266,6 @@ SRR_D bool basic_hit(const SceneView& S, const DObj& ob, const Ray& lr, float tm
                      ObjHit& h, const TraceCtx& cx) {
   switch (ob.kind) {
     case OBJ_MESH: {
-#ifdef SRR_EXP_NOMESH  // timing experiment only (wrong image): meshes never hit
-      return false;
-#endif
       MeshHit mh;
       const DMesh m = maybe_uni<U>(wload<TR>(S.meshes, ob.idx));
       bool hit;
@@ -1488,8 +1301,8 @@ SRR_D bool list_hit(const SceneView& S, int b, int n, const Ray& r, float tmin, 
   bool any = false;
   float closest = tmax;
   for (int k = 0; k < n; ++k) {
-    const DObj ob = maybe_uni<SRR_UNIFORM != 0>(wload<TR>(S.objs, b + k));
-    const Ray lr = chain_in<TR, SRR_UNIFORM != 0>(S, ob, r);
+    const DObj ob = uni(wload<TR>(S.objs, b + k));
+    const Ray lr = chain_in<TR, true>(S, ob, r);
     float th = 0;
     bool hit;
     if (ob.kind == OBJ_MESH) {
@@ -1506,7 +1319,7 @@ SRR_D bool list_hit(const SceneView& S, int b, int n, const Ray& r, float tmin, 
     } else if (ob.kind == OBJ_MEDIUM) {
       hit = false;
     } else {
-      hit = prim_hit<TR, SRR_UNIFORM != 0>(S, ob, lr, tmin, closest, true, th);
+      hit = prim_hit<TR, true>(S, ob, lr, tmin, closest, true, th);
     }
     if (hit) {
       any = true;
@@ -1562,15 +1375,15 @@ SRR_D void world_objs(const SceneView& S, const Ray& r, Rng& rng, const TraceCtx
                       float& closest) {
   const float tmin = 0.001f;
   for (int k = k0; k < k1; ++k) {
-    const DObj ob = maybe_uni<SRR_UNIFORM != 0>(wload<TR>(S.objs, k));
-    Ray lr = chain_in<TR, SRR_UNIFORM != 0>(S, ob, r);
+    const DObj ob = uni(wload<TR>(S.objs, k));
+    Ray lr = chain_in<TR, true>(S, ob, r);
     ObjHit h;
     bool hit;
     if (MEDIA && ob.kind == OBJ_MEDIUM) {
-      hit = medium_hit<TR>(S, maybe_uni<SRR_UNIFORM != 0>(wload<TR>(S.media, ob.idx)), lr, tmin, closest, rng, h.t, cx);
+      hit = medium_hit<TR>(S, uni(wload<TR>(S.media, ob.idx)), lr, tmin, closest, rng, h.t, cx);
       h.prim = -1;
     } else {
-      hit = basic_hit<TR, SRR_UNIFORM != 0>(S, ob, lr, tmin, closest, false, h, cx);
+      hit = basic_hit<TR, true>(S, ob, lr, tmin, closest, false, h, cx);
     }
     if (hit) {
       closest = h.t;
@@ -1613,20 +1426,20 @@ SRR_D WorldHit world_hit(const SceneView& S, const Ray& r, Rng& rng, const Trace
     }
   }
   for (int k = 0; k < S.n_world; ++k) {
-    const DObj ob = maybe_uni<SRR_UNIFORM != 0>(wload<TR>(S.objs, k));
+    const DObj ob = uni(wload<TR>(S.objs, k));
     if constexpr (SUSP) {
       // (a per-lane skip, not a break: the object loop stays wave-uniform)
       if (skip && (cx.susp || k < k_res)) continue;
       cx.obj_k = k;
     }
-    Ray lr = chain_in<TR, SRR_UNIFORM != 0>(S, ob, r);
+    Ray lr = chain_in<TR, true>(S, ob, r);
     ObjHit h;
     bool hit;
     if (MEDIA && ob.kind == OBJ_MEDIUM) {
-      hit = medium_hit<TR>(S, maybe_uni<SRR_UNIFORM != 0>(wload<TR>(S.media, ob.idx)), lr, tmin, closest, rng, h.t, cx);
+      hit = medium_hit<TR>(S, uni(wload<TR>(S.media, ob.idx)), lr, tmin, closest, rng, h.t, cx);
       h.prim = -1;
     } else {
-      hit = basic_hit<TR, SRR_UNIFORM != 0>(S, ob, lr, tmin, closest, false, h, cx);
+      hit = basic_hit<TR, true>(S, ob, lr, tmin, closest, false, h, cx);
     }
     if (SUSP && skip && cx.susp) {
       *walk_save(cx, 2) = make_float4(__int_as_float(k), closest, __int_as_float(w.obj), __int_as_float(w.prim));
@@ -1651,7 +1464,6 @@ struct HitRec {
   int mat;
 };
 
-#if SRR_XFAX
 // prim_record's rect branch with the plane axis a compile-time constant: u, v by
 // rect_hit's arithmetic (aarect.h:96-147), the normal along the axis
 template <int KAX>
@@ -1665,7 +1477,6 @@ SRR_D void rect_rec(const DRect& q, const Ray& r, HitRec& h) {
   h.n = v3(0.f);
   h.n.set(KAX, 1.f);
 }
-#endif
 
 SRR_D void sphere_uv(V3 p, float& u, float& v) {  // hitable.h:10-15
   float phi = ratan2(p.z, p.x);
@@ -1690,18 +1501,11 @@ SRR_D void prim_record(const SceneView& S, const DObj& ob, const Ray& lr, float 
     }
     case OBJ_RECT: {
       const DRect& q = S.rects[ob.idx];
-#if SRR_XFAX
       switch (q.kax) {
         case 0: rect_rec<0>(q, lr, h); break;
         case 1: rect_rec<1>(q, lr, h); break;
         default: rect_rec<2>(q, lr, h); break;
       }
-#else
-      float tt;
-      rect_hit(q, lr, -FLT_MAX, FLT_MAX, tt, h.u, h.v);
-      h.n = v3(0.f);
-      h.n.set(q.kax, 1.f);
-#endif
       h.p = lr.at(t);
       h.mat = q.mat;
       break;
@@ -2132,24 +1936,16 @@ SRR_D V3 beckmann_sample_wh_pre(const Beck& d, const BeckPre& p, float u1, float
   return wh;
 }
 
-#ifndef SRR_SINCOS
-#define SRR_SINCOS 1  // random_cosine_direction's sine and cosine from one sincosf_ (A/B: -DSRR_SINCOS=0)
-#endif
 // pdf.h:10-18
 SRR_D V3 random_cosine_direction(Rng& rng) {
   float r1 = drand(rng);
   float r2 = drand(rng);
   float phi = 2 * kPi * r1;
   float z = rsqrt_exact(1 - r2);
-#if SRR_SINCOS && !defined(SRR_LIBM_DOUBLE)
   float sp, cp;
-  gm::sincosf_(phi, sp, cp);  // = sinf_(phi), cosf_(phi)
+  gm::sincosf_(phi, sp, cp);  // = sinf_(phi), cosf_(phi) (glibc_mathf.h), sharing one range reduction
   float x = cp * 2 * rsqrt_exact(r2);
   float y = sp * 2 * rsqrt_exact(r2);
-#else
-  float x = rcos(phi) * 2 * rsqrt_exact(r2);  // cosf / sinf (glibc_mathf.h)
-  float y = rsin(phi) * 2 * rsqrt_exact(r2);
-#endif
   return v3(x, y, z);
 }
 
@@ -2179,12 +1975,7 @@ SRR_D float light_pdf_one(const SceneView& S, const DLight& L, V3 o, V3 v) {
   if (L.kind == LIGHT_XZRECT) {  // aarect.h:45-55
     const DRect& q = S.rects[L.idx];
     float t;
-#if SRR_RECTAX
     if (rect_hit_t<1>(q, r, 0.001f, FLT_MAX, t)) {  // an xz_rect light (kax 1)
-#else
-    float u, vv;
-    if (rect_hit(q, r, 0.001f, FLT_MAX, t, u, vv)) {
-#endif
       float area = (q.hi0 - q.lo0) * (q.hi1 - q.lo1);
       float distance_square = t * t * squared_length(v);
       float cosine = fabsf(v.y / length(v));  // dot(v, (0,1,0)) / |v|
@@ -2505,20 +2296,12 @@ SRR_D uint64_t skip_attempt(const SceneView& S, uint64_t s) {
   return s;
 }
 
-
-#ifndef SRR_COOP_HELPERS
-#define SRR_COOP_HELPERS 8
-#endif
-#ifndef SRR_COOP_ID0
-#define SRR_COOP_ID0 0
-#endif
-constexpr int kMaxHelpers = SRR_COOP_HELPERS;  // attempts of one path per round
+constexpr int kMaxHelpers = 8;  // attempts of one path per round
 
 // Runs to completion the loops of every lane with `pend` (converged wave, all 64
 // lanes active).  In: the lane's setup, its LCG state before attempt `tries`.
 // Out: ndir, pdf and the LCG state after the first attempt with pdf != 0 (or the
-// guard's last attempt).  The first round is each pending lane's own attempt
-// (no exchange); later rounds spread the remaining paths over all 64 lanes.
+// guard's last attempt).  Every round spreads the pending paths over all 64 lanes.
 // deep_tries: past this many failed attempts a path takes every free lane
 // (PathWork::deep_tries, 32; SRR_DEEP_TRIES=0 forces it from the first round).
 SRR_D int coop_mixture(const SceneView& S, const DiffSetup& me, bool& pend, int& tries, uint64_t& lcg, V3& ndir,
@@ -2527,7 +2310,6 @@ SRR_D int coop_mixture(const SceneView& S, const DiffSetup& me, bool& pend, int&
   const int lane = lane_id();
   const uint64_t lt = (1ull << lane) - 1;
   uint64_t F = __ballot(pend);
-  bool first = SRR_COOP_ID0 != 0;
   while (F) {
     const int nF = __popcll(F);
     // paths whose loop has failed kDeepTries times (e.g. a hit point in the light's
@@ -2535,32 +2317,23 @@ SRR_D int coop_mixture(const SceneView& S, const DiffSetup& me, bool& pend, int&
     // 100,000 attempts; once every pending path is that deep, all 64 lanes help
     const int cap = __ballot(pend && tries < deep_tries) == 0 ? 64 : kMaxHelpers;
     const int rank = pend ? __popcll(F & lt) : nF + __popcll(~F & lt);
+    // lane r < nF learns the lane of the r-th pending path (a permutation of
+    // all 64 lanes: pending lanes in order, then the others)
+    const int owner_of = __builtin_amdgcn_ds_permute(rank << 2, lane);
+    const int q = lane % nF;
+    const int k = lane / nF;
+    const int src = __builtin_amdgcn_ds_bpermute(q << 2, owner_of);
     DiffSetup d;
-    int t0, k;
-    uint64_t s;
-    if (first) {
-      d = me;
-      t0 = tries;
-      s = lcg;
-      k = pend ? 0 : 64;
-    } else {
-      // lane r < nF learns the lane of the r-th pending path (a permutation of
-      // all 64 lanes: pending lanes in order, then the others)
-      const int owner_of = __builtin_amdgcn_ds_permute(rank << 2, lane);
-      const int q = lane % nF;
-      k = lane / nF;
-      const int src = __builtin_amdgcn_ds_bpermute(q << 2, owner_of);
-      d.p = v3(__shfl(me.p.x, src), __shfl(me.p.y, src), __shfl(me.p.z, src));
-      d.w = v3(__shfl(me.w.x, src), __shfl(me.w.y, src), __shfl(me.w.z, src));
-      d.v = v3(__shfl(me.v.x, src), __shfl(me.v.y, src), __shfl(me.v.z, src));
-      d.nl = v3(__shfl(me.nl.x, src), __shfl(me.nl.y, src), __shfl(me.nl.z, src));
-      d.c0 = __shfl(me.c0, src);
-      d.c1 = __shfl(me.c1, src);
-      d.flags = __shfl(me.flags, src);
-      t0 = __shfl(tries, src);
-      s = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(lcg >> 32), src) << 32) |
-          (uint32_t)__shfl((int)(uint32_t)lcg, src);
-    }
+    d.p = v3(__shfl(me.p.x, src), __shfl(me.p.y, src), __shfl(me.p.z, src));
+    d.w = v3(__shfl(me.w.x, src), __shfl(me.w.y, src), __shfl(me.w.z, src));
+    d.v = v3(__shfl(me.v.x, src), __shfl(me.v.y, src), __shfl(me.v.z, src));
+    d.nl = v3(__shfl(me.nl.x, src), __shfl(me.nl.y, src), __shfl(me.nl.z, src));
+    d.c0 = __shfl(me.c0, src);
+    d.c1 = __shfl(me.c1, src);
+    d.flags = __shfl(me.flags, src);
+    const int t0 = __shfl(tries, src);
+    uint64_t s = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(lcg >> 32), src) << 32) |
+                 (uint32_t)__shfl((int)(uint32_t)lcg, src);
     const bool active = k < cap && t0 + k < kMixtureGuard;
     V3 nd = v3(0.f);
     float pv = 0;
@@ -2572,40 +2345,26 @@ SRR_D int coop_mixture(const SceneView& S, const DiffSetup& me, bool& pend, int&
       s = rr.lcg;
     }
     const uint64_t ok = __ballot(active && (pv != 0 || t0 + k + 1 >= kMixtureGuard));
-    if (first) {  // every pending lane ran its own next attempt
-      if (pend) {
-        lcg = s;
-        if ((ok >> lane) & 1) {
-          ndir = nd;
-          pdf = pv;
-          pend = false;
-        } else {
-          tries += 1;
-        }
-      }
-      first = false;
-    } else {
-      // owner: its first successful helper (k ascending), else its last one
-      int win = lane, m = 0;
-      if (pend) {
-        m = min(cap, (63 - rank) / nF + 1);
-        m = min(m, kMixtureGuard - tries);
-        int j = 0;
-        while (j < m - 1 && !((ok >> (rank + j * nF)) & 1)) ++j;
-        win = rank + j * nF;
-      }
-      const float wx = __shfl(nd.x, win), wy = __shfl(nd.y, win), wz = __shfl(nd.z, win), wp = __shfl(pv, win);
-      const uint64_t ws = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(s >> 32), win) << 32) |
-                          (uint32_t)__shfl((int)(uint32_t)s, win);
-      if (pend) {
-        lcg = ws;
-        if ((ok >> win) & 1) {
-          ndir = v3(wx, wy, wz);
-          pdf = wp;
-          pend = false;
-        } else {
-          tries += m;
-        }
+    // owner: its first successful helper (k ascending), else its last one
+    int win = lane, m = 0;
+    if (pend) {
+      m = min(cap, (63 - rank) / nF + 1);
+      m = min(m, kMixtureGuard - tries);
+      int j = 0;
+      while (j < m - 1 && !((ok >> (rank + j * nF)) & 1)) ++j;
+      win = rank + j * nF;
+    }
+    const float wx = __shfl(nd.x, win), wy = __shfl(nd.y, win), wz = __shfl(nd.z, win), wp = __shfl(pv, win);
+    const uint64_t ws = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(s >> 32), win) << 32) |
+                        (uint32_t)__shfl((int)(uint32_t)s, win);
+    if (pend) {
+      lcg = ws;
+      if ((ok >> win) & 1) {
+        ndir = v3(wx, wy, wz);
+        pdf = wp;
+        pend = false;
+      } else {
+        tries += m;
       }
     }
     F = __ballot(pend);
@@ -2645,9 +2404,6 @@ SRR_D void camera_get_ray(const DCamera& C, float u, float v, Rng& rng, V3& o, V
 // tangent plane -- and evaluates exactly only light-branch attempts, near-tangent
 // BSDF samples, and the guard's last attempt.  The attempts it evaluates and
 // their results are the sequential loop's, bit for bit.
-#ifndef SRR_MIXTURE_SKIP
-#define SRR_MIXTURE_SKIP 2
-#endif
 
 SRR_D bool light_point_far(V3 c, V3 p, V3 w, float sgn, float m) { return sgn * dot(c - p, w) <= -m; }
 
@@ -2667,22 +2423,12 @@ SRR_D bool bsdf_dead(const SceneView& S, const Bsdf& f, V3 p) {
     const DLight L = S.lights[k];
     if (L.kind == LIGHT_XZRECT) {
       const DRect q = S.rects[L.idx];
-#if SRR_XFAX  // an xz_rect light: kax 1, a0 0, a1 2
+      // (an xz_rect light: kax 1, a0 0, a1 2)
       if (!(q.k != p.y)) return false;  // the hit point in the light's plane
-#else
-      if (!(q.k != p[q.kax])) return false;  // the hit point in the light's plane
-#endif
       const float m = 1e-3f * (ps + fmaxf(fmaxf(fmaxf(fabsf(q.lo0), fabsf(q.hi0)), fmaxf(fabsf(q.lo1), fabsf(q.hi1))),
                                           fabsf(q.k)));
       for (int c = 0; c < 4; ++c) {
-#if SRR_XFAX
         const V3 v = v3((c & 1) ? q.hi0 : q.lo0, q.k, (c & 2) ? q.hi1 : q.lo1);
-#else
-        V3 v = v3(0.f);
-        v.set(q.kax, q.k);
-        v.set(q.a0, (c & 1) ? q.hi0 : q.lo0);
-        v.set(q.a1, (c & 2) ? q.hi1 : q.lo1);
-#endif
         if (!light_point_far(v, p, w, sgn, m)) return false;
       }
     } else if (L.kind == LIGHT_SPHERE) {
@@ -2713,7 +2459,7 @@ SRR_D bool bsdf_dead(const SceneView& S, const Bsdf& f, V3 p) {
 // `tries`.  Out: ndir, pdf and the LCG state after the first attempt with
 // pdf != 0 (or the guard's last attempt).  Returns the wave's exact rounds.
 SRR_D int skip_mixture(const SceneView& S, const DiffSetup& me, bool dead, bool& pend, int& tries, uint64_t& lcg,
-                       V3& ndir, float& pdf, int max_rounds = 1 << 30) {
+                       V3& ndir, float& pdf, int max_rounds) {
   int rounds = 0;
   while (rounds < max_rounds && __ballot(pend)) {
     if (pend) {
@@ -2788,7 +2534,6 @@ SRR_D void camera_ray(const SceneView& S, int pix, int s_global, double sx, doub
   float v = float(sy + j) / float(ny);
   camera_get_ray(*S.cam, u, v, rng, o, dir, time);
 }
-
 
 __global__ void __launch_bounds__(256) k_raygen(SceneView S, PathState P, BatchInfo B) {
   int q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3206,24 +2951,15 @@ SRR_D bool shade_one(const SceneView& S, const PathState& P, int p, int max_dept
 // recursion returns, writes the sample and fetches the next (pixel, sample) from
 // a global cursor (one wave-aggregated atomic per refill).  No path state goes
 // through memory between bounces except the write-only bounce records.
-// bounce records: plain stores keep the first bounces' records (a few MB per
-// XCD) in L2 for the fold; nontemporal ones stream them to HBM
-#ifndef SRR_REC_NT
-#define SRR_REC_NT 0
-#endif
-#ifndef SRR_FOLD4
-#define SRR_FOLD4 1  // the fold's record loads four at a time (A/B: -DSRR_FOLD4=0)
-#endif
-SRR_D void rec_store(float4* p, float4 v) {
-  if (SRR_REC_NT) nts(p, v);
-  else *p = v;
-}
-SRR_D float4 rec_load(const float4* p) { return SRR_REC_NT ? ntl(p) : *p; }
+// The bounce records are written and read with plain stores and loads, which keep
+// the first bounces' records (a few MB per XCD) in L2 for the fold (nontemporal
+// ones would stream them to HBM).
+SRR_D float4 rec_load(const float4* p) { return *p; }  // (by value: the fold issues four of these together)
 
 constexpr int kPathsBlock = 256;
 constexpr unsigned long long kPoolChunk = 64;  // path indices a wave takes per cursor atomic
 
-// Camera-ray ring (SRR_RAYRING, default on).  A lane whose path ended used to
+// Camera-ray ring.  A lane whose path ended used to
 // generate its next camera ray itself (pixel and sample from the path index,
 // per-path seeds, Sobol point, lens disk, normalisation: a few hundred VALU
 // instructions) while the wave's other lanes, still inside their paths, idled:
@@ -3233,10 +2969,8 @@ constexpr unsigned long long kPoolChunk = 64;  // path indices a wave takes per 
 // lane k the ray of path chunk + k, every lane busy -- into its 64 LDS entries,
 // and refilling lanes just read theirs: the chunk's rays cost one full-wave
 // generation per ~2 iterations instead of a half-empty one per iteration.  Every
-// path's ray is the same function of its index, so paths are unchanged.
-#ifndef SRR_RAYRING
-#define SRR_RAYRING 1
-#endif
+// path's ray is the same function of its index, so paths are unchanged.  (The
+// quad-cooperative variant runs without the ring.)
 // diagnostics-only k_paths variants (phase timing, compressed nodes): `make diag`
 #ifndef SRR_DIAG_VARIANTS
 #define SRR_DIAG_VARIANTS 0
@@ -3249,7 +2983,7 @@ constexpr int kRingWords = 11;  // o.xyz, d.xyz, time, lcg (2 words), pcg (2 wor
 // 8 KB world + 8 B x kStack x 1,024 lanes of stacks + the camera-ray rings (44 B
 // per lane) + the node cache <= 160 KB (344 nodes at kStack 8)
 constexpr int kPathsLdsNodesBig =
-    (160 * 1024 - 8192 - 8 * kPathsLdsStack * 1024 - 1024 - (SRR_RAYRING ? 4 * kRingWords * 1024 : 0)) / 128;
+    (160 * 1024 - 8192 - 8 * kPathsLdsStack * 1024 - 1024 - 4 * kRingWords * 1024) / 128;
 // 256-lane blocks (4 per CU, <= 40 KB each) of the LDS-world variant: the ring
 // displaces the node cache.  These blocks serve mesh-free scenes by default
 // (paths_block_lanes); mesh scenes reach them only with SRR_BIGBLOCK=0 (an A/B
@@ -3257,7 +2991,7 @@ constexpr int kPathsLdsNodesBig =
 // cache: the global-world one (world tables beyond kWorldLdsBytes) has the 8 KB
 // of the LDS world to spare (16 KB stacks + 11 KB ring + 12 KB nodes), and the
 // quad-cooperative one (SRR_QUAD) runs without the ring.
-constexpr int kPathsLdsNodesSmall = SRR_RAYRING ? 8 : kPathsLdsNodes;
+constexpr int kPathsLdsNodesSmall = 8;
 
 // The camera ray of path index idx of the window (pixel-major: idx = lp * spp_w + s)
 // with its RNG streams, as k_paths' refill needs it.
@@ -3369,7 +3103,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
   const auto work = []() { return PathWork(paths_args()->W); };
   __shared__ int s_node[kStack * BS];
   __shared__ float s_t[kStack * BS];
-  constexpr bool RING = SRR_RAYRING && !QUAD;
+  constexpr bool RING = !QUAD;
   constexpr int kNodesLds = BS == 1024 ? kPathsLdsNodesBig : ((WL && RING) ? kPathsLdsNodesSmall : kPathsLdsNodes);
   __shared__ float4 s_n4[kNodesLds * 8];
   // RING: the wave's camera-ray ring, SoA [kRingWords][BS]; the wave's 64 entries
@@ -3643,7 +3377,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
           f.B = M.p[1];
           bsdf_prepare<false>(f, r.d);
           ds = diff_setup(f, h.p);
-          if (SRR_MIXTURE_SKIP) d_dead = bsdf_dead(S, f, h.p);
+          d_dead = bsdf_dead(S, f, h.p);
           (void)drand(rng);  // mixture_pdf ctor (pdf.h:175)
           d_n = h.n;
           diff = pend = true;
@@ -3665,7 +3399,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
             if (TIMED) fam_dt[1] = __builtin_amdgcn_s_memtime() - tb;
           }
           if (depth >= W.max_depth || slot >= W.lanes) atomicOr(W.err, 2);
-          else rec_store(rec_at(W, depth), rec);
+          else *rec_at(W, depth) = rec;
           if (!sp && S.n_lights > 0 && rec.w == 0) n_events += kCapped;  // the loop reached kMixtureGuard
           r = Ray{h.p, nd, nt};
           ++depth;
@@ -3692,15 +3426,10 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
     if (__ballot(pend)) {
       const SceneView S = view();
       const uint64_t tc = TIMED ? __builtin_amdgcn_s_memtime() : 0;
-      // SRR_MIXTURE_SKIP 1: per-lane loops passing over dead draws; 2: one such
-      // round, then the wave-cooperative loop for what is left; 0: cooperative only
-      int rounds = 0;
-      if (SRR_MIXTURE_SKIP == 1) {
-        rounds = skip_mixture(S, ds, d_dead, pend, d_tries, rng.lcg, d_dir, d_pdf);
-      } else {
-        if (SRR_MIXTURE_SKIP == 2) rounds = skip_mixture(S, ds, d_dead, pend, d_tries, rng.lcg, d_dir, d_pdf, 1);
-        if (__ballot(pend)) rounds += coop_mixture(S, ds, pend, d_tries, rng.lcg, d_dir, d_pdf, paths_args()->W.deep_tries);
-      }
+      // one round of per-lane loops passing over dead draws, then the
+      // wave-cooperative loop for what is left
+      int rounds = skip_mixture(S, ds, d_dead, pend, d_tries, rng.lcg, d_dir, d_pdf, 1);
+      if (__ballot(pend)) rounds += coop_mixture(S, ds, pend, d_tries, rng.lcg, d_dir, d_pdf, paths_args()->W.deep_tries);
       if (TIMED) {
         tp[6] += __builtin_amdgcn_s_memtime() - tc;
         tp[7] += rounds;
@@ -3714,7 +3443,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
       if (c < 0) c = 0;
       const V3 as = d_atten * (c / kPi);
       if (depth >= W.max_depth || slot >= W.lanes) atomicOr(W.err, 2);
-      else rec_store(rec_at(W, depth), make_float4(as.x, as.y, as.z, d_pdf));
+      else *rec_at(W, depth) = make_float4(as.x, as.y, as.z, d_pdf);
       r = Ray{ds.p, d_dir, r.tm};
       ++depth;
     }
@@ -3732,7 +3461,6 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
       }
       if (done) {
         // fold the bounces back to front (Raytracing_n.cpp:69, :94), as finish_path
-#if SRR_FOLD4
         // the last four records' loads issued together (one L2 round trip, not one
         // per bounce), then folded in the same order
         int k = depth - 1;
@@ -3748,14 +3476,6 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
             else C = v3(0.f) + (av * C) / a[j].w;
           }
         }
-#else
-        for (int k = depth - 1; k >= 0; --k) {
-          const float4 a = rec_load(rec_at(W, k));
-          const V3 av = v3(a.x, a.y, a.z);
-          if (__float_as_uint(a.w) == kSpecMark) C = av * C;  // specular: attenuation * color
-          else C = v3(0.f) + (av * C) / a.w;
-        }
-#endif
         if (W.raw) {  // kept paths: [pixel][sample of the frame]
           const size_t kq = (size_t)(g / W.spp_w) * W.keep_spp + W.keep_s0 + (size_t)(g % W.spp_w);
           W.raw[3 * kq] = C.x;
@@ -4607,22 +4327,46 @@ static int paths_min_blocks() {
   return v;
 }
 
-// Lanes per k_paths block for this scene: 1,024 (SRR_BIGBLOCK, the default) when the
-// launch would take the per-lane, LDS-world path, else 256.  render_paths rounds
-// the window's lanes to it.
-int paths_block_lanes(const SceneView& S) {
+// The run-time facts that pick a k_paths variant, gathered in one place:
+// paths_block_lanes (by which render_paths sizes the window) and launch_paths
+// must agree on them.
+struct PathsVariant {
+  bool media, allfam;  // SceneView::has_media; every material family (else the diffuse one alone)
+  bool wl;             // world tables staged in LDS: they fit, and SRR_WORLD_GLOBAL is unset
+  bool quad;           // SceneView::quad_trace
+  bool sp;             // suspendable mesh walks (PathWork::walk_q > 0)
+  bool timing;         // SRR_PATHS_TIMING is set (phase timing: the diagnostics build has it)
+  bool cq;             // compressed nodes, per-lane walks (SRR_CBVH; diagnostics build)
+  int bs;              // lanes per block
+};
+static PathsVariant paths_variant(const SceneView& S, int all_families, int walk_q) {
   static const bool big = [] {
     const char* e = getenv("SRR_BIGBLOCK");
     return !e || atoi(e) != 0;
   }();
-  static const bool timed = SRR_DIAG_VARIANTS && getenv("SRR_PATHS_TIMING") != nullptr;
-  static const bool force_global = getenv("SRR_WORLD_GLOBAL") != nullptr;
-  const bool wl = !force_global && S.world_words * 16 <= dev::kWorldLdsBytes;
-  // (a scene without meshes has no BVH4 nodes to cache: 256-lane blocks, which
-  // free their CU slots at a finer grain when frames overlap -- C1 +1.6 %)
-  return (big && wl && !timed && !S.quad_trace && S.node4_total > 0 &&
-          paths_min_blocks() == kPathsOccDefault) ? 1024 : dev::kPathsBlock;
+  static const bool timing = getenv("SRR_PATHS_TIMING") != nullptr;
+  static const bool force_global = getenv("SRR_WORLD_GLOBAL") != nullptr;  // A/B diagnostics
+  PathsVariant v;
+  v.media = S.has_media != 0;
+  v.allfam = all_families != 0;
+  v.wl = !force_global && S.world_words * 16 <= dev::kWorldLdsBytes;  // else too large for LDS: global reads
+  v.quad = S.quad_trace != 0;
+  v.sp = walk_q > 0;
+  v.timing = timing;
+  const bool timed = SRR_DIAG_VARIANTS && timing;
+  v.cq = SRR_DIAG_VARIANTS && S.use_q && !S.quad_trace && !timed;
+  // 1,024 lanes (SRR_BIGBLOCK, the default) when the launch takes the per-lane,
+  // LDS-world path, else 256.  (A scene without meshes has no BVH4 nodes to cache:
+  // 256-lane blocks, which free their CU slots at a finer grain when frames
+  // overlap -- C1 +1.6 %)
+  v.bs = (big && v.wl && !timed && !S.quad_trace && S.node4_total > 0 && paths_min_blocks() == kPathsOccDefault)
+             ? 1024
+             : dev::kPathsBlock;
+  return v;
 }
+
+// Lanes per k_paths block for this scene.  render_paths rounds the window's lanes to it.
+int paths_block_lanes(const SceneView& S) { return paths_variant(S, 0, 0).bs; }
 
 int paths_lanes_per_device(const SceneView& S, int device) {
   (void)S;
@@ -4635,75 +4379,79 @@ int paths_lanes_per_device(const SceneView& S, int device) {
   return cus * per_cu * dev::kPathsBlock;
 }
 
+// one k_paths instantiation over the window's lanes, in blocks of BS
+template <bool M, bool A, int MINB, bool TIMED = false, bool WL = true, bool QUAD = false, bool CQ = false,
+          int BS = dev::kPathsBlock, bool SP = false>
+static void launch_k_paths(const dev::PathsArgs& args, hipStream_t st) {
+  hipLaunchKernelGGL((dev::k_paths<M, A, MINB, TIMED, WL, QUAD, CQ, BS, SP>), dim3(args.W.lanes / BS), dim3(BS), 0, st,
+                     args);
+}
+
+// The variant for the facts v among those with MEDIA = M and ALLFAM = A: the world
+// tables read from global memory (one occupancy; no 1,024-lane, suspendable or
+// diagnostics form) ...
+template <bool M, bool A>
+static void launch_paths_global(const PathsVariant& v, const dev::PathsArgs& args, hipStream_t st) {
+  if (v.quad) return launch_k_paths<M, A, 4, false, false, true>(args, st);
+  launch_k_paths<M, A, 4, false, false>(args, st);
+}
+
+// ... or staged in LDS, with B resident blocks per CU where the occupancy study
+// builds have more than the default 4
+template <bool M, bool A, int B>
+static void launch_paths_lds(const PathsVariant& v, const dev::PathsArgs& args, hipStream_t st) {
+#if SRR_DIAG_VARIANTS
+  // diagnostics build (make diag): SRR_PATHS_TIMING=1 phase timing, SRR_CBVH=1 compressed nodes
+  if (v.timing && v.sp) return launch_k_paths<M, A, 4, true, true, false, false, dev::kPathsBlock, true>(args, st);
+  if (v.timing) return launch_k_paths<M, A, 4, true>(args, st);
+#endif
+  if constexpr (B == 4) {  // only the default occupancy has the 1,024-lane, quad and compressed-node forms
+#if SRR_DIAG_VARIANTS
+    if (v.cq && v.bs == 1024) return launch_k_paths<M, A, 4, false, true, false, true, 1024>(args, st);
+    if (v.cq) return launch_k_paths<M, A, 4, false, true, false, true>(args, st);
+#endif
+    // suspendable mesh walks: the variant with them when the frame asks for them;
+    // only the 1,024-lane (mesh scene) and diagnostics variants have one
+    if (v.bs == 1024 && !v.quad && v.sp) return launch_k_paths<M, A, 4, false, true, false, false, 1024, true>(args, st);
+    if (v.bs == 1024 && !v.quad) return launch_k_paths<M, A, 4, false, true, false, false, 1024>(args, st);
+    if (v.quad) return launch_k_paths<M, A, 4, false, true, true>(args, st);
+  }
+  launch_k_paths<M, A, B>(args, st);
+}
+
+// (the occupancy B is a template parameter of the kernel: SRR_PATHS_OCC picks it)
+template <bool M, bool A>
+static void launch_paths_lds_occ(const PathsVariant& v, const dev::PathsArgs& args, hipStream_t st) {
+#ifdef SRR_OCC_VARIANTS  // occupancy A/B builds (SRR_PATHS_OCC): 2, 3, 5 and 6 blocks per CU
+  switch (paths_min_blocks()) {
+    case 2: return launch_paths_lds<M, A, 2>(v, args, st);
+    case 3: return launch_paths_lds<M, A, 3>(v, args, st);
+    case 5: return launch_paths_lds<M, A, 5>(v, args, st);
+    case 6: return launch_paths_lds<M, A, 6>(v, args, st);
+  }
+#endif
+  launch_paths_lds<M, A, 4>(v, args, st);
+}
+
 int launch_paths(const SceneView& S, const PathWork& W, int all_families, hipStream_t st) {
   // the kernels index kStack LDS entries per lane: a host built with a larger
   // SRR_KSTACK is refused here (round 4 ran such a mix once: an illegal address)
   if (W.stack_cap < 1 || W.stack_cap > dev::kStack) return -1;
   const dev::PathsArgs args{S, W};
-  const int blocks = W.lanes / dev::kPathsBlock;
-  static const bool force_global = getenv("SRR_WORLD_GLOBAL") != nullptr;  // A/B diagnostics
-  if (force_global || S.world_words * 16 > dev::kWorldLdsBytes) {  // world tables too large for LDS: global reads
-#define SRR_LAUNCH_PATHS_G(M, A)                                                                                      \
-  if (S.quad_trace) hipLaunchKernelGGL((dev::k_paths<M, A, 4, false, false, true>), dim3(blocks), dim3(dev::kPathsBlock), 0, st, args); \
-  else hipLaunchKernelGGL((dev::k_paths<M, A, 4, false, false>), dim3(blocks), dim3(dev::kPathsBlock), 0, st, args)
-    if (S.has_media) {
-      if (all_families) SRR_LAUNCH_PATHS_G(true, true);
-      else SRR_LAUNCH_PATHS_G(true, false);
-    } else {
-      if (all_families) SRR_LAUNCH_PATHS_G(false, true);
-      else SRR_LAUNCH_PATHS_G(false, false);
-    }
-#undef SRR_LAUNCH_PATHS_G
-    return 0;
-  }
-  const int bs = paths_block_lanes(S);
-  const int blocks_b = W.lanes / bs;
-  // suspendable mesh walks: the variant with them when the frame asks for them (walk_q > 0);
-  // only the 1,024-lane (mesh scene) and diagnostics variants have one
-  const bool sp = W.walk_q > 0;
-#if SRR_DIAG_VARIANTS
-  // diagnostics build (make diag): SRR_PATHS_TIMING=1 phase timing, SRR_CBVH=1 compressed nodes
-  static const bool timed = getenv("SRR_PATHS_TIMING") != nullptr;
-  const bool cq = S.use_q && !S.quad_trace && !timed;  // compressed nodes, per-lane walks
-#define SRR_LAUNCH_PATHS_DIAG(M, A, B)                                                                                         \
-  if (timed && sp) hipLaunchKernelGGL((dev::k_paths<M, A, 4, true, true, false, false, dev::kPathsBlock, true>), dim3(blocks), dim3(dev::kPathsBlock), 0, st, args); \
-  else if (timed) hipLaunchKernelGGL((dev::k_paths<M, A, 4, true>), dim3(blocks), dim3(dev::kPathsBlock), 0, st, args);      \
-  else if (bs == 1024 && B == 4 && cq) hipLaunchKernelGGL((dev::k_paths<M, A, 4, false, true, false, true, 1024>), dim3(blocks_b), dim3(1024), 0, st, args); \
-  else if (cq && B == 4) hipLaunchKernelGGL((dev::k_paths<M, A, 4, false, true, false, true>), dim3(blocks), dim3(dev::kPathsBlock), 0, st, args); \
-  else
-#else
-  if (S.use_q || getenv("SRR_PATHS_TIMING"))
+  const PathsVariant v = paths_variant(S, all_families, W.walk_q);
+  if (!SRR_DIAG_VARIANTS && v.wl && (S.use_q || v.timing))
     fprintf(stderr, "srr: SRR_CBVH / SRR_PATHS_TIMING need the diagnostics build (make diag); ignored\n");
-#define SRR_LAUNCH_PATHS_DIAG(M, A, B)
-#endif
-#define SRR_LAUNCH_PATHS(M, A, B)                                                                      \
-  SRR_LAUNCH_PATHS_DIAG(M, A, B)                                                                       \
-  if (bs == 1024 && B == 4 && !S.quad_trace && sp) hipLaunchKernelGGL((dev::k_paths<M, A, 4, false, true, false, false, 1024, true>), dim3(blocks_b), dim3(1024), 0, st, args); \
-  else if (bs == 1024 && B == 4 && !S.quad_trace) hipLaunchKernelGGL((dev::k_paths<M, A, 4, false, true, false, false, 1024>), dim3(blocks_b), dim3(1024), 0, st, args); \
-  else if (S.quad_trace && B == 4) hipLaunchKernelGGL((dev::k_paths<M, A, 4, false, true, true>), dim3(blocks), dim3(dev::kPathsBlock), 0, st, args); \
-  else hipLaunchKernelGGL((dev::k_paths<M, A, B>), dim3(blocks), dim3(dev::kPathsBlock), 0, st, args)
-#ifdef SRR_OCC_VARIANTS  // occupancy A/B builds (SRR_PATHS_OCC): 2, 3, 5 and 6 blocks per CU
-#define SRR_LAUNCH_PATHS_B(M, A)                          \
-  switch (paths_min_blocks()) {                           \
-    case 2: SRR_LAUNCH_PATHS(M, A, 2); break;             \
-    case 3: SRR_LAUNCH_PATHS(M, A, 3); break;             \
-    case 5: SRR_LAUNCH_PATHS(M, A, 5); break;             \
-    case 6: SRR_LAUNCH_PATHS(M, A, 6); break;             \
-    default: SRR_LAUNCH_PATHS(M, A, 4); break;            \
-  }
-#else
-#define SRR_LAUNCH_PATHS_B(M, A) SRR_LAUNCH_PATHS(M, A, 4);
-#endif
-  if (S.has_media) {
-    if (all_families) { SRR_LAUNCH_PATHS_B(true, true) }
-    else { SRR_LAUNCH_PATHS_B(true, false) }
+  if (!v.wl) {
+    if (v.media && v.allfam) launch_paths_global<true, true>(v, args, st);
+    else if (v.media) launch_paths_global<true, false>(v, args, st);
+    else if (v.allfam) launch_paths_global<false, true>(v, args, st);
+    else launch_paths_global<false, false>(v, args, st);
   } else {
-    if (all_families) { SRR_LAUNCH_PATHS_B(false, true) }
-    else { SRR_LAUNCH_PATHS_B(false, false) }
+    if (v.media && v.allfam) launch_paths_lds_occ<true, true>(v, args, st);
+    else if (v.media) launch_paths_lds_occ<true, false>(v, args, st);
+    else if (v.allfam) launch_paths_lds_occ<false, true>(v, args, st);
+    else launch_paths_lds_occ<false, false>(v, args, st);
   }
-#undef SRR_LAUNCH_PATHS_DIAG
-#undef SRR_LAUNCH_PATHS_B
-#undef SRR_LAUNCH_PATHS
   return 0;
 }
 
