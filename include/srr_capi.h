@@ -437,7 +437,11 @@ void srr_image_free(unsigned char* pixels);
  * function on KAT records laid out as oracle/ref/kat.inc writes them (inputs
  * first, outputs overwritten in place): "erf", "beckmann11", "beckmann_dist",
  * "beckmann_pdf", "cosine_pdf", "orennayar_pdf", "dielectric", "metal",
- * "triangle", "aabb"; and "sqrt" (records x, sqrtf(x)).  Needs a GPU. */
+ * "triangle", "aabb", "camera", "lights", "light_list"; "sqrt" (records x,
+ * sqrtf(x)); and the scene KATs, whose objects are built by the host scene calls
+ * and flattened like a scene's: "sphere", "moving_sphere", "rect", "box", "xform",
+ * "medium", "isotropic", "texture_checker", "texture_noise", "texture_image"
+ * (layouts: tests/golden/README.md).  Needs a GPU. */
 int srr_device_kat(const char* name, int n, int width, float* records);
 
 /* Test infrastructure: one math routine of the device build over n elements

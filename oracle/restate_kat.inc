@@ -16,6 +16,35 @@ static void wr_pcg(float*& o, uint64_t s) {
   for (int k = 0; k < 4; ++k) *o++ = (float)((s >> (16 * k)) & 0xFFFF);
 }
 
+// hit t p(3) n(3) [u v]; a miss writes zeros (kat.inc push_rec)
+static void wr_rec(float* o, bool hit, const Hit& h, bool uv) {
+  *o++ = hit ? 1.f : 0.f;
+  *o++ = hit ? h.t : 0;
+  wr3(o, hit ? h.p : V(0.f));
+  wr3(o, hit ? h.normal : V(0.f));
+  if (uv) {
+    *o++ = hit ? h.u : 0;
+    *o++ = hit ? h.v : 0;
+  }
+}
+// box.h:18-33: six rects in a hitable_list, every second one flipped
+static const Hitable* kat_box(Store& St, V p0, V p1) {
+  auto mk = [&](int kax, int a0, int a1, float lo0, float hi0, float lo1, float hi1, float kk, bool flip) {
+    Rect* q = St.add(new Rect());
+    q->kax = kax; q->a0 = a0; q->a1 = a1;
+    q->lo0 = lo0; q->hi0 = hi0; q->lo1 = lo1; q->hi1 = hi1; q->k = kk; q->mat = nullptr;
+    if (!flip) return (const Hitable*)q;
+    Flip* f = St.add(new Flip());
+    f->p = q;
+    return (const Hitable*)f;
+  };
+  List* l = St.add(new List());
+  l->l = {mk(2, 0, 1, p0.x(), p1.x(), p0.y(), p1.y(), p1.z(), false), mk(2, 0, 1, p0.x(), p1.x(), p0.y(), p1.y(), p0.z(), true),
+          mk(1, 0, 2, p0.x(), p1.x(), p0.z(), p1.z(), p1.y(), false), mk(1, 0, 2, p0.x(), p1.x(), p0.z(), p1.z(), p0.y(), true),
+          mk(0, 1, 2, p0.y(), p1.y(), p0.z(), p1.z(), p1.x(), false), mk(0, 1, 2, p0.y(), p1.y(), p0.z(), p1.z(), p0.x(), true)};
+  return l;
+}
+
 static int kat_one(const std::string& name, float* r) {
   float* o;
   if (name == "erf") {
@@ -234,6 +263,118 @@ static int kat_one(const std::string& name, float* r) {
     wr3(o, d2);
     *o++ = p2;
     wr_lcg(o, R.lcg);
+  } else if (name == "sphere") {
+    Sphere s(rd3(r), r[3], nullptr);
+    Hit h{};
+    bool hit = s.hit(Ray(rd3(r + 4), rd3(r + 7)), r[10], r[11], h, false);
+    wr_rec(r + 12, hit, h, true);
+  } else if (name == "moving_sphere") {
+    MovingSphere s;
+    s.c0 = rd3(r); s.c1 = rd3(r + 3); s.t0 = r[6]; s.t1 = r[7]; s.radius = r[8]; s.mat = nullptr;
+    Hit h{};
+    bool hit = s.hit(Ray(rd3(r + 9), rd3(r + 12), r[15]), r[16], r[17], h, false);
+    wr_rec(r + 18, hit, h, false);
+  } else if (name == "rect") {
+    const int kind = (int)r[0];
+    Rect q;
+    q.kax = kind == 0 ? 2 : (kind == 1 ? 1 : 0);
+    q.a0 = kind == 2 ? 1 : 0;
+    q.a1 = kind == 0 ? 1 : 2;
+    q.lo0 = r[2]; q.hi0 = r[3]; q.lo1 = r[4]; q.hi1 = r[5]; q.k = r[6]; q.mat = nullptr;
+    Flip f;
+    f.p = &q;
+    const Hitable* hh = r[1] != 0 ? (const Hitable*)&f : (const Hitable*)&q;
+    Hit h{};
+    bool hit = hh->hit(Ray(rd3(r + 7), rd3(r + 10)), r[13], r[14], h, false);
+    o = r + 15;
+    *o++ = hit ? 1.f : 0.f;
+    *o++ = hit ? h.t : 0;
+    *o++ = hit ? h.u : 0;
+    *o++ = hit ? h.v : 0;
+    wr3(o, hit ? h.p : V(0.f));
+    wr3(o, hit ? h.normal : V(0.f));
+  } else if (name == "box") {
+    Store St;
+    const Hitable* bx = kat_box(St, rd3(r), rd3(r + 3));
+    Hit h{};
+    bool hit = bx->hit(Ray(rd3(r + 6), rd3(r + 9)), r[12], r[13], h, false);
+    wr_rec(r + 14, hit, h, true);
+  } else if (name == "xform") {
+    Store St;
+    const Hitable* hh = r[0] == 0 ? (const Hitable*)St.add(new Sphere(rd3(r + 1), r[4], nullptr)) : kat_box(St, rd3(r + 1), rd3(r + 4));
+    for (int l = 2; l >= 0; --l) {  // the wrappers are listed outermost first
+      const float* w = r + 7 + 4 * l;
+      const int kind = (int)w[0];
+      if (kind == 1) {
+        auto* t = St.add(new Translate());
+        t->p = hh;
+        t->off = rd3(w + 1);
+        hh = t;
+      } else if (kind == 2 || kind == 3) {
+        hh = St.add(new Rotate(hh, w[1], kind == 2));
+      } else if (kind == 4) {
+        auto* f = St.add(new Flip());
+        f->p = hh;
+        hh = f;
+      }
+    }
+    Hit h{};
+    bool hit = hh->hit(Ray(rd3(r + 19), rd3(r + 22)), r[25], r[26], h, false);
+    wr_rec(r + 27, hit, h, false);
+  } else if (name == "medium") {
+    Store St;
+    Medium md;
+    md.boundary = r[0] == 0 ? (const Hitable*)St.add(new Sphere(rd3(r + 1), r[4], nullptr)) : kat_box(St, rd3(r + 1), rd3(r + 4));
+    md.density = r[7];
+    md.phase = nullptr;
+    Hit h{};
+    R.lcg = rd_lcg(r + 16);
+    bool hit = md.hit(Ray(rd3(r + 8), rd3(r + 11)), r[14], r[15], h, false);
+    o = r + 18;
+    *o++ = hit ? 1.f : 0.f;
+    *o++ = hit ? h.t : 0;
+    wr_lcg(o, R.lcg);
+  } else if (name == "isotropic") {
+    static const ConstTex cA(V(0.2f, 0.3f, 0.1f)), cB(V(0.9f, 0.9f, 0.9f));
+    CheckerTex alb;
+    alb.even = &cA;
+    alb.odd = &cB;
+    Isotropic iso;
+    iso.albedo = &alb;
+    Hit h{};
+    h.p = rd3(r);
+    h.u = 0.25f;
+    h.v = 0.75f;
+    Scatter s;
+    R.lcg = rd_lcg(r + 3);
+    iso.scatter(Ray(V(0.f), V(1, 0, 0)), h, s);
+    o = r + 5;
+    wr3(o, s.specular_ray.B);
+    wr3(o, s.attenuation);
+    wr_lcg(o, R.lcg);
+  } else if (name == "texture_checker") {
+    static const ConstTex cA(V(0.2f, 0.3f, 0.1f)), cB(V(0.9f, 0.9f, 0.9f)), cC(V(0.1f, 0.5f, 0.8f)), cD(V(0.6f, 0.1f, 0.4f));
+    CheckerTex ab, cd, nested;
+    ab.even = &cA; ab.odd = &cB;
+    cd.even = &cC; cd.odd = &cD;
+    nested.even = &ab; nested.odd = &cd;
+    o = r + 4;
+    wr3(o, (r[0] != 0 ? nested : ab).value(0.f, 0.f, rd3(r + 1)));
+  } else if (name == "texture_noise") {
+    NoiseTex nt;
+    nt.scale = r[0];
+    o = r + 4;
+    wr3(o, nt.value(0.f, 0.f, rd3(r + 1)));
+  } else if (name == "texture_image") {
+    static const ImageTex im = [] {
+      ImageTex t;
+      t.nx = 7;
+      t.ny = 5;
+      t.px = srr_text::gen_image(7, 5, 7u, 0);
+      return t;
+    }();
+    o = r + 2;
+    wr3(o, im.value(r[0], r[1], V(0.f)));
   } else {
     return -1;
   }

@@ -900,10 +900,13 @@ int srr_device_kat(const char* name, int n, int width, float* records) {
   if (!name || !records || n <= 0 || width <= 0) return fail(SRR_EINVAL, "bad KAT arguments");
   static const char* kNames[] = {"erf",   "beckmann11", "beckmann_dist", "beckmann_pdf", "cosine_pdf",
                                  "orennayar_pdf", "dielectric", "metal", "triangle", "aabb", "sqrt",
-                                 "camera", "lights", "light_list"};
-  static const int kWidth[] = {3, 5, 16, 21, 21, 21, 14, 14, 26, 15, 2, 23, 15, 15};
+                                 "camera", "lights", "light_list",
+                                 // scene KATs, kinds 14 .. 23 (kernels.hip KAT_SPHERE ...)
+                                 "sphere", "moving_sphere", "rect", "box", "xform", "medium", "isotropic",
+                                 "texture_checker", "texture_noise", "texture_image"};
+  static const int kWidth[] = {3, 5, 16, 21, 21, 21, 14, 14, 26, 15, 2, 23, 15, 15, 22, 26, 25, 24, 35, 22, 13, 7, 7, 5};
   int kind = -1;
-  for (int k = 0; k < 14; ++k)
+  for (int k = 0; k < 24; ++k)
     if (!strcmp(name, kNames[k])) kind = k;
   if (kind < 0) return fail(SRR_EINVAL, std::string("no device KAT named ") + name);
   if (width != kWidth[kind]) return fail(SRR_EINVAL, std::string("KAT ") + name + ": unexpected record width");
@@ -974,10 +977,155 @@ int srr_device_kat(const char* name, int n, int width, float* records) {
     std::string e;
     if (flatten(ls, lf, e) < 0 || lf.lights.size() != 3) return fail(SRR_EINVAL, "light KAT scene: " + e);
   }
+  // scene KATs: every object is built by the host scene calls and flattened, as a
+  // scene's are (rotation sines, a box's six faces and flips, a medium's boundary list
+  // and phase material, xf_count and its flip bit, the Perlin tables, texture rows).
+  // Kinds 14 .. 19 make one scene per record and concatenate the tables (`base`: each
+  // record's first rows, kernels.hip kat_scene); the texture kinds make one scene.
+  std::vector<int32_t> base;
+  std::vector<uint8_t> images;
+  std::vector<float> perlin_ranvec;
+  std::vector<int32_t> perlin_perm;
+  if (kind >= 14) {
+    std::string e;
+    Flat f;
+    auto flat_of = [&](Scene& s, int h) {  // world = hitable_list{h}, no lights, any camera
+      s.world = s.list(&h, 1);
+      s.lights = s.list(&h, 0);
+      const float lf3[3] = {0, 0, -1}, la3[3] = {0, 0, 0}, up[3] = {0, 1, 0};
+      s.camera(lf3, la3, up, 40, 1, 0, 1, 0, 1);
+      s.has_camera = true;
+      return flatten(s, f, e) >= 0;
+    };
+    auto prim = [](Scene& s, float kind_, const float* a, const float* b) {  // a sphere (a, b[0]) or a box (a, b)
+      return kind_ == 0 ? s.sphere(a, b[0], -1) : s.box(a, b, -1);
+    };
+    auto tex_of_sphere = [&](int k) { return f.mats[f.spheres[k].mat].tex; };
+    const float org[3] = {0, 0, 0};
+    if (kind <= 19) {
+      for (int q = 0; q < n; ++q) {
+        const float* r = records + (size_t)q * width;
+        Scene s;
+        int h = -1;
+        if (kind == 14) h = s.sphere(r, r[3], -1);
+        else if (kind == 15) h = s.moving_sphere(r, r + 3, r[6], r[7], r[8], -1);
+        else if (kind == 16) {
+          h = s.rect(r[0] == 0 ? H_XY : (r[0] == 1 ? H_XZ : H_YZ), r[2], r[3], r[4], r[5], r[6], -1);
+          if (r[1] != 0) h = s.wrap(H_FLIP, h, nullptr);
+        } else if (kind == 17) h = s.box(r, r + 3, -1);
+        else if (kind == 18) {
+          h = prim(s, r[0], r + 1, r + 4);
+          for (int l = 2; l >= 0; --l) {  // the wrappers are listed outermost first
+            const float* w = r + 7 + 4 * l;
+            if (w[0] == 1) h = s.wrap(H_TRANSLATE, h, w + 1);
+            else if (w[0] == 2 || w[0] == 3) h = s.rotate(w[0] == 2 ? H_ROTY : H_ROTX, h, w[1]);
+            else if (w[0] == 4) h = s.wrap(H_FLIP, h, nullptr);
+          }
+        } else {
+          const float one[3] = {1, 1, 1};
+          HTex t;
+          t.kind = TEX_CONST;
+          std::memcpy(t.c, one, 12);
+          h = s.medium(prim(s, r[0], r + 1, r + 4), r[7], s.add_tex(t));
+        }
+        if (!flat_of(s, h)) return fail(SRR_EINVAL, "KAT scene: " + e);
+        const int32_t b8[8] = {(int32_t)lf.objs.size(),  f.n_world,
+                               (int32_t)lf.xforms.size(), (int32_t)lf.spheres.size(),
+                               (int32_t)lf.rects.size(),  (int32_t)lf.media.size(),
+                               (int32_t)lf.mats.size(),   (int32_t)lf.texs.size()};
+        base.insert(base.end(), b8, b8 + 8);
+        lf.objs.insert(lf.objs.end(), f.objs.begin(), f.objs.end());
+        lf.xforms.insert(lf.xforms.end(), f.xforms.begin(), f.xforms.end());
+        lf.spheres.insert(lf.spheres.end(), f.spheres.begin(), f.spheres.end());
+        lf.rects.insert(lf.rects.end(), f.rects.begin(), f.rects.end());
+        lf.media.insert(lf.media.end(), f.media.begin(), f.media.end());
+        lf.mats.insert(lf.mats.end(), f.mats.begin(), f.mats.end());
+        lf.texs.insert(lf.texs.end(), f.texs.begin(), f.texs.end());
+      }
+    } else {
+      Scene s;
+      auto constant = [&](float x, float y, float z) {
+        HTex t;
+        t.kind = TEX_CONST;
+        t.c[0] = x, t.c[1] = y, t.c[2] = z;
+        return s.add_tex(t);
+      };
+      auto checker = [&](int even, int odd) {
+        HTex t;
+        t.kind = TEX_CHECKER;
+        t.even = even;
+        t.odd = odd;
+        return s.add_tex(t);
+      };
+      auto shown = [&](int tex) {  // a texture flattens only if a placed material reaches it
+        const float prm[4] = {0, 0, 0, 0};
+        return s.sphere(org, 1, s.material(MAT_LAMBERTIAN, tex, prm));
+      };
+      std::vector<int> hs;
+      std::vector<float> scales;
+      if (kind == 20) {  // the phase material of constant_medium(sphere, 1, checker(A, B))
+        hs.push_back(s.medium(s.sphere(org, 1, -1), 1.0f, checker(constant(0.2f, 0.3f, 0.1f), constant(0.9f, 0.9f, 0.9f))));
+      } else if (kind == 21) {  // checker(A, B) and checker(checker(A, B), checker(C, D))
+        const int A = constant(0.2f, 0.3f, 0.1f), B = constant(0.9f, 0.9f, 0.9f), C = constant(0.1f, 0.5f, 0.8f),
+                  D = constant(0.6f, 0.1f, 0.4f);
+        hs.push_back(shown(checker(A, B)));
+        hs.push_back(shown(checker(checker(A, B), checker(C, D))));
+      } else if (kind == 22) {  // one noise_texture per scale the records name
+        for (int q = 0; q < n; ++q) {
+          const float sc = records[(size_t)q * width];
+          size_t k = 0;
+          while (k < scales.size() && std::memcmp(&scales[k], &sc, 4) != 0) ++k;
+          if (k == scales.size()) {
+            if (scales.size() == 64) return fail(SRR_EINVAL, "noise KAT: more than 64 scales");
+            scales.push_back(sc);
+            HTex t;
+            t.kind = TEX_NOISE;
+            t.c[0] = sc;
+            hs.push_back(shown(s.add_tex(t)));
+          }
+          aux[4 * (size_t)q] = (float)k;
+        }
+      } else {  // the 7 x 5 synthetic image of oracle/ref/kat.inc
+        HTex t;
+        t.kind = TEX_IMAGE;
+        t.nx = 7;
+        t.ny = 5;
+        t.px = gen_image(7, 5, 7u, 0);
+        hs.push_back(shown(s.add_tex(std::move(t))));
+      }
+      // (a rect between the spheres keeps them plain list objects, not a sphere group)
+      std::vector<int> kids;
+      for (int h : hs) {
+        kids.push_back(h);
+        kids.push_back(s.rect(H_XY, 0, 1, 0, 1, 0, -1));
+      }
+      if (!flat_of(s, s.list(kids.data(), (int)kids.size()))) return fail(SRR_EINVAL, "KAT scene: " + e);
+      if (kind >= 21)  // aux: the record's texture row after flattening
+        for (int q = 0; q < n; ++q) {
+          const float* r = records + (size_t)q * width;
+          const int k = kind == 21 ? (r[0] != 0 ? 1 : 0) : (kind == 22 ? (int)aux[4 * (size_t)q] : 0);
+          aux[4 * (size_t)q] = (float)tex_of_sphere(k);
+        }
+      lf = f;
+    }
+    images = f.images;
+    perlin_ranvec = f.perlin_ranvec;
+    perlin_perm = f.perlin_perm;
+    if (kind != 23) images.clear();
+  }
   float* d_rec = nullptr;
   float* d_aux = nullptr;
   DStandaloneTri* d_tris = nullptr;
   DCamera* d_cams = nullptr;
+  DObj* d_objs = nullptr;
+  DXform* d_xforms = nullptr;
+  DMedium* d_media = nullptr;
+  DMat* d_mats = nullptr;
+  DTex* d_texs = nullptr;
+  uint8_t* d_images = nullptr;
+  float* d_ranvec = nullptr;
+  int32_t* d_perm = nullptr;
+  int32_t* d_base = nullptr;
   DRect* d_rects = nullptr;
   DSphere* d_sph = nullptr;
   DStandaloneTri* d_stris = nullptr;
@@ -1002,12 +1150,23 @@ int srr_device_kat(const char* name, int n, int width, float* records) {
   upload(d_sph, lf.spheres);
   upload(d_stris, lf.stris);
   upload(d_lights, lf.lights);
-  const KatTables kt{d_cams, d_rects, d_sph, d_stris, d_lights, (int)lf.lights.size()};
+  upload(d_objs, lf.objs);
+  upload(d_xforms, lf.xforms);
+  upload(d_media, lf.media);
+  upload(d_mats, lf.mats);
+  upload(d_texs, lf.texs);
+  upload(d_images, images);
+  upload(d_ranvec, perlin_ranvec);
+  upload(d_perm, perlin_perm);
+  upload(d_base, base);
+  const KatTables kt{d_cams, d_rects, d_sph, d_stris, d_lights, (int)lf.lights.size(), d_objs, d_xforms, d_media,
+                     d_mats, d_texs, d_images, d_ranvec, d_perm, d_base};
   if (!rc && launch_kat(kind, n, width, d_rec, d_aux, d_tris, kt) < 0) rc = fail(SRR_EIO, "KAT kernel launch failed");
   if (!rc && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(records, d_rec, rb, hipMemcpyDeviceToHost) != hipSuccess))
     rc = fail(SRR_EIO, "KAT kernel failed");
   for (void* p : {(void*)d_rec, (void*)d_aux, (void*)d_tris, (void*)d_cams, (void*)d_rects, (void*)d_sph,
-                  (void*)d_stris, (void*)d_lights})
+                  (void*)d_stris, (void*)d_lights, (void*)d_objs, (void*)d_xforms, (void*)d_media, (void*)d_mats,
+                  (void*)d_texs, (void*)d_images, (void*)d_ranvec, (void*)d_perm, (void*)d_base})
     (void)hipFree(p);
   return rc;
 }

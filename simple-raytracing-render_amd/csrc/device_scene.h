@@ -43,11 +43,14 @@ enum XformKind : int32_t { XF_FLIP = 0, XF_TRANSLATE = 1, XF_ROTY = 2, XF_ROTX =
 
 struct DXform {  // one instance wrapper (hitable.h:35-203, aarect.h:149-171)
   int32_t kind;
-  float a, b, c;  // translate: offset; rotate: sin, cos
+  float a, b, c;  // translate: offset; rotate: sin, cos, and c != 0: negate the normal before
+                  // rotating it on the way out (flip_normals directly inside this rotation)
 };
 
 // DObj::xf_count: moving transforms (translate / rotate) in the low bits, and
-// kXfFlipBit when an odd number of flip_normals wrap the object
+// kXfFlipBit when an odd number of flip_normals wrap the object outside every
+// rotation of its chain
+
 constexpr int32_t kXfFlipBit = 1 << 30;
 constexpr int32_t kXfCountMask = 0xFFFF;
 

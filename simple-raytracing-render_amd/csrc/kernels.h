@@ -151,7 +151,10 @@ int paths_block_lanes(const SceneView& S);  // k_paths lanes per block for this 
 int launch_paths(const SceneView& S, const PathWork& W, int all_families, hipStream_t st);
 // device known-answer tests (srr_device_kat); kind = dev::KatKind
 // device tables of the camera / light KATs (srr_device_kat builds them with the
-// host scene code: one camera per record, one light list for all records)
+// host scene code: one camera per record, one light list for all records), and of
+// the scene KATs (sphere ... texture_image): the flattened tables of one host scene
+// per record, concatenated, with each record's first rows in `base` (kernels.hip
+// kat_scene; nullptr: one scene for all records)
 struct KatTables {
   const DCamera* cams;
   const DRect* rects;
@@ -159,6 +162,15 @@ struct KatTables {
   const DStandaloneTri* stris;
   const DLight* lights;
   int n_lights;
+  const DObj* objs;
+  const DXform* xforms;
+  const DMedium* media;
+  const DMat* mats;
+  const DTex* texs;
+  const uint8_t* images;
+  const float* perlin_ranvec;
+  const int32_t* perlin_perm;
+  const int32_t* base;  // [n][8]: objs, world count, xforms, spheres, rects, media, mats, texs
 };
 int launch_kat(int kind, int n, int w, float* d_rec, const float* d_aux, const DStandaloneTri* d_tris,
                const KatTables& kt);

@@ -1073,6 +1073,10 @@ SRR_D void rot_in(const DXform& x, Ray& r) {
 template <int IA>  // ...and the record coming out
 SRR_D void rot_out(const DXform& x, V3& p, V3& n) {
   const float s = x.a, c = x.b;
+  // an odd number of flip_normals between this rotation and the next one inside it
+  // (DXform::c, set by the flattener): the reference negates the normal before it
+  // rotates it, and a component that is a sum of zeros takes its sign from that order
+  if (x.c != 0.0f) n = -n;
   V3 pp = p, nn = n;
   pp.set(IA, c * p[IA] + s * p.z);
   pp.z = -s * p[IA] + c * p.z;
@@ -1104,7 +1108,7 @@ SRR_D void chain_out(const SceneView& S, const DObj& ob, V3& p, V3& n) {
     else if (x.kind == XF_ROTY) rot_out<0>(x, p, n);
     else rot_out<1>(x, p, n);
   }
-  if (ob.xf_count & kXfFlipBit) n = -n;  // flip_normals (aarect.h:149-171), exact in any order
+  if (ob.xf_count & kXfFlipBit) n = -n;  // the flip_normals (aarect.h:149-171) outside every rotation of the chain
 }
 
 struct ObjHit {
@@ -1634,14 +1638,20 @@ SRR_D void store_hit(const SceneView& S, const PathState& P, int p, const WorldH
 // (oracle/restate.cpp kMixtureGuard): stop after kMixtureGuard attempts and keep
 // the last attempt (pdf 0; the record's division then gives inf/NaN, de_nan'd).
 constexpr int kMixtureGuard = 100000;
+// (int)x as the reference's host converts (cvttss2si / cvttsd2si): INT_MIN unless x is
+// strictly inside the int range, NaN included.  The device's own conversion saturates
+// (a huge positive x gives INT_MAX), which would pick the last image column / row
+// where the reference picks the first, and other Perlin lattice cells.
+SRR_D int cvt_i32_ref(float x) { return fabsf(x) < 2147483648.0f ? (int)x : INT_MIN; }
+SRR_D int cvt_i32_ref(double x) { return fabs(x) < 2147483648.0 ? (int)x : INT_MIN; }
 SRR_D V3 tex_value_slow(const SceneView& S, int ti, float u, float v, V3 p) {
   // checker_texture recursion (texture.h:13-19) unrolled to a few levels
   for (int guard = 0; guard < 8; ++guard) {
     const DTex& T = S.texs[ti];
     if (T.kind == TEX_CONST) return v3(T.c[0], T.c[1], T.c[2]);
     if (T.kind == TEX_IMAGE) {  // texture.h:58-70
-      int i = (u) * T.nx;
-      int j = (1 - v) * T.ny - 0.001;
+      int i = cvt_i32_ref((u) * T.nx);
+      int j = cvt_i32_ref((1 - v) * T.ny - 0.001);
       if (i < 0) i = 0;
       if (j < 0) j = 0;
       if (i > T.nx - 1) i = T.nx - 1;
@@ -1667,7 +1677,7 @@ SRR_D V3 tex_value_slow(const SceneView& S, int ti, float u, float v, V3 p) {
     for (int oct = 0; oct < 7; ++oct) {
       float fx = floorf(tp.x), fy = floorf(tp.y), fz = floorf(tp.z);
       float uu = tp.x - fx, vv = tp.y - fy, ww = tp.z - fz;
-      int i = (int)fx, j = (int)fy, k = (int)fz;
+      int i = cvt_i32_ref(fx), j = cvt_i32_ref(fy), k = cvt_i32_ref(fz);
       float hu = uu * uu * (3 - 2 * uu), hv = vv * vv * (3 - 2 * vv), hw = ww * ww * (3 - 2 * ww);
       float acc = 0;
       for (int a = 0; a < 2; a++)
@@ -3935,7 +3945,10 @@ __global__ void __launch_bounds__(256) k_merl_lookup(const double* table, int64_
 // test can compare them bit for bit with the reference's outputs.
 // aux: 4 host-computed floats per record (Beckmann alphas, Oren-Nayar A / B).
 enum KatKind : int { KAT_ERF, KAT_BECK11, KAT_BECK_DIST, KAT_BECK_PDF, KAT_COSINE, KAT_ORENNAYAR, KAT_DIELECTRIC,
-                     KAT_METAL, KAT_TRIANGLE, KAT_AABB, KAT_SQRT, KAT_CAMERA, KAT_LIGHTS, KAT_LIGHT_LIST };
+                     KAT_METAL, KAT_TRIANGLE, KAT_AABB, KAT_SQRT, KAT_CAMERA, KAT_LIGHTS, KAT_LIGHT_LIST,
+                     // scene KATs (one flattened host scene per record, kat_scene)
+                     KAT_SPHERE, KAT_MSPHERE, KAT_RECT, KAT_BOX, KAT_XFORM, KAT_MEDIUM, KAT_ISOTROPIC, KAT_TEX_CHECKER,
+                     KAT_TEX_NOISE, KAT_TEX_IMAGE };
 
 SRR_D V3 kat3(const float* p) { return v3(p[0], p[1], p[2]); }
 SRR_D void kat_put3(float* p, V3 v) { p[0] = v.x, p[1] = v.y, p[2] = v.z; }
@@ -3950,12 +3963,140 @@ SRR_D void kat_put_pcg(float* p, uint64_t s) {
   for (int k = 0; k < 4; ++k) p[k] = (float)((s >> (16 * k)) & 0xFFFF);
 }
 
+// The scene of record q of a scene KAT: srr_device_kat flattens one host scene per
+// record (or one for all records: base == nullptr) and concatenates the tables;
+// base[8 q ..] = first row of the record's objs, its world count, and the first rows of
+// its xforms, spheres, rects, media, mats, texs -- every index inside stays as
+// flatten() wrote it.
+SRR_D SceneView kat_scene(const KatTables& kt, int q) {
+  int32_t b[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (kt.base)
+    for (int k = 0; k < 8; ++k) b[k] = kt.base[8 * (size_t)q + k];
+  SceneView S{};
+  S.objs = kt.objs + b[0];
+  S.n_world = b[1];
+  S.xforms = kt.xforms + b[2];
+  S.spheres = kt.spheres + b[3];
+  S.rects = kt.rects + b[4];
+  S.media = kt.media + b[5];
+  S.mats = kt.mats + b[6];
+  S.texs = kt.texs + b[7];
+  S.images = kt.images;
+  S.perlin_ranvec = kt.perlin_ranvec;
+  S.perlin_perm = kt.perlin_perm;
+  return S;
+}
+
+// hitable_list::hit (hitable_list.h:21-33) over the record's world objects -- one
+// primitive, a box's six rects, either under its instance chain -- and the winner's
+// record.  list_hit gives hit and t; the object that keeps the record is the last
+// one to report a hit against the closest-so-far, found with the same prim_hit.
+// out: hit t p(3) n(3) u v (zeros on a miss; hit = -1 if the two walks disagree)
+SRR_D void kat_list_record(const SceneView& S, const Ray& ray, float tmin, float tmax, float* out) {
+  const TraceCtx cx{nullptr, nullptr, nullptr};
+  float t = 0;
+  const bool h = list_hit<0>(S, 0, S.n_world, ray, tmin, tmax, t, cx);
+  int win = -1;
+  float closest = tmax;
+  for (int k = 0; k < S.n_world; ++k) {
+    const DObj ob = S.objs[k];
+    float th;
+    if (prim_hit<0>(S, ob, chain_in<0>(S, ob, ray), tmin, closest, false, th)) {
+      closest = th;
+      win = k;
+    }
+  }
+  for (int k = 0; k < 10; ++k) out[k] = 0;
+  if ((win >= 0) != h) out[0] = -1.f;
+  else if (h) {
+    const DObj ob = S.objs[win];
+    HitRec hr;
+    hr.u = hr.v = 0;
+    prim_record<0>(S, ob, chain_in<0>(S, ob, ray), t, -1, hr);
+    chain_out(S, ob, hr.p, hr.n);
+    out[0] = 1.f;
+    out[1] = t;
+    kat_put3(out + 2, hr.p);
+    kat_put3(out + 5, hr.n);
+    out[8] = hr.u;
+    out[9] = hr.v;
+  }
+}
+
 __global__ void k_kat(int kind, int n, int w, float* rec, const float* aux, const DStandaloneTri* tris, KatTables kt) {
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  // the scene KATs run one wave per record (their list walks read the object tables
+  // through uni(), which wants every lane of the wave at the same object); lane 0 stores
+  const bool wave_per_record = kind >= KAT_SPHERE;
+  const int q = wave_per_record ? (int)blockIdx.x : (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (q >= n) return;
   float* r = rec + (size_t)q * w;
   const float* a = aux + 4 * (size_t)q;
+  float out[10];
+  int out_at = 0, out_n = 0;
   switch (kind) {
+    case KAT_SPHERE:  // in: c r o d tmin tmax | out: hit t p n u v
+      kat_list_record(kat_scene(kt, q), Ray{kat3(r + 4), kat3(r + 7), 0.0f}, r[10], r[11], out);
+      out_at = 12, out_n = 10;
+      break;
+    case KAT_MSPHERE:  // in: c0 c1 t0 t1 r o d time tmin tmax | out: hit t p n
+      kat_list_record(kat_scene(kt, q), Ray{kat3(r + 9), kat3(r + 12), r[15]}, r[16], r[17], out);
+      out_at = 18, out_n = 8;
+      break;
+    case KAT_RECT: {  // in: kind flip lo0 hi0 lo1 hi1 k o d tmin tmax | out: hit t u v p n
+      float o2[10];
+      kat_list_record(kat_scene(kt, q), Ray{kat3(r + 7), kat3(r + 10), 0.0f}, r[13], r[14], o2);
+      out[0] = o2[0], out[1] = o2[1], out[2] = o2[8], out[3] = o2[9];
+      for (int k = 0; k < 6; ++k) out[4 + k] = o2[2 + k];
+      out_at = 15, out_n = 10;
+      break;
+    }
+    case KAT_BOX:  // in: p0 p1 o d tmin tmax | out: hit t p n u v
+      kat_list_record(kat_scene(kt, q), Ray{kat3(r + 6), kat3(r + 9), 0.0f}, r[12], r[13], out);
+      out_at = 14, out_n = 10;
+      break;
+    case KAT_XFORM:  // in: prim a b 3 x (kind v) o d tmin tmax | out: hit t p n
+      kat_list_record(kat_scene(kt, q), Ray{kat3(r + 19), kat3(r + 22), 0.0f}, r[25], r[26], out);
+      out_at = 27, out_n = 8;
+      break;
+    case KAT_MEDIUM: {  // in: boundary a b density o d tmin tmax lcg | out: hit t lcg
+      const SceneView S = kat_scene(kt, q);
+      const TraceCtx cx{nullptr, nullptr, nullptr};
+      const DObj ob = S.objs[0];
+      Rng rng{kat_lcg(r + 16), 0};
+      float t = 0;
+      const bool h = ob.kind == OBJ_MEDIUM &&
+                     medium_hit<0>(S, S.media[ob.idx], chain_in<0>(S, ob, Ray{kat3(r + 8), kat3(r + 11), 0.0f}), r[14],
+                                   r[15], rng, t, cx);
+      out[0] = h ? 1.f : 0.f;
+      out[1] = h ? t : 0;
+      kat_put_lcg(out + 2, rng.lcg);
+      out_at = 18, out_n = 4;
+      break;
+    }
+    case KAT_ISOTROPIC: {  // in: p lcg | out: dir attenuation lcg   (the medium's phase material, u = 0.25, v = 0.75)
+      const SceneView S = kat_scene(kt, q);
+      Rng rng{kat_lcg(r + 3), 0};
+      float4 rc;
+      bool sp;
+      V3 nd;
+      float nt;
+      scatter<FAM_SPEC>(S, S.mats[S.media[0].phase_mat], v3(1, 0, 0), 0.0f, kat3(r), v3(1, 0, 0), 0.25f, 0.75f, rng, rc,
+                        sp, nd, nt);
+      kat_put3(out, nd);
+      out[3] = rc.x, out[4] = rc.y, out[5] = rc.z;
+      kat_put_lcg(out + 6, rng.lcg);
+      out_at = 5, out_n = 8;
+      break;
+    }
+    case KAT_TEX_CHECKER:  // in: which p | out: rgb       (aux: the record's texture row)
+    case KAT_TEX_NOISE:    // in: scale p | out: rgb
+      kat_put3(out, tex_value(kat_scene(kt, q), (int)a[0], 0.f, 0.f, kat3(r + 1)));
+      out_at = 4, out_n = 3;
+      break;
+    case KAT_TEX_IMAGE:  // in: u v | out: rgb
+      kat_put3(out, tex_value(kat_scene(kt, q), (int)a[0], r[0], r[1], v3(0.f)));
+      out_at = 2, out_n = 3;
+      break;
     case KAT_ERF:
       r[1] = Erf(r[0]);
       r[2] = ErfInv(r[0]);
@@ -4105,6 +4246,8 @@ __global__ void k_kat(int kind, int n, int w, float* rec, const float* aux, cons
       break;
     }
   }
+  if (wave_per_record && threadIdx.x == 0)
+    for (int k = 0; k < out_n; ++k) r[out_at + k] = out[k];
 }
 
 // Test infrastructure (srr_device_libm): one libm routine of the device build over
@@ -4464,7 +4607,9 @@ int launch_merl_lookup(const double* table, int64_t n, const double* angles, dou
 
 int launch_kat(int kind, int n, int w, float* d_rec, const float* d_aux, const DStandaloneTri* d_tris,
                const KatTables& kt) {
-  hipLaunchKernelGGL(dev::k_kat, dim3((n + 63) / 64), dim3(64), 0, 0, kind, n, w, d_rec, d_aux, d_tris, kt);
+  // a thread per record; the scene KATs a wave per record
+  const int blocks = kind >= dev::KAT_SPHERE ? n : (n + 63) / 64;
+  hipLaunchKernelGGL(dev::k_kat, dim3(blocks), dim3(64), 0, 0, kind, n, w, d_rec, d_aux, d_tris, kt);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

@@ -1228,14 +1228,23 @@ struct Flattener {
   bool walk(int h, std::vector<DXform> ch, std::vector<DObj>& out, bool in_medium) {
     const HObj& o = S.obj[h];
     auto emit = [&](int kind, int idx) {
-      // flip_normals only negates the normal, which commutes with the rotations
-      // and is untouched by translations: the chain keeps the moving transforms
-      // and the flips become one parity bit (kXfFlipBit), applied last on the way out
+      // flip_normals only negates the normal, which translations leave alone: the
+      // chain keeps the moving transforms.  A flip outside every rotation of the chain
+      // goes into one parity bit (kXfFlipBit), applied last on the way out.  A flip
+      // inside a rotation is marked on the nearest rotation outside it (DXform::c, a
+      // parity again), which negates the normal before rotating it as the reference
+      // does: rotating first gives the same values, but a component that is a sum of
+      // zeros (c * 0 + s * 0) can come out with the other sign.
       std::vector<DXform> moving;
-      int flips = 0;
+      int flips = 0, last_rot = -1;
       for (const DXform& x : ch) {
-        if (x.kind == XF_FLIP) ++flips;
-        else moving.push_back(x);
+        if (x.kind == XF_FLIP) {
+          if (last_rot < 0) ++flips;
+          else moving[last_rot].c = moving[last_rot].c != 0.0f ? 0.0f : 1.0f;
+        } else {
+          if (x.kind == XF_ROTY || x.kind == XF_ROTX) last_rot = (int)moving.size();
+          moving.push_back(x);
+        }
       }
       DObj d;
       d.kind = kind;

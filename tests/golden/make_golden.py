@@ -4,6 +4,8 @@ code (oracle/_ref/ref_harness, built by `make -C oracle ref` from
 descriptions (inputs) and the reference's outputs for them.
 
     python tests/golden/make_golden.py
+    python tests/golden/make_golden.py --kats sphere rect ...   # only these KATs; every
+                                                                # other fixture stays as it is
 
 Fixture list and layouts: tests/golden/README.md.
 """
@@ -42,7 +44,10 @@ RENDERS = [
 
 KATS = [("erf", 512), ("beckmann11", 512), ("beckmann_dist", 512), ("beckmann_pdf", 512), ("cosine_pdf", 256),
         ("orennayar_pdf", 256), ("dielectric", 256), ("metal", 256), ("triangle", 1024), ("aabb", 1024),
-        ("camera", 256), ("lights", 256), ("light_list", 256), ("merl", 2048), ("merl_same", 4096)]
+        ("camera", 256), ("lights", 256), ("light_list", 256), ("merl", 2048), ("merl_same", 4096),
+        # scene KATs: a constructed half of edge blocks and a pseudo-random half (README.md)
+        ("sphere", 1024), ("moving_sphere", 1024), ("rect", 1024), ("box", 1024), ("xform", 1024), ("medium", 1024),
+        ("isotropic", 1024), ("texture_checker", 1024), ("texture_noise", 1024), ("texture_image", 1024)]
 
 
 # The MERL KATs' out == in records are decided by the last-ulp rounding of glibc's
@@ -72,9 +77,29 @@ def run(*args):
     return out.stdout
 
 
+def only_kats(names):
+    """Generate the named KATs alone and add their entries to golden.json."""
+    sizes = dict(KATS)
+    unknown = [k for k in names if k not in sizes or k in MERL_KATS]
+    if unknown:
+        sys.exit(f"--kats: cannot generate {unknown} alone")
+    path = os.path.join(HERE, "golden.json")
+    with open(path) as f:
+        meta = json.load(f)
+    for name in names:
+        run("kat", name, sizes[name], 1234567, os.path.join(HERE, f"kat_{name}.bin"))
+        meta["kats"][name] = sizes[name]
+    with open(path, "w") as f:
+        json.dump(meta, f, indent=1, sort_keys=True)
+
+
 def main():
     if not os.path.exists(HARNESS):
         sys.exit("build the reference harness first: make -C oracle ref")
+    if len(sys.argv) > 1:
+        if sys.argv[1] != "--kats" or len(sys.argv) < 3:
+            sys.exit("usage: make_golden.py [--kats NAME ...]")
+        return only_kats(sys.argv[2:])
     libm = host_libm()
     meta = {"renders": {}, "kats": {}, "merl_libm": MERL_LIBM_PIN}
     for name, fac, nx, ny, spp, md in RENDERS:

@@ -1,7 +1,9 @@
 """Device known-answer tests: the HIP implementations of the reference's
 per-function code (material.h, pdf.h, microfacet_distribution.h, common.h,
 triangle.h, aabb.h, camera.h, light sampling of aarect.h / sphere.h / triangle.h /
-hitable_list.h), run through srr_device_kat on the reference's own KAT
+hitable_list.h; sphere.h, moving_sphere.h, aarect.h, box.h, the instance wrappers
+of hitable.h, constant_medium.h, isotropic and texture.h / perlin.h on flattened
+host scenes), run through srr_device_kat on the reference's own KAT
 records (tests/golden/kat_*.bin, made by oracle/ref from the reference's
 functions), must reproduce the reference's outputs bit for bit."""
 import ctypes
@@ -9,6 +11,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import kat_classes
 import oracle_bind as ob
 from srr import capi
 
@@ -17,7 +20,11 @@ OUT = {"erf": range(1, 3), "beckmann11": range(3, 5), "beckmann_dist": range(7, 
        "beckmann_pdf": range(12, 21), "cosine_pdf": list(range(9, 16)) + [19, 20],
        "orennayar_pdf": list(range(9, 16)) + [19, 20], "dielectric": range(9, 14), "metal": range(9, 14),
        "triangle": range(16, 26), "aabb": [14], "camera": range(14, 23), "lights": range(5, 15),
-       "light_list": range(5, 15)}
+       "light_list": range(5, 15),
+       # scene KATs (tests/golden/README.md): every output column, no record exempted
+       "sphere": range(12, 22), "moving_sphere": range(18, 26), "rect": range(15, 25), "box": range(14, 24),
+       "xform": range(27, 35), "medium": range(18, 22), "isotropic": range(5, 13), "texture_checker": range(4, 7),
+       "texture_noise": range(4, 7), "texture_image": range(2, 5)}
 
 
 def device_kat(name, rec):
@@ -43,7 +50,8 @@ def test_device_kat_bitexact(name):
     bad = np.flatnonzero(~eq.all(axis=1))
     per_col = {c: int((~eq[:, k]).sum()) for k, c in enumerate(cols) if (~eq[:, k]).any()}
     for i in bad[:4]:
-        print(name, "record", i, "in", rec[i, :cols[0]].tolist(), "\n  ref", rec[i, cols].tolist(),
+        print(name, "record", i, f"[{kat_classes.classes_of(name, rec, i)}]", "in", rec[i, :cols[0]].tolist(),
+              "\n  ref", rec[i, cols].tolist(),
               "\n  dev", got[i, cols].tolist())
     assert len(bad) == 0, f"{name}: {len(bad)} of {len(rec)} records differ; per output column {per_col}"
 

@@ -1,0 +1,32 @@
+"""The edge cases the scene KATs were built for are really in the committed
+files.  Every record of tests/golden/kat_{sphere ... texture_image}.bin is
+classified from its inputs and the reference's outputs alone (tests/kat_classes.py:
+float32 arithmetic in numpy, no device and no restatement code): each class of the
+issue's table holds at least 8 records, and each KAT with a hit flag has between a
+quarter and three quarters of hits.  This is what lets the bit-exact comparisons
+(test_oracle_pins.py, test_device_kat.py) fail where the code can go wrong."""
+import numpy as np
+
+import kat_classes as kc
+import oracle_bind as ob
+
+MIN_PER_CLASS = 8
+
+
+def test_kat_edge_classes_populated():
+    short, report = [], []
+    for name in kc.NEW_KATS:
+        rec = ob.read_kat(name)
+        assert 512 <= len(rec) <= 1024, (name, len(rec))
+        counts = {k: int(m.sum()) for k, m in kc.classify(name, rec).items()}
+        report.append(f"{name} ({len(rec)} records): " + ", ".join(f"{k}: {v}" for k, v in counts.items()))
+        short += [f"{name}: {k}: {v}" for k, v in counts.items() if v < MIN_PER_CLASS]
+        if name in kc.HIT:
+            flag = rec[:, kc.HIT[name]]
+            assert np.isin(flag, (0.0, 1.0)).all(), name
+            frac = float((flag == 1).mean())
+            report.append(f"{name}: hits {frac:.3f}")
+            if not 0.25 <= frac <= 0.75:
+                short.append(f"{name}: hit fraction {frac:.3f}")
+    print("\n".join(report))
+    assert not short, "classes with fewer than 8 records, or a hit fraction outside [0.25, 0.75]: " + "; ".join(short)
