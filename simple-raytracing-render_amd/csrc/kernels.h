@@ -144,6 +144,58 @@ constexpr int kPathsWorldLdsBytes = 8192;  // == kernels.hip kWorldLdsBytes
 #define SRR_LDS_NODES 96
 #endif
 constexpr int kPathsLdsNodes = SRR_LDS_NODES;  // BVH4 nodes cached in LDS by k_paths (128 B each)
+
+// k_paths' camera-ray ring (kernels.hip ring_put / ring_get): one entry per lane, the
+// path's camera ray and RNG streams and, in the variants that trace a chunk's camera
+// rays where they are generated (no media, not quad-cooperative), the ray's world hit
+constexpr int kRingRayWords = 11;            // o.xyz, d.xyz, time, lcg (2 words), pcg (2 words)
+constexpr int kRingHitWord = kRingRayWords;  // obj, prim, t: words 11, 12, 13
+constexpr int kRingWordsHit = kRingHitWord + 3;
+constexpr int ring_words(bool pretrace) { return pretrace ? kRingWordsHit : kRingRayWords; }
+static_assert(ring_words(false) == 11 && ring_words(true) == 14 && kRingHitWord + 2 < kRingWordsHit, "ring entry layout");
+
+// k_paths' LDS by block shape.  1,024 lanes (one block per CU, the same 4 waves per
+// SIMD as four 256-lane blocks): one allocation of the CU's 160 KB, which beside the
+// 8 KB world, 8 B x kPathsLdsStack per lane of stacks and the ring (44 B per lane, 56 B
+// with the hit) caches the top BVH4 nodes: at kPathsLdsStack 8, 344 beside an 11-word
+// ring and 248 beside a 14-word one.  256 lanes: four blocks share the CU, 40 KB each.
+constexpr int kLdsPerCu = 160 * 1024;
+constexpr int paths_lds_fixed(int bs, bool wl) {  // world tables, both stack arrays, alignment slack
+  return (wl ? kPathsWorldLdsBytes : 16) + 8 * kPathsLdsStack * bs + bs;
+}
+constexpr int paths_lds_nodes_big(bool pretrace) {
+  return (kLdsPerCu - paths_lds_fixed(1024, true) - 4 * ring_words(pretrace) * 1024) / 128;
+}
+// 256-lane blocks with the world tables in global memory keep kPathsLdsNodes nodes
+// beside the 11-word ring; the 14-word ring leaves room for fewer
+constexpr int paths_lds_nodes_global(bool pretrace) {
+  const int room = (kLdsPerCu / 4 - paths_lds_fixed(256, false) - 4 * ring_words(pretrace) * 256) / 128;
+  return room < kPathsLdsNodes ? room : kPathsLdsNodes;
+}
+constexpr int kPathsLdsNodesSmall = 8;  // 256-lane blocks, world in LDS, with a ring
+// nodes cached by the variant: bs lanes per block, wl world tables in LDS, ring (not the
+// quad-cooperative flow), pretrace (ring entries carry the hit)
+constexpr int paths_lds_nodes(int bs, bool wl, bool ring, bool pretrace) {
+  return bs == 1024 ? paths_lds_nodes_big(pretrace)
+                    : (wl && ring) ? kPathsLdsNodesSmall : ring ? paths_lds_nodes_global(pretrace) : kPathsLdsNodes;
+}
+constexpr int paths_lds_bytes(int bs, bool wl, bool ring, bool pretrace) {
+  return (wl ? kPathsWorldLdsBytes : 16) + 8 * kPathsLdsStack * bs + 128 * paths_lds_nodes(bs, wl, ring, pretrace) +
+         (ring ? 4 * ring_words(pretrace) * bs : 4);
+}
+constexpr bool paths_lds_fits(int bs, bool wl, bool ring, bool pretrace) {
+  return paths_lds_nodes(bs, wl, ring, pretrace) >= 1 && paths_lds_bytes(bs, wl, ring, pretrace) <= (bs == 1024 ? kLdsPerCu : kLdsPerCu / 4);
+}
+#if SRR_KSTACK == 8 && SRR_LDS_NODES == 96
+static_assert(paths_lds_nodes_big(false) == 344 && paths_lds_nodes_big(true) == 248, "1,024-lane node sets");
+#endif
+// every dispatched shape: 1,024 lanes (world in LDS, ring) with and without the hit; 256 lanes with
+// the world in LDS or global memory, ring (with and without the hit) or quad-cooperative
+static_assert(paths_lds_fits(1024, true, true, false) && paths_lds_fits(1024, true, true, true), "1,024-lane blocks: 160 KB");
+static_assert(paths_lds_fits(256, true, true, false) && paths_lds_fits(256, true, true, true) &&
+              paths_lds_fits(256, true, false, false), "256-lane blocks, world in LDS: 40 KB");
+static_assert(paths_lds_fits(256, false, true, false) && paths_lds_fits(256, false, true, true) &&
+              paths_lds_fits(256, false, false, false), "256-lane blocks, world in global memory: 40 KB");
 void dump_trace_timing();
 int paths_lanes_per_device(const SceneView& S, int device);  // persistent grid capacity
 int paths_block_lanes(const SceneView& S);  // k_paths lanes per block for this scene (256 or 1,024)

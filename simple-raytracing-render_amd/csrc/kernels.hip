@@ -2985,24 +2985,7 @@ constexpr unsigned long long kPoolChunk = 64;  // path indices a wave takes per 
 #ifndef SRR_DIAG_VARIANTS
 #define SRR_DIAG_VARIANTS 0
 #endif
-constexpr int kRingWords = 11;  // o.xyz, d.xyz, time, lcg (2 words), pcg (2 words)
-
-// BS: lanes per block.  256 (4 blocks per CU) or 1,024 (one block per CU, the same
-// 4 waves per SIMD): one LDS allocation per CU, whose 160 KB then cache
-// kPathsLdsNodesBig BVH4 nodes (the top ~5 levels) instead of 96.
-// 8 KB world + 8 B x kStack x 1,024 lanes of stacks + the camera-ray rings (44 B
-// per lane) + the node cache <= 160 KB (344 nodes at kStack 8)
-constexpr int kPathsLdsNodesBig =
-    (160 * 1024 - 8192 - 8 * kPathsLdsStack * 1024 - 1024 - 4 * kRingWords * 1024) / 128;
-// 256-lane blocks (4 per CU, <= 40 KB each) of the LDS-world variant: the ring
-// displaces the node cache.  These blocks serve mesh-free scenes by default
-// (paths_block_lanes); mesh scenes reach them only with SRR_BIGBLOCK=0 (an A/B
-// knob).  The two other 256-lane variants that serve mesh scenes keep the whole
-// cache: the global-world one (world tables beyond kWorldLdsBytes) has the 8 KB
-// of the LDS world to spare (16 KB stacks + 11 KB ring + 12 KB nodes), and the
-// quad-cooperative one (SRR_QUAD) runs without the ring.
-constexpr int kPathsLdsNodesSmall = 8;
-
+// (the ring entry's words and the LDS budgets of the block shapes: kernels.h)
 // The camera ray of path index idx of the window (pixel-major: idx = lp * spp_w + s)
 // with its RNG streams, as k_paths' refill needs it.
 SRR_D void path_camera_ray(const SceneView& S, const PathWork& W, uint32_t idx, Ray& r, Rng& rng) {
@@ -3037,6 +3020,18 @@ SRR_D void ring_get(lds_ptr<const float> e, Ray& r, Rng& rng) {
   r = Ray{v3(e[0], e[BS], e[2 * BS]), v3(e[3 * BS], e[4 * BS], e[5 * BS]), e[6 * BS]};
   rng.lcg = (uint64_t)__float_as_uint(e[7 * BS]) | ((uint64_t)__float_as_uint(e[8 * BS]) << 32);
   rng.pcg = (uint64_t)__float_as_uint(e[9 * BS]) | ((uint64_t)__float_as_uint(e[10 * BS]) << 32);
+}
+
+// the entry's pre-traced world hit (obj kNoHit: not traced, the taking lane traces it)
+template <int BS>
+SRR_D void ring_put_hit(lds_ptr<float> e, int obj, int prim, float t) {
+  e[kRingHitWord * BS] = __int_as_float(obj);
+  e[(kRingHitWord + 1) * BS] = __int_as_float(prim);
+  e[(kRingHitWord + 2) * BS] = t;
+}
+template <int BS>
+SRR_D void ring_get_ray(lds_ptr<const float> e, Ray& r) {
+  r = Ray{v3(e[0], e[BS], e[2 * BS]), v3(e[3 * BS], e[4 * BS], e[5 * BS]), e[6 * BS]};
 }
 
 // k_paths' arguments, read through the kernel-argument segment pointer laundered
@@ -3083,6 +3078,9 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
   // lanes in a path; the longest walk's node steps, all lanes' steps, walking lanes (wave time
   // in the mesh is tp[2])
   uint64_t tf[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // TIMED -> W.counters[37..38]: world + mesh ticks of, and the count of, the wave-iterations
+  // whose tracing lanes all hold a camera ray (depth 0); the other iterations are the rest
+  uint64_t tz[2] = {0, 0};
   uint64_t it = 0;
   // WL: world tables staged in LDS (they fit in kWorldLdsBytes); otherwise read
   // from global memory (large object lists, e.g. random_scene's ~490 spheres)
@@ -3114,11 +3112,27 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
   __shared__ int s_node[kStack * BS];
   __shared__ float s_t[kStack * BS];
   constexpr bool RING = !QUAD;
-  constexpr int kNodesLds = BS == 1024 ? kPathsLdsNodesBig : ((WL && RING) ? kPathsLdsNodesSmall : kPathsLdsNodes);
+  // PT: the ring's chunk is traced where it is generated, one full-wave pass over its 64
+  // camera rays (samples of one pixel: the same objects, nodes and leaves), and a
+  // refilling lane takes its path over with the hit.  Not with media, whose boundary
+  // draws come from the path's RNG stream inside the world hit; only in the
+  // diffuse-only variants: with every material family inlined the hit a lane keeps
+  // across a trace pass (3 VGPRs) spills to scratch; and only in the blocks that
+  // serve mesh scenes (1,024 lanes; the diagnostics form): a mesh-free world list
+  // costs the same coherent or not, and C1 lost 0.2-0.5 % to the extra passes.
+  constexpr bool PT = RING && !MEDIA && !ALLFAM && (BS == 1024 || TIMED);
+  constexpr int kRingWords = ring_words(PT);
+  constexpr int kNodesLds = paths_lds_nodes(BS, WL, RING, PT);
+  static_assert(paths_lds_fits(BS, WL, RING, PT), "k_paths LDS");
   __shared__ float4 s_n4[kNodesLds * 8];
   // RING: the wave's camera-ray ring, SoA [kRingWords][BS]; the wave's 64 entries
   // are its own lanes' columns (entry e of wave v at column 64 v + e)
   __shared__ float s_ring[RING ? kRingWords * BS : 1];
+  static_assert(sizeof(s_world) + sizeof(s_node) + sizeof(s_t) + sizeof(s_n4) + sizeof(s_ring) ==
+                    (size_t)paths_lds_bytes(BS, WL, RING, PT), "k_paths LDS as kernels.h counts it");
+  // the LDS node set: the leading nodes of the scene's, up to the variant's room
+  // (CQ: the same LDS bytes hold twice as many 64-B nodes)
+  const auto lds_nodes = [](const SceneView& S) { return min(S.node4_total, (CQ ? 2 : 1) * kNodesLds); };
   const lds_ptr<float> ringw = to_lds(s_ring + (RING ? (threadIdx.x & ~63u) : 0));
   uint32_t ring_base = 0;  // path index of the ring's entry 0 (wave-uniform)
   const uint32_t n_paths = (uint32_t)paths_args()->W.n_paths;
@@ -3127,8 +3141,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
     const SceneView S0 = paths_args()->S;
     if constexpr (WL)
       for (int i = threadIdx.x; i < S0.world_words; i += blockDim.x) s_world[i] = S0.world_blob[i];
-    // (CQ: the same LDS bytes hold twice as many 64-B nodes)
-    const int n_lds_nodes = CQ ? min(S0.node4_total, 2 * kNodesLds) : min(S0.node4_total, kNodesLds);
+    const int n_lds_nodes = lds_nodes(S0);
     if (CQ)
       for (int i = threadIdx.x; i < n_lds_nodes * 4; i += blockDim.x) s_n4[i] = S0.node4q[i];
     else
@@ -3165,9 +3178,27 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
   uint32_t n_events = 0;
   constexpr uint32_t kCapped = 1, kSuspended = 1u << 12;
   uint32_t n_iter = 0, max_rounds = 0;  // wave-iterations, most mixture rounds (SRR_WAVE_TIMES diagnostics)
+  // Without PT an iteration is refill, trace, shade, and every lane in a path does each.
+  // PT: a lane is idle (g < 0), holds a ray to trace (w.obj == kNoHit) or holds a hit to
+  // shade, and an iteration is one trace pass -- the lanes' own rays, or (fill) the ring's new
+  // chunk, whose hits go into the ring while the lanes' own state waits in registers --
+  // and then at most two rounds of refill + shade: lanes whose path ended take the
+  // ring's next paths with their hits, every lane with a hit shades it (record,
+  // scatter, mixture, fold), and the lanes that ended in the first round refill once
+  // more.  A round that finds the ring short hands out what is left, generates the next
+  // chunk and ends the iteration: the next trace pass is that chunk's, and the lanes
+  // that took a hit keep it across the pass (so the round after it shades a full wave).
+  // One world_hit and one shade sequence are inlined either way.
+  constexpr int kNoHit = -2;
+  WorldHit w{kNoHit, -1, 0};
+  bool fill = false;  // (PT, wave-uniform) the coming trace pass is the ring's chunk
+  // TIMED (PT) -> W.counters[39..41]: ticks and passes of the pre-trace, shade rounds
+  uint64_t tpt[3] = {0, 0, 0};
   for (;;) {
     ++n_iter;
     uint64_t tq = TIMED ? __builtin_amdgcn_s_memtime() : 0;
+    if constexpr (!PT) {
+    w = WorldHit{-1, -1, 0};  // (nothing is kept from the last iteration)
     // refill lanes whose path ended, from the wave's pool of path indices; the
     // pool is re-armed one chunk ahead (an atomic whose result is first read an
     // iteration later, so its latency hides behind that iteration's work)
@@ -3263,25 +3294,29 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
       tq = t;
       ++it;
     }
-    bool done = false;
-    V3 C = v3(0.f);
-    // a diffuse bounce with lights: set up here, its mixture loop runs below with
-    // the whole wave (coop_mixture), then its record is written
-    bool diff = false, pend = false;
-    int natt = 0;  // (TIMED: mixture attempts of this lane's Beckmann scatter)
-    uint64_t fam_dt[3] = {0, 0, 0};  // (TIMED: this lane's ticks in the BECK / SPEC / DIFF-set-up branch)
-    DiffSetup ds{};
-    V3 d_atten = v3(0.f), d_n = v3(0.f), d_dir = v3(0.f);
-    float d_pdf = 0;
-    int d_tries = 0;
-    bool d_dead = false;
-    WorldHit w{-1, -1, 0};
-    if (g >= 0) {
+    }  // (!PT)
+    // trace: the lanes that hold a ray, or every lane its entry of the ring's new chunk
+    const bool fill_now = PT && fill;
+    bool act = g >= 0 && (!PT || w.obj == kNoHit);
+    Ray tr = r;
+    if constexpr (PT) {
+      if (fill_now) {
+        // (a lane whose own walk is suspended keeps its traversal stack: its entry stays
+        // untraced, kNoHit, and the lane that takes it traces it as its own ray)
+        act = ring_base + (uint32_t)lane_id() < n_paths && !walking;
+        if (act) ring_get_ray<BS>(ringw + lane_id(), tr);
+      }
+      if (TIMED) {
+        tf[9] += __popcll(__ballot(g >= 0));
+        ++it;
+      }
+    }
+    if (act) {
       const SceneView S = view();
       const PathWork W = work();
       TraceCtx cx{nullptr, to_lds(s_node + threadIdx.x), to_lds(s_t + threadIdx.x)};
       cx.lds_nodes = (const __attribute__((address_space(3))) f32x4*)to_lds(s_n4);
-      cx.lds_count = CQ ? min(S.node4_total, 2 * kNodesLds) : min(S.node4_total, kNodesLds);
+      cx.lds_count = lds_nodes(S);
       // (clamped: a host compiled with another SRR_KSTACK must not index past the
       // kernel's kStack LDS entries per lane)
       cx.st_cap = min(W.stack_cap, kStack);
@@ -3294,21 +3329,28 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
         // suspend walks once at most walk_q / 64 of the wave's lanes in a path still walk
         // (the save area follows the global stack extension: none without it)
         // (walk_q 0: threshold 0, and a walk only stops when its lanes all finished)
-        cx.walk_thr = vreg((int)((__popcll(__ballot(true)) * (uint32_t)paths_args()->W.walk_q) >> 6));
-        cx.resume = walking;
+        // (the ring's chunk never suspends: threshold 0, nothing to resume)
+        cx.walk_thr = vreg(fill_now ? 0 : (int)((__popcll(__ballot(true)) * (uint32_t)paths_args()->W.walk_q) >> 6));
+        cx.resume = fill_now ? vreg(0) : walking;
         cx.susp = vreg(0);
       }
 #ifdef SRR_SLOW_RAYS
       const uint64_t t_w0 = __builtin_amdgcn_s_memrealtime();
       cx.last_steps = 0;
-      const Ray r_in = r;
+      const Ray r_in = tr;
 #endif
-      w = world_hit<MEDIA, TIMED ? (TR_BVH4_TIMED | (WL ? TR_WL : 0) | (SP ? TR_SUSP : 0)) : TR>(S, r, rng, cx);
-      if constexpr ((TR & TR_SUSP) != 0) {
-        walking = cx.susp;  // (its record, scatter and fold wait for the walk's end)
-        if (walking) {
-          w.obj = -1;
-          n_events += kSuspended;
+      const WorldHit wh =
+          world_hit<MEDIA, TIMED ? (TR_BVH4_TIMED | (WL ? TR_WL : 0) | (SP ? TR_SUSP : 0)) : TR>(S, tr, rng, cx);
+      if (fill_now) {
+        ring_put_hit<BS>(ringw + lane_id(), wh.obj, wh.prim, wh.t);
+      } else {
+        w = wh;
+        if constexpr ((TR & TR_SUSP) != 0) {
+          walking = cx.susp;  // (its record, scatter and fold wait for the walk's end)
+          if (walking) {
+            w.obj = PT ? kNoHit : -1;  // (PT: still a ray to trace)
+            n_events += kSuspended;
+          }
         }
       }
 #ifdef SRR_SLOW_RAYS
@@ -3326,9 +3368,9 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
           e[8] = r_in.tm;
           e[9] = __int_as_float((int)t_w);
           e[10] = __int_as_float(cx.last_steps);
-          e[11] = __int_as_float(w.obj);
-          e[12] = __int_as_float(w.prim);
-          e[13] = w.t;
+          e[11] = __int_as_float(wh.obj);
+          e[12] = __int_as_float(wh.prim);
+          e[13] = wh.t;
           e[14] = __int_as_float(slot);
           e[15] = __int_as_float((int)(t_w0 & 0x7fffffff));
         }
@@ -3336,25 +3378,123 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
 #endif
       if (TIMED) {
         const uint64_t t = __builtin_amdgcn_s_memtime();
-        tp[1] += t - tq - cx.mesh_cycles;
-        tp[2] += cx.mesh_cycles;
-        tf[10] += cx.mesh_steps;
-        tf[11] += cx.mesh_lane_steps;
-        tf[12] += cx.mesh_walkers;
-        tf[13] += cx.leaf_cycles;
-        tf[14] += cx.leaf_passes;
-        tf[15] += cx.step_parts[0];
-        tf[16] += cx.step_parts[1];
-        tf[17] += cx.step_parts[2];
+        if (fill_now) {  // the pre-trace pass is a phase of its own
+          tpt[0] += t - tq;
+          ++tpt[1];
+        } else {
+          if (__ballot(depth != 0) == 0) {
+            tz[0] += t - tq;
+            ++tz[1];
+          }
+          tp[1] += t - tq - cx.mesh_cycles;
+          tp[2] += cx.mesh_cycles;
+          tf[10] += cx.mesh_steps;
+          tf[11] += cx.mesh_lane_steps;
+          tf[12] += cx.mesh_walkers;
+          tf[13] += cx.leaf_cycles;
+          tf[14] += cx.leaf_passes;
+          tf[15] += cx.step_parts[0];
+          tf[16] += cx.step_parts[1];
+          tf[17] += cx.step_parts[2];
+        }
         tq = t;
       }
-      done = !walking;
+    }
+    if constexpr (PT) {
+      if (fill_now) {
+        // (one wave writes and reads these entries: its LDS operations run in order;
+        // the fence keeps the compiler from moving the refill's reads above the writes)
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        fill = false;
+      }
     }
     if (nxt_armed && !nxt_ready) {  // (uniform: every lane of the wave is here)
       nxt_base = __builtin_amdgcn_readfirstlane(nxt_lane0);
       nxt_ready = true;
     }
-    if (g >= 0) {
+#pragma nounroll
+    for (int round = 0; round < (PT ? 2 : 1); ++round) {
+    if constexpr (PT) {
+      // refill: lanes whose path ended take the ring's next paths, hits included
+      if (TIMED) tq = __builtin_amdgcn_s_memtime();
+      const bool need = g < 0;
+      const uint64_t nm = __ballot(need);
+      if (nm && pool < n_paths) {
+        const uint32_t cnt = __popcll(nm);
+        const uint32_t rank = __popcll(nm & ((1ull << lane_id()) - 1));
+        const uint32_t avail = pool_end - pool;
+        if (need && rank < avail) {
+          const uint32_t i0 = pool + rank;
+          if (i0 < n_paths) {
+            const lds_ptr<const float> e = ringw + (i0 - ring_base);
+            g = (int)i0;
+            ring_get<BS>(e, r, rng);
+            w = WorldHit{__float_as_int(e[kRingHitWord * BS]), __float_as_int(e[(kRingHitWord + 1) * BS]),
+                         e[(kRingHitWord + 2) * BS]};
+            depth = 0;
+          }
+        }
+        if (avail >= cnt) {
+          pool += cnt;
+        } else {
+          // the ring is short: the next chunk's camera rays, one per lane, every lane of
+          // the wave; the coming trace pass is theirs
+          const SceneView S = view();
+          const PathWork W = work();
+          uint32_t nb;
+          if (nxt_armed) {
+            nb = nxt_ready ? nxt_base : __builtin_amdgcn_readfirstlane(nxt_lane0);
+            nxt_armed = false;
+            nxt_ready = false;
+          } else {
+            uint32_t b = 0;
+            if (lane_id() == 0) b = (uint32_t)atomicAdd(W.cursor, (unsigned long long)kPoolChunk);
+            nb = __builtin_amdgcn_readfirstlane(b);
+          }
+          // (the fence keeps the compiler from moving the writes above the reads of the old chunk)
+          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+          const uint32_t gi = nb + (uint32_t)lane_id();
+          if (gi < n_paths) {
+            Ray gr;
+            Rng grng;
+            path_camera_ray(S, W, gi, gr, grng);
+            ring_put<BS>(ringw + lane_id(), gr, grng);
+            ring_put_hit<BS>(ringw + lane_id(), kNoHit, -1, 0.f);
+          }
+          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+          ring_base = nb;
+          pool = nb;
+          pool_end = nb + (uint32_t)kPoolChunk;
+          fill = nb < n_paths;
+        }
+      }
+      if (TIMED) {
+        __builtin_amdgcn_s_waitcnt(0);
+        const uint64_t t = __builtin_amdgcn_s_memtime();
+        tp[0] += t - tq;
+        tq = t;
+      }
+      if (fill) break;  // (wave-uniform) trace the chunk first
+    }
+    // shade: the lanes that hold a hit (a miss among them: w.obj -1)
+    const bool sh = g >= 0 && (!PT || w.obj != kNoHit);
+    if constexpr (PT) {
+      if (__ballot(sh) == 0) break;
+      if (TIMED) ++tpt[2];
+    }
+    bool done = sh && (PT || !walking);  // (a suspended walk's record, scatter and fold wait for its end)
+    V3 C = v3(0.f);
+    // a diffuse bounce with lights: set up here, its mixture loop runs below with
+    // the whole wave (coop_mixture), then its record is written
+    bool diff = false, pend = false;
+    int natt = 0;  // (TIMED: mixture attempts of this lane's Beckmann scatter)
+    uint64_t fam_dt[3] = {0, 0, 0};  // (TIMED: this lane's ticks in the BECK / SPEC / DIFF-set-up branch)
+    DiffSetup ds{};
+    V3 d_atten = v3(0.f), d_n = v3(0.f), d_dir = v3(0.f);
+    float d_pdf = 0;
+    int d_tries = 0;
+    bool d_dead = false;
+    if (sh) {
       if (w.obj >= 0) {
         const SceneView S = view();
         const PathWork W = work();
@@ -3457,8 +3597,9 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
       r = Ray{ds.p, d_dir, r.tm};
       ++depth;
     }
-    if (g >= 0) {
+    if (sh) {
       const PathWork W = work();
+      if (PT) w.obj = kNoHit;  // shaded: a ray to trace, or (below) the path's end
       if (TIMED) {
         const uint64_t t = __builtin_amdgcn_s_memtime();
         tp[3] += t - tq;
@@ -3504,6 +3645,15 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
       }
       if (TIMED) tp[4] += __builtin_amdgcn_s_memtime() - tq;
     }
+    }  // (round)
+    if constexpr (PT) {
+      if (!nxt_armed && pool_end < n_paths) {  // arm the next chunk
+        if (lane_id() == 0) nxt_lane0 = (uint32_t)atomicAdd(paths_args()->W.cursor, (unsigned long long)kPoolChunk);
+        nxt_armed = true;
+      }
+      // (no lane in a path, no chunk waiting for its trace pass, no path left to hand out)
+      if (!fill && pool >= n_paths && __ballot(g >= 0) == 0) break;
+    }
   }
   const PathWork W = work();
   if (TIMED && lane_id() == 0) {  // per-wave totals -> W.counters[4..9]
@@ -3513,6 +3663,8 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
     atomicAdd(W.counters + 13, (unsigned long long)tp[6]);
     atomicAdd(W.counters + 14, (unsigned long long)tp[7]);
     for (int q = 0; q < 20; ++q) atomicAdd(W.counters + 16 + q, (unsigned long long)tf[q]);
+    for (int q = 0; q < 2; ++q) atomicAdd(W.counters + 37 + q, (unsigned long long)tz[q]);
+    for (int q = 0; q < 3; ++q) atomicAdd(W.counters + 39 + q, (unsigned long long)tpt[q]);
   }
 
   unsigned long long tot = nrays;
@@ -4481,6 +4633,7 @@ struct PathsVariant {
   bool timing;         // SRR_PATHS_TIMING is set (phase timing: the diagnostics build has it)
   bool cq;             // compressed nodes, per-lane walks (SRR_CBVH; diagnostics build)
   int bs;              // lanes per block
+  int lds_nodes_cap;   // SRR_LDS_NODES_CAP: at most this many BVH4 nodes in LDS (0: the variant's room)
 };
 static PathsVariant paths_variant(const SceneView& S, int all_families, int walk_q) {
   static const bool big = [] {
@@ -4489,6 +4642,9 @@ static PathsVariant paths_variant(const SceneView& S, int all_families, int walk
   }();
   static const bool timing = getenv("SRR_PATHS_TIMING") != nullptr;
   static const bool force_global = getenv("SRR_WORLD_GLOBAL") != nullptr;  // A/B diagnostics
+  // (tests render the same frame with 1 node and with the whole set: read per launch)
+  const char* nc_env = getenv("SRR_LDS_NODES_CAP");
+  const int nodes_cap = nc_env ? std::max(0, atoi(nc_env)) : 0;
   PathsVariant v;
   v.media = S.has_media != 0;
   v.allfam = all_families != 0;
@@ -4496,6 +4652,7 @@ static PathsVariant paths_variant(const SceneView& S, int all_families, int walk
   v.quad = S.quad_trace != 0;
   v.sp = walk_q > 0;
   v.timing = timing;
+  v.lds_nodes_cap = nodes_cap;
   const bool timed = SRR_DIAG_VARIANTS && timing;
   v.cq = SRR_DIAG_VARIANTS && S.use_q && !S.quad_trace && !timed;
   // 1,024 lanes (SRR_BIGBLOCK, the default) when the launch takes the per-lane,
@@ -4580,8 +4737,10 @@ int launch_paths(const SceneView& S, const PathWork& W, int all_families, hipStr
   // the kernels index kStack LDS entries per lane: a host built with a larger
   // SRR_KSTACK is refused here (round 4 ran such a mix once: an illegal address)
   if (W.stack_cap < 1 || W.stack_cap > dev::kStack) return -1;
-  const dev::PathsArgs args{S, W};
+  dev::PathsArgs args{S, W};
   const PathsVariant v = paths_variant(S, all_families, W.walk_q);
+  // (the kernels read node4_total only to size their LDS node set, a prefix of the nodes)
+  if (v.lds_nodes_cap > 0) args.S.node4_total = std::min(args.S.node4_total, v.lds_nodes_cap);
   if (!SRR_DIAG_VARIANTS && v.wl && (S.use_q || v.timing))
     fprintf(stderr, "srr: SRR_CBVH / SRR_PATHS_TIMING need the diagnostics build (make diag); ignored\n");
   if (!v.wl) {

@@ -13,7 +13,7 @@
 
 namespace srr {
 
-constexpr int kCtrWords = 40;  // FrameSlot::ctr: world rays, cursor, error, overflow and diagnostics counters
+constexpr int kCtrWords = 48;  // FrameSlot::ctr: world rays, cursor, error, overflow and diagnostics counters
 constexpr int kVisitWords = 3 + 2 * 64;  // SRR_FLAG_COUNT_VISITS: sums + two histograms
 
 #define RCHK(x)                                                        \
@@ -662,6 +662,14 @@ static int paths_finish(srr_renderer* r, FrameSlot& F, const srr_params* p, srr_
     fprintf(stderr, "  beckmann mixture: %.2f attempts per Beckmann scatter, %.2f for the wave's slowest lane per run\n",
             per(ctr[34], ctr[22]), per(ctr[35], ctr[19]));
     fprintf(stderr, "  suspended walks: %.2f lanes per wave-iteration\n", ctr[36] / it);
+    fprintf(stderr, "  camera-ray-only iterations (every tracing lane at depth 0): %llu of %llu, world + mesh %.0f ticks "
+                    "per wave-iteration of them; the others %.0f\n",
+            ctr[38], ctr[9], per(ctr[37], ctr[38]), per(ctr[5] + ctr[6] - ctr[37], ctr[9] - ctr[38]));
+    // (the wave-iterations above count every trace pass; the pre-trace passes are among them,
+    // their ticks in no other phase)
+    fprintf(stderr, "  pre-trace: %llu passes of the %llu wave-iterations, %.0f ticks each (%.0f per wave-iteration); "
+                    "shade rounds %.2f per wave-iteration\n",
+            ctr[40], ctr[9], per(ctr[39], ctr[40]), ctr[39] / it, ctr[41] / it);
   }
 #ifdef SRR_SLOW_RAYS
   if (r->pw_slow) {  // diagnostics build: dump the slow world hits' records (one line per lane, JSON)
