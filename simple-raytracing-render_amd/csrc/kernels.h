@@ -112,7 +112,7 @@ struct PathWork {
   int64_t n_paths;        // npix * spp_w
   int max_depth;
   unsigned long long* cursor;  // next path to start (device, zeroed per window)
-  unsigned long long* counters;  // [0] += world rays traced
+  unsigned long long* counters;  // kPathsCtrWords words, named by PathsCtr (below)
   float* sample;          // [n_paths][3] de_nan'd radiance, index g
   float* raw;             // optional kept paths [npix][keep_spp][3] before de_nan
   uint8_t* rays;          // optional kept [npix][keep_spp] world rays per path
@@ -133,6 +133,64 @@ struct PathWork {
   // that follows gstack's gstack_cap x lanes entries (so walks suspend only with gstack)
   int walk_q;
 };
+
+// The words of PathWork::counters (renderer.cpp FrameSlot::ctr), zeroed per frame.  k_paths
+// adds to them, paths_finish reads the first group into srr_stats and prints the rest as
+// the SRR_PATHS_TIMING report.  Words from kCtrTicksRefill on, the four event counts among
+// them aside, are written only by the diagnostics (TIMED) variants, per wave, in ticks of
+// s_memtime; "its" are wave-iterations.
+enum PathsCtr : int {
+  kCtrWorldRays = 0,        // world rays traced (srr_stats::world_rays)
+  kCtrCursor = 1,           // PathWork::cursor: next path to start (zeroed per window)
+  kCtrError = 2,            // PathWork::err: guard bits of an out-of-range index
+  // per-wave ticks in the phases of the path loop
+  kCtrTicksRefill = 4,
+  kCtrTicksWorld,           // world hit without its mesh part
+  kCtrTicksMesh,            // ... and the mesh part (TraceCtx::mesh_cycles)
+  kCtrTicksShade,           // record + scatter (the report subtracts the record's)
+  kCtrTicksFold,
+  kCtrWaveIters = 9,        // wave-iterations (every trace pass, the pre-trace's among them)
+  kCtrTicksRecord = 10,     // world_record
+  kCtrStackOverflows = 11,  // traversals that overflowed into the exact re-walk (TraceCtx::ovf)
+  kCtrDeepTraversals = 12,  // traversals that used the stack's global extension
+  kCtrTicksMixture = 13,    // the wave-cooperative mixture loop
+  kCtrMixtureRounds = 14,
+  kCtrMixtureCapped = 15,   // resampling loops stopped by kMixtureGuard
+  // the per-lane scatter's BECK / SPEC / DIFF-set-up branches: wave ticks in each,
+  // iterations each ran in, lanes it ran for
+  kCtrTicksBeck = 16, kCtrTicksSpec, kCtrTicksDiffSetup,
+  kCtrItsBeck, kCtrItsSpec, kCtrItsDiff,
+  kCtrLanesBeck, kCtrLanesSpec, kCtrLanesDiff,
+  kCtrLanesInPath,          // lanes in a path, summed over the wave-iterations
+  // mesh walks (wave time in the mesh is kCtrTicksMesh): the longest walk's node steps,
+  // all lanes' steps, walking lanes; the leaf-triangle queue's ticks and passes; the
+  // parts of a node step: node fetch, slab + queue set-up, order + push + pop
+  kCtrMeshSteps, kCtrMeshLaneSteps, kCtrMeshWalkers,
+  kCtrLeafTicks, kCtrLeafPasses,
+  kCtrStepFetch, kCtrStepSlab, kCtrStepOrder,
+  kCtrBeckAttempts,         // mixture attempts of the Beckmann scatters: the wave's sum
+  kCtrBeckAttemptsMax,      // ... and its slowest lane's
+  kCtrSuspended = 36,       // suspended mesh walks (srr_stats::walks_suspended)
+  // world + mesh ticks of, and the count of, the wave-iterations whose tracing lanes all
+  // hold a camera ray (depth 0); the other iterations are the rest
+  kCtrTicksCamOnly = 37, kCtrItsCamOnly,
+  // the pre-trace: ticks and passes of the chunk's trace, shade rounds
+  kCtrTicksPretrace = 39, kCtrPretracePasses, kCtrShadeRounds,
+  kPathsCtrCount
+};
+constexpr int kPathsCtrWords = 48;  // words allocated (FrameSlot::ctr)
+static_assert(kPathsCtrCount == 42 && kPathsCtrCount <= kPathsCtrWords, "PathsCtr fits FrameSlot::ctr");
+// the groups that code walks by offset: the phases, the three family branches in BECK, SPEC,
+// DIFF order (ticks, its, lanes), the step parts (TraceCtx::step_parts), the deep word behind
+// the overflow word (TraceCtx::ovf)
+static_assert(kCtrTicksFold == kCtrTicksRefill + 4 && kCtrTicksFold < kCtrWaveIters, "phase ticks");
+static_assert(kCtrTicksDiffSetup == kCtrTicksBeck + 2 && kCtrItsBeck == kCtrTicksBeck + 3 && kCtrItsDiff == kCtrItsBeck + 2 &&
+                  kCtrLanesBeck == kCtrItsBeck + 3 && kCtrLanesDiff == kCtrLanesBeck + 2 && kCtrLanesInPath == 25,
+              "family words");
+static_assert(kCtrMeshSteps == 26 && kCtrStepOrder == kCtrStepFetch + 2 && kCtrBeckAttemptsMax == 35 &&
+                  kCtrBeckAttemptsMax < kCtrSuspended, "mesh words");
+static_assert(kCtrDeepTraversals == kCtrStackOverflows + 1, "TraceCtx::ovf counts overflows, ovf[1] deep traversals");
+static_assert(kCtrItsCamOnly == 38 && kCtrShadeRounds == 41, "camera-only and pre-trace words");
 #ifndef SRR_KSTACK
 #define SRR_KSTACK 8
 #endif

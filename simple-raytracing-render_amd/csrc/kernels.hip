@@ -269,7 +269,9 @@ struct TraceCtx {
   const __attribute__((address_space(3))) f32x4* lds_nodes = nullptr;  // LDS copy of node4[0, lds_count) (k_paths)
   int lds_count = 0;
   int st_cap = kStack;                   // stack entries used (<= kStack; SRR_STACK_CAP tests the re-walk)
-  unsigned long long* ovf = nullptr;     // optional: += 1 per traversal that overflowed into the re-walk
+  // optional (k_paths: its kCtrStackOverflows word): += 1 per traversal that overflowed into the
+  // re-walk; the word kCtrDeepTraversals - kCtrStackOverflows behind it counts the deep ones
+  unsigned long long* ovf = nullptr;
   // optional global extension of the stack (k_paths): entries kStack.. of lane
   // `slot` at gst[(sp - st_cap) * gst_stride + slot] = (node, entry t bits), up to
   // gst_cap of them; only a traversal deeper than that re-walks the BVH2
@@ -803,7 +805,7 @@ SRR_D bool mesh_hit4(const SceneView& S, const DMesh& m, const Ray& r, float tmi
   }
   if (cx.ovf && cx.gst) {  // traversals that used the global stack (one atomic per wave; a suspended walk counts when it ends)
     const uint64_t dm = __ballot(deep && !suspended);
-    if (dm && (int)__lane_id() == __ffsll((unsigned long long)dm) - 1) atomicAdd(cx.ovf + 1, (unsigned long long)__popcll(dm));
+    if (dm && (int)__lane_id() == __ffsll((unsigned long long)dm) - 1) atomicAdd(cx.ovf + (kCtrDeepTraversals - kCtrStackOverflows), (unsigned long long)__popcll(dm));
   }
 #ifdef SRR_SLOW_RAYS
   cx.last_steps += (int)(nbox / 4) | (overflow ? 1 << 30 : 0) | (deep ? 1 << 29 : 0);
@@ -1045,7 +1047,7 @@ SRR_D bool mesh_hit4_quad(const SceneView& S, const DMesh& m, const Ray& r, floa
       t_me = t_r;
       i_me = i_r;
       redo_me = o_r;
-      if (cx.ovf && d_r) atomicAdd(cx.ovf + 1, 1ull);
+      if (cx.ovf && d_r) atomicAdd(cx.ovf + (kCtrDeepTraversals - kCtrStackOverflows), 1ull);
     }
   }
   if (redo_me) {  // rare: exact re-walk
@@ -2969,18 +2971,20 @@ SRR_D float4 rec_load(const float4* p) { return *p; }  // (by value: the fold is
 constexpr int kPathsBlock = 256;
 constexpr unsigned long long kPoolChunk = 64;  // path indices a wave takes per cursor atomic
 
-// Camera-ray ring.  A lane whose path ended used to
-// generate its next camera ray itself (pixel and sample from the path index,
-// per-path seeds, Sobol point, lens disk, normalisation: a few hundred VALU
-// instructions) while the wave's other lanes, still inside their paths, idled:
-// about half the lanes refill per wave-iteration (C2 paths average 2.03 world
-// rays), so the refill ran at ~50 % lane utilisation every iteration.  With the
-// ring, the wave generates the camera rays of a whole 64-path chunk at once --
-// lane k the ray of path chunk + k, every lane busy -- into its 64 LDS entries,
-// and refilling lanes just read theirs: the chunk's rays cost one full-wave
-// generation per ~2 iterations instead of a half-empty one per iteration.  Every
-// path's ray is the same function of its index, so paths are unchanged.  (The
-// quad-cooperative variant runs without the ring.)
+// Camera-ray ring.  A wave takes path indices from the cursor a 64-path chunk at a
+// time (k_paths' pool) and generates the chunk's camera rays at once -- lane k the ray of
+// path chunk + k, every lane busy -- into its 64 LDS entries (ring_fill); a lane
+// whose path ended just reads its entry (ring_take).  In the pre-trace variants
+// (k_paths' PT) the wave also traces the chunk where it generated it, one coherent
+// pass, and the entry carries the hit to the lane that takes it.  Generating a camera
+// ray (pixel and sample from the path index, per-path seeds, Sobol point, lens disk,
+// normalisation) is a few hundred VALU instructions, and about half the lanes refill
+// per wave-iteration (C2 paths average 2.03 world rays): a refilling lane that
+// generates its own ray does so at ~50 % lane utilisation every iteration, while
+// the chunk's rays cost one full-wave generation per ~2 iterations.  Every path's
+// ray is the same function of its index, so paths are the same either way.  Only the
+// quad-cooperative variant runs without the ring, each refilling lane generating
+// its own ray.
 // diagnostics-only k_paths variants (phase timing, compressed nodes): `make diag`
 #ifndef SRR_DIAG_VARIANTS
 #define SRR_DIAG_VARIANTS 0
@@ -3016,13 +3020,18 @@ SRR_D void ring_put(lds_ptr<float> e, const Ray& r, const Rng& rng) {  // e: the
 }
 
 template <int BS>
-SRR_D void ring_get(lds_ptr<const float> e, Ray& r, Rng& rng) {
+SRR_D void ring_get_ray(lds_ptr<const float> e, Ray& r) {
   r = Ray{v3(e[0], e[BS], e[2 * BS]), v3(e[3 * BS], e[4 * BS], e[5 * BS]), e[6 * BS]};
+}
+template <int BS>
+SRR_D void ring_get(lds_ptr<const float> e, Ray& r, Rng& rng) {
+  ring_get_ray<BS>(e, r);
   rng.lcg = (uint64_t)__float_as_uint(e[7 * BS]) | ((uint64_t)__float_as_uint(e[8 * BS]) << 32);
   rng.pcg = (uint64_t)__float_as_uint(e[9 * BS]) | ((uint64_t)__float_as_uint(e[10 * BS]) << 32);
 }
 
 // the entry's pre-traced world hit (obj kNoHit: not traced, the taking lane traces it)
+constexpr int kNoHit = -2;
 template <int BS>
 SRR_D void ring_put_hit(lds_ptr<float> e, int obj, int prim, float t) {
   e[kRingHitWord * BS] = __int_as_float(obj);
@@ -3030,8 +3039,34 @@ SRR_D void ring_put_hit(lds_ptr<float> e, int obj, int prim, float t) {
   e[(kRingHitWord + 2) * BS] = t;
 }
 template <int BS>
-SRR_D void ring_get_ray(lds_ptr<const float> e, Ray& r) {
-  r = Ray{v3(e[0], e[BS], e[2 * BS]), v3(e[3 * BS], e[4 * BS], e[5 * BS]), e[6 * BS]};
+SRR_D WorldHit ring_get_hit(lds_ptr<const float> e) {
+  return WorldHit{__float_as_int(e[kRingHitWord * BS]), __float_as_int(e[(kRingHitWord + 1) * BS]), e[(kRingHitWord + 2) * BS]};
+}
+
+// The wave fills its ring with chunk nb: lane k the camera ray of path nb + k, every
+// lane of the wave (HIT: the entry's hit starts as not traced).  `ring` is the wave's
+// entry 0.  The caller fences: one wave writes and reads these entries and its LDS
+// operations run in order, so a wavefront fence is enough, but where it must stand
+// depends on what the site read from the old chunk.
+template <int BS, bool HIT>
+SRR_D void ring_fill(lds_ptr<float> ring, const SceneView& S, const PathWork& W, uint32_t nb, uint32_t n_paths) {
+  const uint32_t gi = nb + (uint32_t)lane_id();
+  if (gi < n_paths) {
+    Ray gr;
+    Rng grng;
+    path_camera_ray(S, W, gi, gr, grng);
+    ring_put<BS>(ring + lane_id(), gr, grng);
+    if (HIT) ring_put_hit<BS>(ring + lane_id(), kNoHit, -1, 0.f);
+  }
+}
+
+// A refilling lane takes the ring entry e: the path's camera ray and RNG streams and (HIT)
+// the world hit the wave traced for it.  (The lane's path index and depth stay with the
+// caller: k_paths keeps them, like the pool, in plain locals that nothing points to.)
+template <int BS, bool HIT>
+SRR_D void ring_take(lds_ptr<const float> e, Ray& r, Rng& rng, WorldHit& w) {
+  ring_get<BS>(e, r, rng);
+  if (HIT) w = ring_get_hit<BS>(e);
 }
 
 // k_paths' arguments, read through the kernel-argument segment pointer laundered
@@ -3059,8 +3094,90 @@ SRR_D kptr<PathsArgs> paths_args() {
 SRR_D const PathsArgs* paths_args() { return nullptr; }
 #endif
 
+// k_paths' pool of path indices: the wave hands its refilling lanes the unissued indices
+// [pool, pool_end) of its chunk and takes the next chunk from the window's cursor, one
+// wave-aggregated atomic per chunk, armed one chunk ahead: the atomic is issued when the
+// chunk it follows is opened and its result (nxt_lane0, lane 0's) is first read an
+// iteration later, so its latency hides behind that iteration's work.  The state stays
+// k_paths' own locals and these take and return values only; taking the next chunk's base
+// stays written out at its three sites (profiles/r10/codegen.txt).
+struct PoolRanks {
+  uint32_t cnt;    // refilling lanes of the wave (nm: their ballot)
+  uint32_t rank;   // this lane's place among them
+  uint32_t avail;  // indices left in the chunk: ranks below it are served from it
+};
+SRR_D PoolRanks pool_ranks(uint64_t nm, uint32_t pool, uint32_t pool_end) {
+  return PoolRanks{(uint32_t)__popcll(nm), (uint32_t)__popcll(nm & ((1ull << lane_id()) - 1)), pool_end - pool};
+}
+// arm the next chunk: the new nxt_lane0 (the cursor is read here, behind the caller's test:
+// k_paths' arguments are not kept in registers across its loop, paths_args())
+SRR_D uint32_t pool_arm(uint32_t nxt_lane0) {
+  if (lane_id() == 0) nxt_lane0 = (uint32_t)atomicAdd(paths_args()->W.cursor, (unsigned long long)kPoolChunk);
+  return nxt_lane0;
+}
+
+#ifdef SRR_SLOW_RAYS
+// diagnostics build: every lane of a world hit slower than SRR_SLOW_RAYS ticks (100 MHz;
+// t_w0: its start) or flagged in its step count records its ray in PathWork::slow_rays.
+// The 16 words of a record (renderer.cpp paths_finish prints them):
+//   0 g  1 depth  2-4 o  5-7 d  8 time  9 ticks  10 steps (TraceCtx::last_steps)
+//   11 hit obj  12 hit prim  13 hit t  14 slot  15 start tick (low 31 bits)
+SRR_D void slow_ray_record(const PathWork& W, int g, int depth, const Ray& r_in, uint64_t t_w0, int steps, const WorldHit& wh,
+                           int slot) {
+  const uint64_t t_w = __builtin_amdgcn_s_memrealtime() - t_w0;
+  if ((t_w > (uint64_t)SRR_SLOW_RAYS || (steps & (1 << 28))) && W.slow_rays) {
+    const unsigned q = atomicAdd(W.slow_count, 1u);
+    if (q < 65536u) {
+      float* e = W.slow_rays + 16 * (size_t)q;
+      e[0] = __int_as_float(g);
+      e[1] = __int_as_float(depth);
+      e[2] = r_in.o.x; e[3] = r_in.o.y; e[4] = r_in.o.z;
+      e[5] = r_in.d.x; e[6] = r_in.d.y; e[7] = r_in.d.z;
+      e[8] = r_in.tm;
+      e[9] = __int_as_float((int)t_w);
+      e[10] = __int_as_float(steps);
+      e[11] = __int_as_float(wh.obj);
+      e[12] = __int_as_float(wh.prim);
+      e[13] = wh.t;
+      e[14] = __int_as_float(slot);
+      e[15] = __int_as_float((int)(t_w0 & 0x7fffffff));
+    }
+  }
+}
+#endif
+
 // SP: mesh walks may suspend (TR_SUSP; launched when PathWork::walk_q > 0): the 1,024-lane
 // variants and the diagnostics (TIMED) one are built both ways
+// The TIMED variants' totals (kernels.h PathsCtr) live in four small arrays, as many words as
+// the kernel can afford in scratch: the phases with the record and mixture words (tp), the
+// family and mesh words (tf), the camera-only (tz) and the pre-trace words (tpt).  Slot of
+// word Q in its array; a word that is not the array's does not compile.
+constexpr int kTpWords = 8, kTfWords = kCtrBeckAttemptsMax - kCtrTicksBeck + 1, kTzWords = 2, kTptWords = 3;
+constexpr int kTpPhases = kCtrTicksFold - kCtrTicksRefill + 1;  // tp's leading slots, words kCtrTicksRefill on
+template <int Q>
+constexpr int tp_at() {
+  constexpr int at = Q >= kCtrTicksRefill && Q <= kCtrTicksFold ? Q - kCtrTicksRefill
+                     : Q == kCtrTicksRecord ? kTpPhases : Q == kCtrTicksMixture ? kTpPhases + 1
+                     : Q == kCtrMixtureRounds ? kTpPhases + 2 : -1;
+  static_assert(at >= 0 && at < kTpWords, "not a word of tp");
+  return at;
+}
+template <int Q>
+constexpr int tf_at() {
+  static_assert(Q >= kCtrTicksBeck && Q <= kCtrBeckAttemptsMax, "not a word of tf");
+  return Q - kCtrTicksBeck;
+}
+template <int Q>
+constexpr int tz_at() {
+  static_assert(Q >= kCtrTicksCamOnly && Q < kCtrTicksCamOnly + kTzWords, "not a word of tz");
+  return Q - kCtrTicksCamOnly;
+}
+template <int Q>
+constexpr int tpt_at() {
+  static_assert(Q >= kCtrTicksPretrace && Q < kCtrTicksPretrace + kTptWords, "not a word of tpt");
+  return Q - kCtrTicksPretrace;
+}
+
 template <bool MEDIA, bool ALLFAM, int MINB, bool TIMED = false, bool WL = true, bool QUAD = false, bool CQ = false,
           int BS = kPathsBlock, bool SP = false>
 #ifdef SRR_NUM_VGPR  // register-pressure study builds only: cap k_paths' VGPRs
@@ -3071,17 +3188,13 @@ template <bool MEDIA, bool ALLFAM, int MINB, bool TIMED = false, bool WL = true,
 __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArgs A) {
   static_assert(BS == kPathsBlock || BS == 1024, "block size");
   (void)A;  // read through paths_args()
-  // TIMED (diagnostics): per-wave cycles in refill / world hit (mesh part) / record+scatter / fold
-  uint64_t tp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  // TIMED family diagnostics -> W.counters[16..35]: ticks in the BECK / SPEC / DIFF-set-up
-  // branches of the per-lane scatter, iterations each branch ran, lanes it ran for;
-  // lanes in a path; the longest walk's node steps, all lanes' steps, walking lanes (wave time
-  // in the mesh is tp[2])
-  uint64_t tf[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  // TIMED -> W.counters[37..38]: world + mesh ticks of, and the count of, the wave-iterations
-  // whose tracing lanes all hold a camera ray (depth 0); the other iterations are the rest
-  uint64_t tz[2] = {0, 0};
+  // TIMED (diagnostics): this wave's totals for W.counters, indexed by the word's name
+  // (tp_at ... tpt_at above); `it` is kCtrWaveIters
+  uint64_t tp[kTpWords] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t tf[kTfWords] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t tz[kTzWords] = {0, 0};
   uint64_t it = 0;
+  uint64_t tpt[kTptWords] = {0, 0, 0};
   // WL: world tables staged in LDS (they fit in kWorldLdsBytes); otherwise read
   // from global memory (large object lists, e.g. random_scene's ~490 spheres)
   // QUAD: meshes traced by mesh_hit4_quad (large BVHs, SceneView::quad_trace)
@@ -3158,6 +3271,11 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
   };
   int g = -1;  // path of this lane (a window numbers its paths below 2^31), -1 idle
   // the wave's unissued path indices [pool, pool_end): wave-uniform (scalar)
+  // (The pool's state, like g and depth, is loose locals that no helper takes by
+  // reference or as a struct: the compiler turns such locals into registers before it
+  // inlines anything, and what a helper reaches through a pointer only afterwards, in
+  // another order, which the kernel's register allocation follows: gathered into a
+  // struct with member functions, every variant compiled to other code, profiles/r10/codegen.txt)
   uint32_t pool = 0, pool_end = 0;
   uint32_t nxt_lane0 = 0;  // lane 0: base of the armed next chunk
   bool nxt_armed = false;
@@ -3189,11 +3307,8 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
   // chunk and ends the iteration: the next trace pass is that chunk's, and the lanes
   // that took a hit keep it across the pass (so the round after it shades a full wave).
   // One world_hit and one shade sequence are inlined either way.
-  constexpr int kNoHit = -2;
   WorldHit w{kNoHit, -1, 0};
   bool fill = false;  // (PT, wave-uniform) the coming trace pass is the ring's chunk
-  // TIMED (PT) -> W.counters[39..41]: ticks and passes of the pre-trace, shade rounds
-  uint64_t tpt[3] = {0, 0, 0};
   for (;;) {
     ++n_iter;
     uint64_t tq = TIMED ? __builtin_amdgcn_s_memtime() : 0;
@@ -3207,9 +3322,8 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
     if (nm && pool < n_paths) {
       const SceneView S = view();
       const PathWork W = work();
-      const uint32_t cnt = __popcll(nm);
-      const uint32_t rank = __popcll(nm & ((1ull << lane_id()) - 1));
-      const uint32_t avail = pool_end - pool;
+      const PoolRanks k = pool_ranks(nm, pool, pool_end);
+      const uint32_t cnt = k.cnt, rank = k.rank, avail = k.avail;
       uint32_t idx = 0;
       if (RING) {
         // lanes whose path is in the ring's chunk take it first (before the chunk is replaced)
@@ -3217,7 +3331,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
           const uint32_t i0 = pool + rank;
           if (i0 < n_paths) {
             g = (int)i0;
-            ring_get<BS>(ringw + (i0 - ring_base), r, rng);
+            ring_take<BS, false>(ringw + (i0 - ring_base), r, rng, w);
             depth = 0;
           }
         }
@@ -3234,23 +3348,15 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
             if (lane_id() == 0) b = (uint32_t)atomicAdd(W.cursor, (unsigned long long)kPoolChunk);
             nb = __builtin_amdgcn_readfirstlane(b);
           }
-          // the next chunk's camera rays, one per lane, every lane of the wave
-          const uint32_t gi = nb + (uint32_t)lane_id();
-          if (gi < n_paths) {
-            Ray gr;
-            Rng grng;
-            path_camera_ray(S, W, gi, gr, grng);
-            ring_put<BS>(ringw + lane_id(), gr, grng);
-          }
-          // (one wave writes and reads these entries: its LDS operations run in order;
-          // the fence keeps the compiler from moving the reads above the writes)
+          ring_fill<BS, false>(ringw, S, W, nb, n_paths);
+          // (the fence keeps the compiler from moving the reads above the writes)
           __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
           ring_base = nb;
           if (need && rank >= avail) {
             const uint32_t i1 = nb + (rank - avail);
             if (i1 < n_paths) {
               g = (int)i1;
-              ring_get<BS>(ringw + (i1 - nb), r, rng);
+              ring_take<BS, false>(ringw + (i1 - nb), r, rng, w);
               depth = 0;
             }
           }
@@ -3281,16 +3387,16 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
         depth = 0;
       }
     }
-    if (!nxt_armed && pool_end < n_paths) {  // arm the next chunk
-      if (lane_id() == 0) nxt_lane0 = (uint32_t)atomicAdd(paths_args()->W.cursor, (unsigned long long)kPoolChunk);
+    if (!nxt_armed && pool_end < n_paths) {
+      nxt_lane0 = pool_arm(nxt_lane0);
       nxt_armed = true;
     }
     if (__ballot(g >= 0) == 0) break;
-    if (TIMED) tf[9] += __popcll(__ballot(g >= 0));
+    if (TIMED) tf[tf_at<kCtrLanesInPath>()] += __popcll(__ballot(g >= 0));
     if (TIMED) {
       __builtin_amdgcn_s_waitcnt(0);
       const uint64_t t = __builtin_amdgcn_s_memtime();
-      tp[0] += t - tq;
+      tp[tp_at<kCtrTicksRefill>()] += t - tq;
       tq = t;
       ++it;
     }
@@ -3307,7 +3413,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
         if (act) ring_get_ray<BS>(ringw + lane_id(), tr);
       }
       if (TIMED) {
-        tf[9] += __popcll(__ballot(g >= 0));
+        tf[tf_at<kCtrLanesInPath>()] += __popcll(__ballot(g >= 0));
         ++it;
       }
     }
@@ -3320,7 +3426,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
       // (clamped: a host compiled with another SRR_KSTACK must not index past the
       // kernel's kStack LDS entries per lane)
       cx.st_cap = min(W.stack_cap, kStack);
-      cx.ovf = W.counters + 11;
+      cx.ovf = W.counters + kCtrStackOverflows;
       cx.gst = W.gstack;
       cx.gst_cap = W.gstack ? W.gstack_cap : 0;
       cx.gst_stride = W.lanes;
@@ -3354,48 +3460,28 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
         }
       }
 #ifdef SRR_SLOW_RAYS
-      // diagnostics build: every lane of a world hit slower than SRR_SLOW_RAYS
-      // ticks (100 MHz) records its ray: g, depth, o, d, time, ticks, steps, hit
-      const uint64_t t_w = __builtin_amdgcn_s_memrealtime() - t_w0;
-      if ((t_w > (uint64_t)SRR_SLOW_RAYS || (cx.last_steps & (1 << 28))) && W.slow_rays) {
-        const unsigned q = atomicAdd(W.slow_count, 1u);
-        if (q < 65536u) {
-          float* e = W.slow_rays + 16 * (size_t)q;
-          e[0] = __int_as_float(g);
-          e[1] = __int_as_float(depth);
-          e[2] = r_in.o.x; e[3] = r_in.o.y; e[4] = r_in.o.z;
-          e[5] = r_in.d.x; e[6] = r_in.d.y; e[7] = r_in.d.z;
-          e[8] = r_in.tm;
-          e[9] = __int_as_float((int)t_w);
-          e[10] = __int_as_float(cx.last_steps);
-          e[11] = __int_as_float(wh.obj);
-          e[12] = __int_as_float(wh.prim);
-          e[13] = wh.t;
-          e[14] = __int_as_float(slot);
-          e[15] = __int_as_float((int)(t_w0 & 0x7fffffff));
-        }
-      }
+      slow_ray_record(W, g, depth, r_in, t_w0, cx.last_steps, wh, slot);
 #endif
       if (TIMED) {
         const uint64_t t = __builtin_amdgcn_s_memtime();
         if (fill_now) {  // the pre-trace pass is a phase of its own
-          tpt[0] += t - tq;
-          ++tpt[1];
+          tpt[tpt_at<kCtrTicksPretrace>()] += t - tq;
+          ++tpt[tpt_at<kCtrPretracePasses>()];
         } else {
           if (__ballot(depth != 0) == 0) {
-            tz[0] += t - tq;
-            ++tz[1];
+            tz[tz_at<kCtrTicksCamOnly>()] += t - tq;
+            ++tz[tz_at<kCtrItsCamOnly>()];
           }
-          tp[1] += t - tq - cx.mesh_cycles;
-          tp[2] += cx.mesh_cycles;
-          tf[10] += cx.mesh_steps;
-          tf[11] += cx.mesh_lane_steps;
-          tf[12] += cx.mesh_walkers;
-          tf[13] += cx.leaf_cycles;
-          tf[14] += cx.leaf_passes;
-          tf[15] += cx.step_parts[0];
-          tf[16] += cx.step_parts[1];
-          tf[17] += cx.step_parts[2];
+          tp[tp_at<kCtrTicksWorld>()] += t - tq - cx.mesh_cycles;
+          tp[tp_at<kCtrTicksMesh>()] += cx.mesh_cycles;
+          tf[tf_at<kCtrMeshSteps>()] += cx.mesh_steps;
+          tf[tf_at<kCtrMeshLaneSteps>()] += cx.mesh_lane_steps;
+          tf[tf_at<kCtrMeshWalkers>()] += cx.mesh_walkers;
+          tf[tf_at<kCtrLeafTicks>()] += cx.leaf_cycles;
+          tf[tf_at<kCtrLeafPasses>()] += cx.leaf_passes;
+          tf[tf_at<kCtrStepFetch>()] += cx.step_parts[0];
+          tf[tf_at<kCtrStepSlab>()] += cx.step_parts[1];
+          tf[tf_at<kCtrStepOrder>()] += cx.step_parts[2];
         }
         tq = t;
       }
@@ -3420,25 +3506,20 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
       const bool need = g < 0;
       const uint64_t nm = __ballot(need);
       if (nm && pool < n_paths) {
-        const uint32_t cnt = __popcll(nm);
-        const uint32_t rank = __popcll(nm & ((1ull << lane_id()) - 1));
-        const uint32_t avail = pool_end - pool;
+        const PoolRanks k = pool_ranks(nm, pool, pool_end);
+        const uint32_t cnt = k.cnt, rank = k.rank, avail = k.avail;
         if (need && rank < avail) {
           const uint32_t i0 = pool + rank;
           if (i0 < n_paths) {
-            const lds_ptr<const float> e = ringw + (i0 - ring_base);
             g = (int)i0;
-            ring_get<BS>(e, r, rng);
-            w = WorldHit{__float_as_int(e[kRingHitWord * BS]), __float_as_int(e[(kRingHitWord + 1) * BS]),
-                         e[(kRingHitWord + 2) * BS]};
+            ring_take<BS, true>(ringw + (i0 - ring_base), r, rng, w);
             depth = 0;
           }
         }
         if (avail >= cnt) {
           pool += cnt;
         } else {
-          // the ring is short: the next chunk's camera rays, one per lane, every lane of
-          // the wave; the coming trace pass is theirs
+          // the ring is short: the next chunk's camera rays; the coming trace pass is theirs
           const SceneView S = view();
           const PathWork W = work();
           uint32_t nb;
@@ -3453,14 +3534,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
           }
           // (the fence keeps the compiler from moving the writes above the reads of the old chunk)
           __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-          const uint32_t gi = nb + (uint32_t)lane_id();
-          if (gi < n_paths) {
-            Ray gr;
-            Rng grng;
-            path_camera_ray(S, W, gi, gr, grng);
-            ring_put<BS>(ringw + lane_id(), gr, grng);
-            ring_put_hit<BS>(ringw + lane_id(), kNoHit, -1, 0.f);
-          }
+          ring_fill<BS, true>(ringw, S, W, nb, n_paths);
           __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
           ring_base = nb;
           pool = nb;
@@ -3471,7 +3545,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
       if (TIMED) {
         __builtin_amdgcn_s_waitcnt(0);
         const uint64_t t = __builtin_amdgcn_s_memtime();
-        tp[0] += t - tq;
+        tp[tp_at<kCtrTicksRefill>()] += t - tq;
         tq = t;
       }
       if (fill) break;  // (wave-uniform) trace the chunk first
@@ -3480,7 +3554,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
     const bool sh = g >= 0 && (!PT || w.obj != kNoHit);
     if constexpr (PT) {
       if (__ballot(sh) == 0) break;
-      if (TIMED) ++tpt[2];
+      if (TIMED) ++tpt[tpt_at<kCtrShadeRounds>()];
     }
     bool done = sh && (PT || !walking);  // (a suspended walk's record, scatter and fold wait for its end)
     V3 C = v3(0.f);
@@ -3503,15 +3577,15 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
         if (TIMED) {
           __builtin_amdgcn_s_waitcnt(0);
           const uint64_t t = __builtin_amdgcn_s_memtime();
-          tp[5] += t - tq;
+          tp[tp_at<kCtrTicksRecord>()] += t - tq;
           tq = t;
         }
         const int fam = family_of(h.mat, kind, depth, W.max_depth);
         if (TIMED) {
           const uint64_t mb = __ballot(fam == FAM_BECK), ms = __ballot(fam == FAM_SPEC),
                          md = __ballot(fam == FAM_DIFF && S.n_lights > 0);
-          tf[3] += mb != 0; tf[4] += ms != 0; tf[5] += md != 0;
-          tf[6] += __popcll(mb); tf[7] += __popcll(ms); tf[8] += __popcll(md);
+          tf[tf_at<kCtrItsBeck>()] += mb != 0; tf[tf_at<kCtrItsSpec>()] += ms != 0; tf[tf_at<kCtrItsDiff>()] += md != 0;
+          tf[tf_at<kCtrLanesBeck>()] += __popcll(mb); tf[tf_at<kCtrLanesSpec>()] += __popcll(ms); tf[tf_at<kCtrLanesDiff>()] += __popcll(md);
         }
         if (fam == FAM_TERM) {
           C = hit_emitted(S, h.mat, r.d, h.p, h.n, h.u, h.v);
@@ -3563,26 +3637,26 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
         sum += __shfl_xor(sum, o);
         mx = max(mx, __shfl_xor(mx, o));
       }
-      tf[18] += sum;
-      tf[19] += mx;
+      tf[tf_at<kCtrBeckAttempts>()] += sum;
+      tf[tf_at<kCtrBeckAttemptsMax>()] += mx;
       // the family branches' wave time this iteration: the longest of their lanes' stamps
       // (lanes of one branch run it together; lanes outside it stamped 0)
       for (int q = 0; q < 3; ++q) {
         uint64_t m = fam_dt[q];
         for (int o = 32; o > 0; o >>= 1) m = max(m, (uint64_t)__shfl_xor((unsigned long long)m, o));
-        tf[q] += m;
+        tf[tf_at<kCtrTicksBeck>() + q] += m;
       }
     }
     if (__ballot(pend)) {
       const SceneView S = view();
-      const uint64_t tc = TIMED ? __builtin_amdgcn_s_memtime() : 0;
+      const uint64_t t_mix = TIMED ? __builtin_amdgcn_s_memtime() : 0;
       // one round of per-lane loops passing over dead draws, then the
       // wave-cooperative loop for what is left
       int rounds = skip_mixture(S, ds, d_dead, pend, d_tries, rng.lcg, d_dir, d_pdf, 1);
       if (__ballot(pend)) rounds += coop_mixture(S, ds, pend, d_tries, rng.lcg, d_dir, d_pdf, paths_args()->W.deep_tries);
       if (TIMED) {
-        tp[6] += __builtin_amdgcn_s_memtime() - tc;
-        tp[7] += rounds;
+        tp[tp_at<kCtrTicksMixture>()] += __builtin_amdgcn_s_memtime() - t_mix;
+        tp[tp_at<kCtrMixtureRounds>()] += rounds;
       }
       max_rounds = max(max_rounds, (uint32_t)rounds);
     }
@@ -3602,7 +3676,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
       if (PT) w.obj = kNoHit;  // shaded: a ray to trace, or (below) the path's end
       if (TIMED) {
         const uint64_t t = __builtin_amdgcn_s_memtime();
-        tp[3] += t - tq;
+        tp[tp_at<kCtrTicksShade>()] += t - tq;
         tq = t;
       }
       if (done && (g >= W.n_paths || depth > W.max_depth)) {
@@ -3643,12 +3717,12 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
         nrays += depth + 1;
         g = -1;
       }
-      if (TIMED) tp[4] += __builtin_amdgcn_s_memtime() - tq;
+      if (TIMED) tp[tp_at<kCtrTicksFold>()] += __builtin_amdgcn_s_memtime() - tq;
     }
     }  // (round)
     if constexpr (PT) {
-      if (!nxt_armed && pool_end < n_paths) {  // arm the next chunk
-        if (lane_id() == 0) nxt_lane0 = (uint32_t)atomicAdd(paths_args()->W.cursor, (unsigned long long)kPoolChunk);
+      if (!nxt_armed && pool_end < n_paths) {
+        nxt_lane0 = pool_arm(nxt_lane0);
         nxt_armed = true;
       }
       // (no lane in a path, no chunk waiting for its trace pass, no path left to hand out)
@@ -3656,20 +3730,20 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
     }
   }
   const PathWork W = work();
-  if (TIMED && lane_id() == 0) {  // per-wave totals -> W.counters[4..9]
-    for (int q = 0; q < 5; ++q) atomicAdd(W.counters + 4 + q, (unsigned long long)tp[q]);
-    atomicAdd(W.counters + 9, (unsigned long long)it);
-    atomicAdd(W.counters + 10, (unsigned long long)tp[5]);
-    atomicAdd(W.counters + 13, (unsigned long long)tp[6]);
-    atomicAdd(W.counters + 14, (unsigned long long)tp[7]);
-    for (int q = 0; q < 20; ++q) atomicAdd(W.counters + 16 + q, (unsigned long long)tf[q]);
-    for (int q = 0; q < 2; ++q) atomicAdd(W.counters + 37 + q, (unsigned long long)tz[q]);
-    for (int q = 0; q < 3; ++q) atomicAdd(W.counters + 39 + q, (unsigned long long)tpt[q]);
+  if (TIMED && lane_id() == 0) {  // per-wave totals
+    for (int q = 0; q < kTpPhases; ++q) atomicAdd(W.counters + kCtrTicksRefill + q, (unsigned long long)tp[q]);
+    atomicAdd(W.counters + kCtrWaveIters, (unsigned long long)it);
+    atomicAdd(W.counters + kCtrTicksRecord, (unsigned long long)tp[tp_at<kCtrTicksRecord>()]);
+    atomicAdd(W.counters + kCtrTicksMixture, (unsigned long long)tp[tp_at<kCtrTicksMixture>()]);
+    atomicAdd(W.counters + kCtrMixtureRounds, (unsigned long long)tp[tp_at<kCtrMixtureRounds>()]);
+    for (int q = 0; q < kTfWords; ++q) atomicAdd(W.counters + kCtrTicksBeck + q, (unsigned long long)tf[q]);
+    for (int q = 0; q < kTzWords; ++q) atomicAdd(W.counters + kCtrTicksCamOnly + q, (unsigned long long)tz[q]);
+    for (int q = 0; q < kTptWords; ++q) atomicAdd(W.counters + kCtrTicksPretrace + q, (unsigned long long)tpt[q]);
   }
 
   unsigned long long tot = nrays;
   for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
-  if (lane_id() == 0 && tot) atomicAdd(W.counters, tot);
+  if (lane_id() == 0 && tot) atomicAdd(W.counters + kCtrWorldRays, tot);
   if (__ballot(n_events != 0)) {
     unsigned long long cap = n_events & (kSuspended - 1), su = n_events / kSuspended;
     for (int o = 32; o > 0; o >>= 1) {
@@ -3677,8 +3751,8 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
       su += __shfl_xor(su, o);
     }
     if (lane_id() == 0) {
-      if (cap) atomicAdd(W.counters + 15, cap);
-      if (su) atomicAdd(W.counters + 36, su);
+      if (cap) atomicAdd(W.counters + kCtrMixtureCapped, cap);
+      if (su) atomicAdd(W.counters + kCtrSuspended, su);
     }
   }
   if (W.wave_times && lane_id() == 0) {  // diagnostics: start, exit, world rays, wave-iterations

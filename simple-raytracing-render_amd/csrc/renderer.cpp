@@ -13,7 +13,6 @@
 
 namespace srr {
 
-constexpr int kCtrWords = 48;  // FrameSlot::ctr: world rays, cursor, error, overflow and diagnostics counters
 constexpr int kVisitWords = 3 + 2 * 64;  // SRR_FLAG_COUNT_VISITS: sums + two histograms
 
 #define RCHK(x)                                                        \
@@ -366,8 +365,8 @@ static int slot_init(FrameSlot& F, hipStream_t shared_st, std::string& err) {
   }
   RCHK(hipEventCreate(&F.ev_beg));
   RCHK(hipEventCreate(&F.ev_end));
-  RCHK(hipMalloc((void**)&F.ctr, kCtrWords * sizeof(unsigned long long)));
-  RCHK(hipHostMalloc((void**)&F.ctr_host, kCtrWords * sizeof(unsigned long long)));
+  RCHK(hipMalloc((void**)&F.ctr, kPathsCtrWords * sizeof(unsigned long long)));
+  RCHK(hipHostMalloc((void**)&F.ctr_host, kPathsCtrWords * sizeof(unsigned long long)));
   return 0;
 }
 
@@ -504,11 +503,11 @@ static PathWork paths_work(srr_renderer* r, FrameSlot& F, const srr_params* p, c
   w.base_seed = p->base_seed;
   w.n_paths = (int64_t)npix * Wn;
   w.max_depth = p->max_depth;
-  w.cursor = F.ctr + 1;
+  w.cursor = F.ctr + kCtrCursor;
   w.counters = F.ctr;
   w.sample = F.sample;
   w.rec = F.rec;
-  w.err = (int*)(F.ctr + 2);
+  w.err = (int*)(F.ctr + kCtrError);
   const int64_t bl = paths_block_lanes(r->view);  // whole blocks of the launch's size
   w.lanes = (int)std::min<int64_t>(r->pw_lanes, ((w.n_paths + bl - 1) / bl) * bl);
   w.stack_cap = ps.stack_cap;
@@ -538,7 +537,7 @@ static int paths_enqueue(srr_renderer* r, FrameSlot& F, const srr_params* p, boo
     const int rc = ensure_window(r, F, (size_t)npix * W, err);
     if (rc < 0) return rc;
   }
-  RCHK(hipMemsetAsync(F.ctr, 0, kCtrWords * sizeof(unsigned long long), st));
+  RCHK(hipMemsetAsync(F.ctr, 0, kPathsCtrWords * sizeof(unsigned long long), st));
   const bool want_sums = (p->flags & SRR_FLAG_SUMS) != 0;
   // per-window HIP events around k_paths, read once the frame is done (no host
   // round trip between windows)
@@ -623,7 +622,7 @@ static int paths_enqueue(srr_renderer* r, FrameSlot& F, const srr_params* p, boo
     else
       launch_finish(acc, d_mean, npix, (int)acc_total, st);
   }
-  RCHK(hipMemcpyAsync(F.ctr_host, F.ctr, kCtrWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  RCHK(hipMemcpyAsync(F.ctr_host, F.ctr, kPathsCtrWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   RCHK(hipEventRecord(F.ev_end, st));
   F.npix = npix;
   F.paths = npix * p->spp;
@@ -640,36 +639,43 @@ static int paths_finish(srr_renderer* r, FrameSlot& F, const srr_params* p, srr_
     RCHK(hipEventElapsedTime(&ms, F.win_ev[2 * wi], F.win_ev[2 * wi + 1]));
     kernel_ms += ms;
   }
-  unsigned long long ctr[kCtrWords];
+  unsigned long long ctr[kPathsCtrWords];
   std::memcpy(ctr, F.ctr_host, sizeof(ctr));
-  if (getenv("SRR_PATHS_TIMING") && ctr[9]) {
-    const double it = (double)ctr[9];
+  if (getenv("SRR_PATHS_TIMING") && ctr[kCtrWaveIters]) {
+    const double it = (double)ctr[kCtrWaveIters];
     fprintf(stderr, "k_paths per wave-iteration (ticks): refill %.0f  world %.0f  mesh %.0f  record %.0f  scatter %.0f  fold %.0f  (%llu wave-iterations)\n",
-            ctr[4] / it, ctr[5] / it, ctr[6] / it, ctr[10] / it, (ctr[7] - ctr[10]) / it, ctr[8] / it, ctr[9]);
-    fprintf(stderr, "  scatter: mixture loop %.0f ticks, %.2f rounds per wave-iteration\n", ctr[13] / it, ctr[14] / it);
+            ctr[kCtrTicksRefill] / it, ctr[kCtrTicksWorld] / it, ctr[kCtrTicksMesh] / it, ctr[kCtrTicksRecord] / it,
+            (ctr[kCtrTicksShade] - ctr[kCtrTicksRecord]) / it, ctr[kCtrTicksFold] / it, ctr[kCtrWaveIters]);
+    fprintf(stderr, "  scatter: mixture loop %.0f ticks, %.2f rounds per wave-iteration\n", ctr[kCtrTicksMixture] / it,
+            ctr[kCtrMixtureRounds] / it);
     auto per = [](unsigned long long a, unsigned long long b) { return b ? (double)a / (double)b : 0.0; };
     fprintf(stderr, "  families: beck %.0f ticks/it (runs in %.1f %% of its, %.1f lanes/run), spec %.0f (%.1f %%, %.1f), "
                     "diff set-up %.0f (%.1f %%, %.1f); lanes in a path %.1f of 64\n",
-            ctr[16] / it, 100 * ctr[19] / it, per(ctr[22], ctr[19]), ctr[17] / it, 100 * ctr[20] / it,
-            per(ctr[23], ctr[20]), ctr[18] / it, 100 * ctr[21] / it, per(ctr[24], ctr[21]), ctr[25] / it);
+            ctr[kCtrTicksBeck] / it, 100 * ctr[kCtrItsBeck] / it, per(ctr[kCtrLanesBeck], ctr[kCtrItsBeck]),
+            ctr[kCtrTicksSpec] / it, 100 * ctr[kCtrItsSpec] / it, per(ctr[kCtrLanesSpec], ctr[kCtrItsSpec]),
+            ctr[kCtrTicksDiffSetup] / it, 100 * ctr[kCtrItsDiff] / it, per(ctr[kCtrLanesDiff], ctr[kCtrItsDiff]),
+            ctr[kCtrLanesInPath] / it);
     fprintf(stderr, "  mesh: longest walk %.1f node steps/it, %.1f lane steps/it over %.1f walking lanes, "
                     "%.0f ticks per step of the longest walk\n",
-            ctr[26] / it, ctr[27] / it, ctr[28] / it, per(ctr[6], ctr[26]));
-    fprintf(stderr, "  mesh leaf queue: %.0f ticks/it, %.1f passes/it (%.0f ticks per pass)\n", ctr[29] / it,
-            ctr[30] / it, per(ctr[29], ctr[30]));
+            ctr[kCtrMeshSteps] / it, ctr[kCtrMeshLaneSteps] / it, ctr[kCtrMeshWalkers] / it,
+            per(ctr[kCtrTicksMesh], ctr[kCtrMeshSteps]));
+    fprintf(stderr, "  mesh leaf queue: %.0f ticks/it, %.1f passes/it (%.0f ticks per pass)\n", ctr[kCtrLeafTicks] / it,
+            ctr[kCtrLeafPasses] / it, per(ctr[kCtrLeafTicks], ctr[kCtrLeafPasses]));
     fprintf(stderr, "  mesh step parts (ticks/it): node fetch %.0f  slab + queue %.0f  order + push + pop %.0f\n",
-            ctr[31] / it, ctr[32] / it, ctr[33] / it);
+            ctr[kCtrStepFetch] / it, ctr[kCtrStepSlab] / it, ctr[kCtrStepOrder] / it);
     fprintf(stderr, "  beckmann mixture: %.2f attempts per Beckmann scatter, %.2f for the wave's slowest lane per run\n",
-            per(ctr[34], ctr[22]), per(ctr[35], ctr[19]));
-    fprintf(stderr, "  suspended walks: %.2f lanes per wave-iteration\n", ctr[36] / it);
+            per(ctr[kCtrBeckAttempts], ctr[kCtrLanesBeck]), per(ctr[kCtrBeckAttemptsMax], ctr[kCtrItsBeck]));
+    fprintf(stderr, "  suspended walks: %.2f lanes per wave-iteration\n", ctr[kCtrSuspended] / it);
     fprintf(stderr, "  camera-ray-only iterations (every tracing lane at depth 0): %llu of %llu, world + mesh %.0f ticks "
                     "per wave-iteration of them; the others %.0f\n",
-            ctr[38], ctr[9], per(ctr[37], ctr[38]), per(ctr[5] + ctr[6] - ctr[37], ctr[9] - ctr[38]));
+            ctr[kCtrItsCamOnly], ctr[kCtrWaveIters], per(ctr[kCtrTicksCamOnly], ctr[kCtrItsCamOnly]),
+            per(ctr[kCtrTicksWorld] + ctr[kCtrTicksMesh] - ctr[kCtrTicksCamOnly], ctr[kCtrWaveIters] - ctr[kCtrItsCamOnly]));
     // (the wave-iterations above count every trace pass; the pre-trace passes are among them,
     // their ticks in no other phase)
     fprintf(stderr, "  pre-trace: %llu passes of the %llu wave-iterations, %.0f ticks each (%.0f per wave-iteration); "
                     "shade rounds %.2f per wave-iteration\n",
-            ctr[40], ctr[9], per(ctr[39], ctr[40]), ctr[39] / it, ctr[41] / it);
+            ctr[kCtrPretracePasses], ctr[kCtrWaveIters], per(ctr[kCtrTicksPretrace], ctr[kCtrPretracePasses]),
+            ctr[kCtrTicksPretrace] / it, ctr[kCtrShadeRounds] / it);
   }
 #ifdef SRR_SLOW_RAYS
   if (r->pw_slow) {  // diagnostics build: dump the slow world hits' records (one line per lane, JSON)
@@ -691,17 +697,17 @@ static int paths_finish(srr_renderer* r, FrameSlot& F, const srr_params* p, srr_
   (void)r;
   (void)p;
 #endif
-  if (ctr[2]) {
-    err = "k_paths index guard tripped (bits " + std::to_string(ctr[2]) + ")";
+  if (ctr[kCtrError]) {
+    err = "k_paths index guard tripped (bits " + std::to_string(ctr[kCtrError]) + ")";
     return SRR_EIO;
   }
   float total = 0;
   RCHK(hipEventElapsedTime(&total, F.ev_beg, F.ev_end));
-  s.world_rays = (int64_t)ctr[0];
-  s.stack_overflows = (int64_t)ctr[11];
-  s.deep_traversals = (int64_t)ctr[12];
-  s.mixture_capped = (int64_t)ctr[15];
-  s.walks_suspended = (int64_t)ctr[36];
+  s.world_rays = (int64_t)ctr[kCtrWorldRays];
+  s.stack_overflows = (int64_t)ctr[kCtrStackOverflows];
+  s.deep_traversals = (int64_t)ctr[kCtrDeepTraversals];
+  s.mixture_capped = (int64_t)ctr[kCtrMixtureCapped];
+  s.walks_suspended = (int64_t)ctr[kCtrSuspended];
   s.paths = F.paths;
   s.trace_ms = kernel_ms;
   s.total_ms = total;
@@ -825,7 +831,7 @@ static int adaptive_passes(srr_renderer* r, FrameSlot& F, const srr_params* p, c
   const int32_t* shard_pixels = identity ? nullptr : r->pixels;
   int32_t* n_dev = A.blk + (A.cap + 255) / 256;
   srr_adaptive_stats s{};
-  RCHK(hipMemsetAsync(F.ctr, 0, kCtrWords * sizeof(unsigned long long), st));
+  RCHK(hipMemsetAsync(F.ctr, 0, kPathsCtrWords * sizeof(unsigned long long), st));
   RCHK(hipEventRecord(F.ev_beg, st));
   int n = 0;     // samples every active pixel holds
   int cur = -1;  // the active lists are A.slot / A.pixel[cur]; -1: every slot, in order
@@ -886,17 +892,17 @@ static int adaptive_passes(srr_renderer* r, FrameSlot& F, const srr_params* p, c
     n_act = n_next;
     cur = nxt;
   }
-  RCHK(hipMemcpyAsync(F.ctr_host, F.ctr, kCtrWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  RCHK(hipMemcpyAsync(F.ctr_host, F.ctr, kPathsCtrWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   RCHK(hipEventRecord(F.ev_end, st));
   RCHK(hipStreamSynchronize(st));
   RCHK(hipGetLastError());
-  if (F.ctr_host[2]) {
-    err = "k_paths index guard tripped (bits " + std::to_string(F.ctr_host[2]) + ")";
+  if (F.ctr_host[kCtrError]) {
+    err = "k_paths index guard tripped (bits " + std::to_string(F.ctr_host[kCtrError]) + ")";
     return SRR_EIO;
   }
   float total = 0;
   RCHK(hipEventElapsedTime(&total, F.ev_beg, F.ev_end));
-  s.world_rays = (int64_t)F.ctr_host[0];
+  s.world_rays = (int64_t)F.ctr_host[kCtrWorldRays];
   s.total_ms = total;
   if (stats) {
     s.struct_size = stats->struct_size;

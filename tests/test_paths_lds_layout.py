@@ -31,12 +31,33 @@ int main() { return 0; }
 """
 
 
+# PathWork::counters word by word (kernels.h PathsCtr): the words paths_finish copies into
+# srr_stats keep their numbers (the kernel's immediates, the cursor and error pointers)
+CTR_PROBE = r"""
+#include "kernels.h"
+using namespace srr;
+static_assert(kCtrWorldRays == 0 && kCtrCursor == 1 && kCtrError == 2, "world rays, cursor, error");
+static_assert(kCtrStackOverflows == 11 && kCtrDeepTraversals == 12, "stack overflows, deep traversals");
+static_assert(kCtrMixtureCapped == 15 && kCtrSuspended == 36, "capped loops, suspended walks");
+static_assert(kPathsCtrCount <= kPathsCtrWords, "the names fit the allocation");
+int main() { return 0; }
+"""
+
+
 def test_ring_entry_and_lds_budgets_compile(tmp_path):
+    compile_probe(tmp_path, PROBE)
+
+
+def test_counter_slots_compile(tmp_path):
+    compile_probe(tmp_path, CTR_PROBE)
+
+
+def compile_probe(tmp_path, text):
     cxx = shutil.which("g++") or shutil.which("c++")
     if cxx is None:
         pytest.fail("no host C++ compiler")
     src = tmp_path / "probe.cpp"
-    src.write_text(PROBE)
+    src.write_text(text)
     inc = []
     for d in ("/opt/rocm/include", os.environ.get("ROCM_PATH", "") + "/include"):
         if os.path.isdir(d):
