@@ -117,7 +117,7 @@ struct PathWork {
   float* raw;             // optional kept paths [npix][keep_spp][3] before de_nan
   uint8_t* rays;          // optional kept [npix][keep_spp] world rays per path
   int keep_spp, keep_s0;  // frame spp and this window's first sample in them
-  float4* rec;            // bounce records [max_depth][lanes]
+  float4* rec;            // bounce records [2][max_depth][lanes]: a survivor slot's column, then a head-pass lane's
   int lanes;              // persistent lanes (grid * block)
   int* err;               // guard bits set on an out-of-range index (never expected)
   int stack_cap;          // BVH4 traversal stack entries (kStack = 8; fewer forces the exact re-walk)
@@ -132,7 +132,11 @@ struct PathWork {
   // path are still walking (0: never); its state goes to the [3][lanes] float4 save area
   // that follows gstack's gstack_cap x lanes entries (so walks suspend only with gstack)
   int walk_q;
+  // chunk-synchronous variants (kernels.hip k_paths' PT; SRR_TAIL_MIN, SRR_POOL_CAP): survivors
+  // in the wave's pool that trigger a tail pass, and the usable survivor slots (1..64)
+  int tail_min, pool_cap;
 };
+constexpr int kPathsTailMin = 48;  // PathWork::tail_min by default: 16 of the 64 slots stay free for arrivals
 
 // The words of PathWork::counters (renderer.cpp FrameSlot::ctr), zeroed per frame.  k_paths
 // adds to them, paths_finish reads the first group into srr_stats and prints the rest as
@@ -175,11 +179,17 @@ enum PathsCtr : int {
   // hold a camera ray (depth 0); the other iterations are the rest
   kCtrTicksCamOnly = 37, kCtrItsCamOnly,
   // the pre-trace: ticks and passes of the chunk's trace, shade rounds
+  // (the chunk-synchronous flow: the head pass's first trace is the pre-trace)
   kCtrTicksPretrace = 39, kCtrPretracePasses, kCtrShadeRounds,
+  // the chunk-synchronous flow's two kinds of pass: ticks of the whole pass (refill or
+  // adoption, trace, shade, fold, promotion), passes, lanes in a path at the trace
+  kCtrTicksHead = 42, kCtrHeadPasses, kCtrHeadLanes,
+  kCtrTicksTail, kCtrTailPasses, kCtrTailLanes,
   kPathsCtrCount
 };
 constexpr int kPathsCtrWords = 48;  // words allocated (FrameSlot::ctr)
-static_assert(kPathsCtrCount == 42 && kPathsCtrCount <= kPathsCtrWords, "PathsCtr fits FrameSlot::ctr");
+static_assert(kPathsCtrCount == 48 && kPathsCtrCount <= kPathsCtrWords, "PathsCtr fits FrameSlot::ctr");
+static_assert(kCtrTailLanes == kCtrTicksHead + 5, "head and tail words");
 // the groups that code walks by offset: the phases, the three family branches in BECK, SPEC,
 // DIFF order (ticks, its, lanes), the step parts (TraceCtx::step_parts), the deep word behind
 // the overflow word (TraceCtx::ovf)
@@ -204,10 +214,12 @@ constexpr int kPathsWorldLdsBytes = 8192;  // == kernels.hip kWorldLdsBytes
 constexpr int kPathsLdsNodes = SRR_LDS_NODES;  // BVH4 nodes cached in LDS by k_paths (128 B each)
 
 // k_paths' camera-ray ring (kernels.hip ring_put / ring_get): one entry per lane, the
-// path's camera ray and RNG streams and, in the variants that trace a chunk's camera
-// rays where they are generated (no media, not quad-cooperative), the ray's world hit
+// path's camera ray and RNG streams.  In the chunk-synchronous variants (no media, not
+// quad-cooperative, diffuse only) the same entries are the wave's survivor pool
+// (kernels.hip pool_put / pool_get): ray, LCG, then path index and depth in the PCG's
+// words 9 and 10; words 11..13 (once the pre-traced hit) are unused
 constexpr int kRingRayWords = 11;            // o.xyz, d.xyz, time, lcg (2 words), pcg (2 words)
-constexpr int kRingHitWord = kRingRayWords;  // obj, prim, t: words 11, 12, 13
+constexpr int kRingHitWord = kRingRayWords;  // words 11, 12, 13
 constexpr int kRingWordsHit = kRingHitWord + 3;
 constexpr int ring_words(bool pretrace) { return pretrace ? kRingWordsHit : kRingRayWords; }
 static_assert(ring_words(false) == 11 && ring_words(true) == 14 && kRingHitWord + 2 < kRingWordsHit, "ring entry layout");

@@ -2974,9 +2974,9 @@ constexpr unsigned long long kPoolChunk = 64;  // path indices a wave takes per 
 // Camera-ray ring.  A wave takes path indices from the cursor a 64-path chunk at a
 // time (k_paths' pool) and generates the chunk's camera rays at once -- lane k the ray of
 // path chunk + k, every lane busy -- into its 64 LDS entries (ring_fill); a lane
-// whose path ended just reads its entry (ring_take).  In the pre-trace variants
-// (k_paths' PT) the wave also traces the chunk where it generated it, one coherent
-// pass, and the entry carries the hit to the lane that takes it.  Generating a camera
+// whose path ended just reads its entry (ring_get).  The chunk-synchronous variants
+// (k_paths' PT) generate a chunk's rays straight into the lanes' registers and use the
+// same entries as their survivor pool (pool_put / pool_get below).  Generating a camera
 // ray (pixel and sample from the path index, per-path seeds, Sobol point, lens disk,
 // normalisation) is a few hundred VALU instructions, and about half the lanes refill
 // per wave-iteration (C2 paths average 2.03 world rays): a refilling lane that
@@ -3030,25 +3030,37 @@ SRR_D void ring_get(lds_ptr<const float> e, Ray& r, Rng& rng) {
   rng.pcg = (uint64_t)__float_as_uint(e[9 * BS]) | ((uint64_t)__float_as_uint(e[10 * BS]) << 32);
 }
 
-// the entry's pre-traced world hit (obj kNoHit: not traced, the taking lane traces it)
-constexpr int kNoHit = -2;
+// The same entries as the survivor pool of the chunk-synchronous variants (k_paths' PT):
+// entry e holds a path between two tail passes -- its next ray, its LCG, and in the
+// PCG's words its index and depth.  (Those variants never reach pcg_uniform: it is
+// drawn only by the Beckmann generate, which the diffuse-only kernels do not contain.)
 template <int BS>
-SRR_D void ring_put_hit(lds_ptr<float> e, int obj, int prim, float t) {
-  e[kRingHitWord * BS] = __int_as_float(obj);
-  e[(kRingHitWord + 1) * BS] = __int_as_float(prim);
-  e[(kRingHitWord + 2) * BS] = t;
+SRR_D void pool_put(lds_ptr<float> e, const Ray& r, const Rng& rng, int g, int depth) {
+  e[0] = r.o.x;
+  e[BS] = r.o.y;
+  e[2 * BS] = r.o.z;
+  e[3 * BS] = r.d.x;
+  e[4 * BS] = r.d.y;
+  e[5 * BS] = r.d.z;
+  e[6 * BS] = r.tm;
+  e[7 * BS] = __uint_as_float((uint32_t)rng.lcg);
+  e[8 * BS] = __uint_as_float((uint32_t)(rng.lcg >> 32));
+  e[9 * BS] = __int_as_float(g);
+  e[10 * BS] = __int_as_float(depth);
 }
 template <int BS>
-SRR_D WorldHit ring_get_hit(lds_ptr<const float> e) {
-  return WorldHit{__float_as_int(e[kRingHitWord * BS]), __float_as_int(e[(kRingHitWord + 1) * BS]), e[(kRingHitWord + 2) * BS]};
+SRR_D void pool_get(lds_ptr<const float> e, Ray& r, Rng& rng, int& g, int& depth) {
+  ring_get_ray<BS>(e, r);
+  rng.lcg = (uint64_t)__float_as_uint(e[7 * BS]) | ((uint64_t)__float_as_uint(e[8 * BS]) << 32);
+  g = __float_as_int(e[9 * BS]);
+  depth = __float_as_int(e[10 * BS]);
 }
 
 // The wave fills its ring with chunk nb: lane k the camera ray of path nb + k, every
-// lane of the wave (HIT: the entry's hit starts as not traced).  `ring` is the wave's
-// entry 0.  The caller fences: one wave writes and reads these entries and its LDS
-// operations run in order, so a wavefront fence is enough, but where it must stand
-// depends on what the site read from the old chunk.
-template <int BS, bool HIT>
+// lane of the wave.  `ring` is the wave's entry 0.  The caller fences: one wave writes
+// and reads these entries and its LDS operations run in order, so a wavefront fence is
+// enough, but where it must stand depends on what the site read from the old chunk.
+template <int BS>
 SRR_D void ring_fill(lds_ptr<float> ring, const SceneView& S, const PathWork& W, uint32_t nb, uint32_t n_paths) {
   const uint32_t gi = nb + (uint32_t)lane_id();
   if (gi < n_paths) {
@@ -3056,18 +3068,9 @@ SRR_D void ring_fill(lds_ptr<float> ring, const SceneView& S, const PathWork& W,
     Rng grng;
     path_camera_ray(S, W, gi, gr, grng);
     ring_put<BS>(ring + lane_id(), gr, grng);
-    if (HIT) ring_put_hit<BS>(ring + lane_id(), kNoHit, -1, 0.f);
   }
 }
 
-// A refilling lane takes the ring entry e: the path's camera ray and RNG streams and (HIT)
-// the world hit the wave traced for it.  (The lane's path index and depth stay with the
-// caller: k_paths keeps them, like the pool, in plain locals that nothing points to.)
-template <int BS, bool HIT>
-SRR_D void ring_take(lds_ptr<const float> e, Ray& r, Rng& rng, WorldHit& w) {
-  ring_get<BS>(e, r, rng);
-  if (HIT) w = ring_get_hit<BS>(e);
-}
 
 // k_paths' arguments, read through the kernel-argument segment pointer laundered
 // by an empty asm (paths_args): the compiler can no longer prove two reads of a
@@ -3177,6 +3180,11 @@ constexpr int tpt_at() {
   static_assert(Q >= kCtrTicksPretrace && Q < kCtrTicksPretrace + kTptWords, "not a word of tpt");
   return Q - kCtrTicksPretrace;
 }
+constexpr int kThtWords = kCtrTailLanes - kCtrTicksHead + 1;  // the head and tail passes' words (tht)
+// A head pass hands its paths to the survivor pool once no more than this many are alive
+// (and two trace passes are done, and they fit the free slots): with more, the next pass
+// is still denser in these lanes than a tail pass would be.
+constexpr int kHeadLiveMin = 32;
 
 template <bool MEDIA, bool ALLFAM, int MINB, bool TIMED = false, bool WL = true, bool QUAD = false, bool CQ = false,
           int BS = kPathsBlock, bool SP = false>
@@ -3297,21 +3305,85 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
   constexpr uint32_t kCapped = 1, kSuspended = 1u << 12;
   uint32_t n_iter = 0, max_rounds = 0;  // wave-iterations, most mixture rounds (SRR_WAVE_TIMES diagnostics)
   // Without PT an iteration is refill, trace, shade, and every lane in a path does each.
-  // PT: a lane is idle (g < 0), holds a ray to trace (w.obj == kNoHit) or holds a hit to
-  // shade, and an iteration is one trace pass -- the lanes' own rays, or (fill) the ring's new
-  // chunk, whose hits go into the ring while the lanes' own state waits in registers --
-  // and then at most two rounds of refill + shade: lanes whose path ended take the
-  // ring's next paths with their hits, every lane with a hit shades it (record,
-  // scatter, mixture, fold), and the lanes that ended in the first round refill once
-  // more.  A round that finds the ring short hands out what is left, generates the next
-  // chunk and ends the iteration: the next trace pass is that chunk's, and the lanes
-  // that took a hit keep it across the pass (so the round after it shades a full wave).
-  // One world_hit and one shade sequence are inlined either way.
-  WorldHit w{kNoHit, -1, 0};
-  bool fill = false;  // (PT, wave-uniform) the coming trace pass is the ring's chunk
+  // PT (chunk-synchronous): an iteration is one trace pass and one shade of a head pass or
+  // of a tail pass.  A head pass is a 64-path chunk run in lockstep: lane k generates path
+  // chunk + k's camera ray into its registers, and the wave loops trace -> shade over the
+  // lanes still in a path (walks never suspend) until, two trace passes done, the few
+  // paths left fit the free slots of the survivor pool -- the wave's 64 ring entries,
+  // entry e lane e's for good -- and are promoted to it: state into the entry, records so
+  // far into the slot's record column.  A path that ends in the head pass is folded by the
+  // lane that holds it, from the lane's head column of W.rec (a first record kept in
+  // registers across the trace pass cost 32 B of scratch per lane).  A tail pass runs when the pool
+  // holds tail_min paths, when an entry's walk is suspended (the lane's LDS stack is the
+  // walk's), or when no chunk is left: lane e adopts entry e, traces and shades once, and
+  // what continues goes back to entry e.  One world_hit and one shade sequence are
+  // inlined either way.
+  WorldHit w{-1, -1, 0};
+  uint64_t used = 0;   // (PT, wave-uniform) occupied survivor slots
+  uint64_t walkm = 0;  // ... and those whose path's walk is suspended
+  bool head = false, tail = false;  // (PT, wave-uniform) the kind of pass the lanes are in
+  int passes = 0;           // trace passes of the head pass so far
+  uint32_t last_end = 0;    // end of the last chunk this wave took: at n_paths or past it, none is left
+  uint64_t tht[kThtWords] = {0, 0, 0, 0, 0, 0};
+  // the row of record k in W.rec: a survivor slot's column in rows [0, max_depth), a head-pass
+  // lane's own in the max_depth rows after them
+  const auto rec_row = [&](const PathWork& W, int k) { return PT && !tail ? k + W.max_depth : k; };
   for (;;) {
     ++n_iter;
     uint64_t tq = TIMED ? __builtin_amdgcn_s_memtime() : 0;
+    const uint64_t t_pass = tq;
+    if constexpr (PT) {
+      if (!head) {  // no lane holds a path: the next chunk, or the pool's paths
+        const PathWork W = work();
+        if (last_end < n_paths && walkm == 0 && __popcll(used) < max(1, W.tail_min)) {
+          uint32_t nb;
+          if (nxt_armed) {
+            nb = nxt_ready ? nxt_base : __builtin_amdgcn_readfirstlane(nxt_lane0);
+            nxt_armed = false;
+            nxt_ready = false;
+          } else {
+            uint32_t b = 0;
+            if (lane_id() == 0) b = (uint32_t)atomicAdd(W.cursor, (unsigned long long)kPoolChunk);
+            nb = __builtin_amdgcn_readfirstlane(b);
+          }
+          last_end = nb + (uint32_t)kPoolChunk;
+          if (nb < n_paths) {
+            const SceneView S = view();
+            const uint32_t gi = nb + (uint32_t)lane_id();
+            if (gi < n_paths) {
+              path_camera_ray(S, W, gi, r, rng);
+              g = (int)gi;
+              depth = 0;
+            }
+            head = true;
+            passes = 0;
+          }
+        }
+        if (!head) {
+          if (used == 0) break;  // (no chunk left: an armed one is always taken above)
+          tail = true;
+          if ((used >> lane_id()) & 1) {
+            pool_get<BS>(ringw + lane_id(), r, rng, g, depth);
+            if constexpr (SP) walking = (int)((walkm >> lane_id()) & 1);
+          }
+        }
+      }
+      if (!nxt_armed && last_end < n_paths) {
+        nxt_lane0 = pool_arm(nxt_lane0);
+        nxt_armed = true;
+      }
+      if (TIMED) {
+        __builtin_amdgcn_s_waitcnt(0);
+        const uint64_t t = __builtin_amdgcn_s_memtime();
+        tp[tp_at<kCtrTicksRefill>()] += t - tq;
+        tq = t;
+        const int n_in = __popcll(__ballot(g >= 0));
+        tf[tf_at<kCtrLanesInPath>()] += n_in;
+        ++it;
+        ++tht[tail ? kCtrTailPasses - kCtrTicksHead : kCtrHeadPasses - kCtrTicksHead];
+        tht[tail ? kCtrTailLanes - kCtrTicksHead : kCtrHeadLanes - kCtrTicksHead] += n_in;
+      }
+    }
     if constexpr (!PT) {
     w = WorldHit{-1, -1, 0};  // (nothing is kept from the last iteration)
     // refill lanes whose path ended, from the wave's pool of path indices; the
@@ -3331,7 +3403,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
           const uint32_t i0 = pool + rank;
           if (i0 < n_paths) {
             g = (int)i0;
-            ring_take<BS, false>(ringw + (i0 - ring_base), r, rng, w);
+            ring_get<BS>(ringw + (i0 - ring_base), r, rng);
             depth = 0;
           }
         }
@@ -3348,7 +3420,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
             if (lane_id() == 0) b = (uint32_t)atomicAdd(W.cursor, (unsigned long long)kPoolChunk);
             nb = __builtin_amdgcn_readfirstlane(b);
           }
-          ring_fill<BS, false>(ringw, S, W, nb, n_paths);
+          ring_fill<BS>(ringw, S, W, nb, n_paths);
           // (the fence keeps the compiler from moving the reads above the writes)
           __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
           ring_base = nb;
@@ -3356,7 +3428,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
             const uint32_t i1 = nb + (rank - avail);
             if (i1 < n_paths) {
               g = (int)i1;
-              ring_take<BS, false>(ringw + (i1 - nb), r, rng, w);
+              ring_get<BS>(ringw + (i1 - nb), r, rng);
               depth = 0;
             }
           }
@@ -3401,22 +3473,10 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
       ++it;
     }
     }  // (!PT)
-    // trace: the lanes that hold a ray, or every lane its entry of the ring's new chunk
-    const bool fill_now = PT && fill;
-    bool act = g >= 0 && (!PT || w.obj == kNoHit);
-    Ray tr = r;
-    if constexpr (PT) {
-      if (fill_now) {
-        // (a lane whose own walk is suspended keeps its traversal stack: its entry stays
-        // untraced, kNoHit, and the lane that takes it traces it as its own ray)
-        act = ring_base + (uint32_t)lane_id() < n_paths && !walking;
-        if (act) ring_get_ray<BS>(ringw + lane_id(), tr);
-      }
-      if (TIMED) {
-        tf[tf_at<kCtrLanesInPath>()] += __popcll(__ballot(g >= 0));
-        ++it;
-      }
-    }
+    // trace: the lanes in a path (every one of them holds a ray)
+    const bool head_now = PT && !tail;  // (wave-uniform) a head pass: walks never suspend
+    const bool act = g >= 0;
+    const Ray tr = r;
     if (act) {
       const SceneView S = view();
       const PathWork W = work();
@@ -3435,9 +3495,9 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
         // suspend walks once at most walk_q / 64 of the wave's lanes in a path still walk
         // (the save area follows the global stack extension: none without it)
         // (walk_q 0: threshold 0, and a walk only stops when its lanes all finished)
-        // (the ring's chunk never suspends: threshold 0, nothing to resume)
-        cx.walk_thr = vreg(fill_now ? 0 : (int)((__popcll(__ballot(true)) * (uint32_t)paths_args()->W.walk_q) >> 6));
-        cx.resume = fill_now ? vreg(0) : walking;
+        // (a head pass never suspends: threshold 0, and none of its lanes has a walk to resume)
+        cx.walk_thr = vreg(head_now ? 0 : (int)((__popcll(__ballot(true)) * (uint32_t)paths_args()->W.walk_q) >> 6));
+        cx.resume = walking;
         cx.susp = vreg(0);
       }
 #ifdef SRR_SLOW_RAYS
@@ -3447,16 +3507,12 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
 #endif
       const WorldHit wh =
           world_hit<MEDIA, TIMED ? (TR_BVH4_TIMED | (WL ? TR_WL : 0) | (SP ? TR_SUSP : 0)) : TR>(S, tr, rng, cx);
-      if (fill_now) {
-        ring_put_hit<BS>(ringw + lane_id(), wh.obj, wh.prim, wh.t);
-      } else {
-        w = wh;
-        if constexpr ((TR & TR_SUSP) != 0) {
-          walking = cx.susp;  // (its record, scatter and fold wait for the walk's end)
-          if (walking) {
-            w.obj = PT ? kNoHit : -1;  // (PT: still a ray to trace)
-            n_events += kSuspended;
-          }
+      w = wh;
+      if constexpr ((TR & TR_SUSP) != 0) {
+        walking = cx.susp;  // (its record, scatter and fold wait for the walk's end)
+        if (walking) {
+          w.obj = -1;
+          n_events += kSuspended;
         }
       }
 #ifdef SRR_SLOW_RAYS
@@ -3464,7 +3520,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
 #endif
       if (TIMED) {
         const uint64_t t = __builtin_amdgcn_s_memtime();
-        if (fill_now) {  // the pre-trace pass is a phase of its own
+        if (head_now && passes == 0) {  // a chunk's camera rays: the pre-trace, a phase of its own
           tpt[tpt_at<kCtrTicksPretrace>()] += t - tq;
           ++tpt[tpt_at<kCtrPretracePasses>()];
         } else {
@@ -3486,77 +3542,16 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
         tq = t;
       }
     }
-    if constexpr (PT) {
-      if (fill_now) {
-        // (one wave writes and reads these entries: its LDS operations run in order;
-        // the fence keeps the compiler from moving the refill's reads above the writes)
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        fill = false;
-      }
-    }
     if (nxt_armed && !nxt_ready) {  // (uniform: every lane of the wave is here)
       nxt_base = __builtin_amdgcn_readfirstlane(nxt_lane0);
       nxt_ready = true;
     }
-#pragma nounroll
-    for (int round = 0; round < (PT ? 2 : 1); ++round) {
-    if constexpr (PT) {
-      // refill: lanes whose path ended take the ring's next paths, hits included
-      if (TIMED) tq = __builtin_amdgcn_s_memtime();
-      const bool need = g < 0;
-      const uint64_t nm = __ballot(need);
-      if (nm && pool < n_paths) {
-        const PoolRanks k = pool_ranks(nm, pool, pool_end);
-        const uint32_t cnt = k.cnt, rank = k.rank, avail = k.avail;
-        if (need && rank < avail) {
-          const uint32_t i0 = pool + rank;
-          if (i0 < n_paths) {
-            g = (int)i0;
-            ring_take<BS, true>(ringw + (i0 - ring_base), r, rng, w);
-            depth = 0;
-          }
-        }
-        if (avail >= cnt) {
-          pool += cnt;
-        } else {
-          // the ring is short: the next chunk's camera rays; the coming trace pass is theirs
-          const SceneView S = view();
-          const PathWork W = work();
-          uint32_t nb;
-          if (nxt_armed) {
-            nb = nxt_ready ? nxt_base : __builtin_amdgcn_readfirstlane(nxt_lane0);
-            nxt_armed = false;
-            nxt_ready = false;
-          } else {
-            uint32_t b = 0;
-            if (lane_id() == 0) b = (uint32_t)atomicAdd(W.cursor, (unsigned long long)kPoolChunk);
-            nb = __builtin_amdgcn_readfirstlane(b);
-          }
-          // (the fence keeps the compiler from moving the writes above the reads of the old chunk)
-          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-          ring_fill<BS, true>(ringw, S, W, nb, n_paths);
-          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-          ring_base = nb;
-          pool = nb;
-          pool_end = nb + (uint32_t)kPoolChunk;
-          fill = nb < n_paths;
-        }
-      }
-      if (TIMED) {
-        __builtin_amdgcn_s_waitcnt(0);
-        const uint64_t t = __builtin_amdgcn_s_memtime();
-        tp[tp_at<kCtrTicksRefill>()] += t - tq;
-        tq = t;
-      }
-      if (fill) break;  // (wave-uniform) trace the chunk first
-    }
-    // shade: the lanes that hold a hit (a miss among them: w.obj -1)
-    const bool sh = g >= 0 && (!PT || w.obj != kNoHit);
-    if constexpr (PT) {
-      if (__ballot(sh) == 0) break;
-      if (TIMED) ++tpt[tpt_at<kCtrShadeRounds>()];
-    }
-    bool done = sh && (PT || !walking);  // (a suspended walk's record, scatter and fold wait for its end)
+    {
+    // shade: the lanes that hold a hit (a miss among them: w.obj -1); a suspended walk's
+    // record, scatter and fold wait for its end
+    const bool sh = g >= 0 && !(PT && walking);
+    if (PT && TIMED) ++tpt[tpt_at<kCtrShadeRounds>()];
+    bool done = sh && !walking;
     V3 C = v3(0.f);
     // a diffuse bounce with lights: set up here, its mixture loop runs below with
     // the whole wave (coop_mixture), then its record is written
@@ -3623,7 +3618,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
             if (TIMED) fam_dt[1] = __builtin_amdgcn_s_memtime() - tb;
           }
           if (depth >= W.max_depth || slot >= W.lanes) atomicOr(W.err, 2);
-          else *rec_at(W, depth) = rec;
+          else *rec_at(W, rec_row(W, depth)) = rec;
           if (!sp && S.n_lights > 0 && rec.w == 0) n_events += kCapped;  // the loop reached kMixtureGuard
           r = Ray{h.p, nd, nt};
           ++depth;
@@ -3667,13 +3662,12 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
       if (c < 0) c = 0;
       const V3 as = d_atten * (c / kPi);
       if (depth >= W.max_depth || slot >= W.lanes) atomicOr(W.err, 2);
-      else *rec_at(W, depth) = make_float4(as.x, as.y, as.z, d_pdf);
+      else *rec_at(W, rec_row(W, depth)) = make_float4(as.x, as.y, as.z, d_pdf);
       r = Ray{ds.p, d_dir, r.tm};
       ++depth;
     }
     if (sh) {
       const PathWork W = work();
-      if (PT) w.obj = kNoHit;  // shaded: a ray to trace, or (below) the path's end
       if (TIMED) {
         const uint64_t t = __builtin_amdgcn_s_memtime();
         tp[tp_at<kCtrTicksShade>()] += t - tq;
@@ -3692,7 +3686,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
         for (; k >= 0; k -= 4) {
           float4 a[4];
 #pragma unroll
-          for (int j = 0; j < 4; ++j) a[j] = k - j >= 0 ? rec_load(rec_at(W, k - j)) : make_float4(0, 0, 0, 0);
+          for (int j = 0; j < 4; ++j) a[j] = k - j >= 0 ? rec_load(rec_at(W, rec_row(W, k - j))) : make_float4(0, 0, 0, 0);
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             if (k - j < 0) break;
@@ -3719,14 +3713,54 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
       }
       if (TIMED) tp[tp_at<kCtrTicksFold>()] += __builtin_amdgcn_s_memtime() - tq;
     }
-    }  // (round)
+    }
     if constexpr (PT) {
-      if (!nxt_armed && pool_end < n_paths) {
-        nxt_lane0 = pool_arm(nxt_lane0);
-        nxt_armed = true;
+      const uint64_t live = __ballot(g >= 0);
+      if (tail) {
+        // what continues goes back to its entry; the slots of the paths that ended are free
+        if (g >= 0) pool_put<BS>(ringw + lane_id(), r, rng, g, depth);
+        used = live;
+        if constexpr (SP) walkm = __ballot(g >= 0 && walking != 0);
+        g = -1;
+        walking = 0;
+        // (one wave writes and reads these entries: its LDS operations run in order; the
+        // fence keeps the compiler from moving a later pass's reads above the writes)
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      } else {
+        ++passes;
+        const PathWork W = work();
+        const int n_live = __popcll(live);
+        const uint64_t fr0 = (W.pool_cap >= 64 ? ~0ull : (1ull << max(1, W.pool_cap)) - 1) & ~used;
+        if (live == 0) {
+          head = false;
+        } else if (passes >= 2 && n_live <= kHeadLiveMin && n_live <= (int)__popcll(fr0)) {
+          // promote: the i-th live lane's path to the i-th free slot (wave-uniform masks)
+          int s = 0;
+          uint64_t lv = live, fr = fr0;
+          while (lv) {
+            if (lane_id() == __ffsll((unsigned long long)lv) - 1) s = __ffsll((unsigned long long)fr) - 1;
+            lv &= lv - 1;
+            fr &= fr - 1;
+          }
+          if (g >= 0) {
+            pool_put<BS>(ringw + s, r, rng, g, depth);
+            // its records so far (two at least: depth = passes) into column s
+            const int col = slot - lane_id() + s;
+            if (depth > W.max_depth || slot >= W.lanes) atomicOr(W.err, 2);
+            else
+              for (int j = 0; j < depth; ++j) W.rec[(size_t)j * W.lanes + col] = *rec_at(W, j + W.max_depth);
+          }
+          used |= fr0 & ~fr;
+          g = -1;
+          head = false;
+          // (only this wave's lane s reads entry s and column s, in a later pass: the wave's LDS
+          // operations run in order, and a load follows a store of the same wave to the same
+          // address through the CU's L1; the fence keeps the compiler from reordering them)
+          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        }
       }
-      // (no lane in a path, no chunk waiting for its trace pass, no path left to hand out)
-      if (!fill && pool >= n_paths && __ballot(g >= 0) == 0) break;
+      if (TIMED) tht[tail ? kCtrTicksTail - kCtrTicksHead : 0] += __builtin_amdgcn_s_memtime() - t_pass;
+      tail = false;
     }
   }
   const PathWork W = work();
@@ -3739,6 +3773,8 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
     for (int q = 0; q < kTfWords; ++q) atomicAdd(W.counters + kCtrTicksBeck + q, (unsigned long long)tf[q]);
     for (int q = 0; q < kTzWords; ++q) atomicAdd(W.counters + kCtrTicksCamOnly + q, (unsigned long long)tz[q]);
     for (int q = 0; q < kTptWords; ++q) atomicAdd(W.counters + kCtrTicksPretrace + q, (unsigned long long)tpt[q]);
+    if (PT)
+      for (int q = 0; q < kThtWords; ++q) atomicAdd(W.counters + kCtrTicksHead + q, (unsigned long long)tht[q]);
   }
 
   unsigned long long tot = nrays;

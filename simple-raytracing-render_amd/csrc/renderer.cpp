@@ -407,12 +407,17 @@ struct PathsSetup {
   int deep_tries = 32; // coop_mixture threshold
   int stack_cap = kPathsLdsStack;
   size_t budget = 0;   // sample-window bytes (SRR_WINDOW_MB over the renderers sharing the device)
+  int tail_min = kPathsTailMin;  // chunk-synchronous variants: survivors that trigger a tail pass (SRR_TAIL_MIN)
+  int pool_cap = 64;             // ... and usable survivor slots (SRR_POOL_CAP)
 };
 
 static int paths_prepare(srr_renderer* r, FrameSlot& F, int max_depth, PathsSetup& ps, std::string& err) {
   // persistent lanes and their bounce records
   if (!r->pw_lanes) r->pw_lanes = paths_lanes_per_device(r->view, r->device);
-  const size_t rec_need = (size_t)r->pw_lanes * std::max(1, max_depth);
+  // (a second column set, a head-pass lane's, where a chunk-synchronous variant may be
+  // launched: diffuse only, no media; 16 B x lanes x max_depth more, 210 MB per slot at depth 50)
+  const bool head_cols = r->diffuse_only && !r->view.has_media;
+  const size_t rec_need = (head_cols ? 2 : 1) * (size_t)r->pw_lanes * std::max(1, max_depth);
   if (rec_need > F.rec_cap) {
     (void)hipFree(F.rec);
     F.rec = nullptr;
@@ -443,6 +448,9 @@ static int paths_prepare(srr_renderer* r, FrameSlot& F, int max_depth, PathsSetu
   // wave (kernels.hip coop_mixture); SRR_DEEP_TRIES=0 forces that branch (tests)
   const char* dt_env = getenv("SRR_DEEP_TRIES");
   ps.deep_tries = dt_env ? std::max(0, atoi(dt_env)) : 32;
+  // the survivor pool of the chunk-synchronous variants (tests force the rare flows; read per frame)
+  if (const char* e = getenv("SRR_TAIL_MIN")) ps.tail_min = std::max(1, std::min(64, atoi(e)));
+  if (const char* e = getenv("SRR_POOL_CAP")) ps.pool_cap = std::max(1, std::min(64, atoi(e)));
   ps.stack_cap = kPathsLdsStack;  // kernels.hip kStack
   if (const char* e = getenv("SRR_STACK_CAP")) ps.stack_cap = std::max(1, std::min(kPathsLdsStack, atoi(e)));
   return 0;
@@ -515,6 +523,8 @@ static PathWork paths_work(srr_renderer* r, FrameSlot& F, const srr_params* p, c
   w.gstack_cap = ps.gst_cap;
   w.deep_tries = ps.deep_tries;
   w.walk_q = ps.gst_cap ? ps.walk_q : 0;  // (the save area follows the global stack extension)
+  w.tail_min = ps.tail_min;
+  w.pool_cap = ps.pool_cap;
   return w;
 }
 
@@ -676,6 +686,10 @@ static int paths_finish(srr_renderer* r, FrameSlot& F, const srr_params* p, srr_
                     "shade rounds %.2f per wave-iteration\n",
             ctr[kCtrPretracePasses], ctr[kCtrWaveIters], per(ctr[kCtrTicksPretrace], ctr[kCtrPretracePasses]),
             ctr[kCtrTicksPretrace] / it, ctr[kCtrShadeRounds] / it);
+    // the chunk-synchronous flow's passes (each one wave-iteration: trace, shade, fold and its bookkeeping)
+    fprintf(stderr, "  head passes: %llu, %.0f ticks each, %.1f lanes in a path; tail passes: %llu, %.0f ticks each, %.1f lanes\n",
+            ctr[kCtrHeadPasses], per(ctr[kCtrTicksHead], ctr[kCtrHeadPasses]), per(ctr[kCtrHeadLanes], ctr[kCtrHeadPasses]),
+            ctr[kCtrTailPasses], per(ctr[kCtrTicksTail], ctr[kCtrTailPasses]), per(ctr[kCtrTailLanes], ctr[kCtrTailPasses]));
   }
 #ifdef SRR_SLOW_RAYS
   if (r->pw_slow) {  // diagnostics build: dump the slow world hits' records (one line per lane, JSON)
