@@ -444,6 +444,21 @@ void srr_image_free(unsigned char* pixels);
  * (layouts: tests/golden/README.md).  Needs a GPU. */
 int srr_device_kat(const char* name, int n, int width, float* records);
 
+/* Test infrastructure: the mesh walkers on the `mesh` KAT's records (width 21:
+ * mesh o(3) d(3) tmin tmax is_medium | hit t tri p(3) n(3) u v; layouts and the
+ * fixture scene: tests/golden/README.md).  scene_text's world is a list of `bvh`
+ * objects over triangles, mesh m being its m-th; it is parsed, flattened and
+ * uploaded as for a render, and one kernel runs the walker of `variant` on
+ * every record: 0 the threaded BVH2 walk, 1 the 4-wide walk without pruning,
+ * 2 with pruning (the default walk), 3 the quad-cooperative walk (n is padded to
+ * whole waves of 64 with copies of the last record; a wave in which more than
+ * quad_max lanes enter one mesh falls back to the per-lane walk).  stack_cap is
+ * the LDS stack's depth (1 .. 8), use_gstack adds the per-lane global extension;
+ * a deeper walk ends in the exact BVH2 re-walk.  tri is the triangle's position
+ * in its bvh command.  Outputs are written in place.  Needs a GPU. */
+int srr_device_mesh_kat(const char* scene_text, int variant, int quad_max, int stack_cap, int use_gstack, int n,
+                        int width, float* records);
+
 /* Test infrastructure: one math routine of the device build over n elements
  * (host buffers; one thread per element).  float elements: the wrappers the
  * kernels call, "rsin", "rcos", "rexp", "rlog", "rpow" (x, y), "racos", "rasin",

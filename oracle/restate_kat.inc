@@ -45,9 +45,42 @@ static const Hitable* kat_box(Store& St, V p0, V p1) {
   return l;
 }
 
+// the mesh KAT's scene (tests/golden/kat_mesh.scene, given by oracle_kat_scene): its bvh
+// objects in file order; each triangle's material pointer is its index in its bvh
+// command + 1 (never dereferenced), as in oracle/ref/kat.inc
+static std::unique_ptr<Scene> g_kat_scene;
+static std::vector<const Hitable*> g_kat_meshes;
+static void kat_scene(const std::string& text) {
+  g_kat_meshes.clear();
+  g_kat_scene = build(text);
+  for (const auto& c : srr_text::parse(text))
+    if (c.at(0) == "obj" && c.at(2) == "bvh") {
+      g_kat_meshes.push_back(g_kat_scene->obj.at(c.i(1)));
+      for (long long k = 0; k < c.i(5); ++k) {
+        auto* t = const_cast<Triangle*>(dynamic_cast<const Triangle*>(g_kat_scene->obj.at(c.i(6 + k))));
+        if (!t) throw std::runtime_error("kat mesh: a bvh child is not a triangle");
+        t->mat = (const Material*)(uintptr_t)(k + 1);
+      }
+    }
+}
+
 static int kat_one(const std::string& name, float* r) {
   float* o;
-  if (name == "erf") {
+  if (name == "mesh") {
+    // in: mesh o d tmin tmax is_medium | out: hit t tri p n u v
+    const int mi = (int)r[0];
+    if (mi < 0 || mi >= (int)g_kat_meshes.size()) return -1;
+    Hit h{};
+    const bool hit = g_kat_meshes[mi]->hit(Ray(rd3(r + 1), rd3(r + 4)), r[7], r[8], h, r[9] != 0);
+    o = r + 10;
+    *o++ = hit ? 1.f : 0.f;
+    *o++ = hit ? h.t : 0;
+    *o++ = hit ? (float)((int)(uintptr_t)h.mat - 1) : -1.f;
+    wr3(o, hit ? h.p : V(0.f));
+    wr3(o, hit ? h.normal : V(0.f));
+    *o++ = hit ? h.u : 0;
+    *o++ = hit ? h.v : 0;
+  } else if (name == "erf") {
     o = r + 1;
     *o++ = Erf(r[0]);
     *o++ = ErfInv(r[0]);
@@ -381,6 +414,17 @@ static int kat_one(const std::string& name, float* r) {
   return 0;
 }
 }  // namespace orc
+
+// the scene text the `mesh` KAT replays over (call before oracle_kat("mesh", ...))
+extern "C" int oracle_kat_scene(const char* text) {
+  try {
+    orc::kat_scene(text);
+  } catch (const std::exception& e) {
+    orc::g_err = e.what();
+    return -1;
+  }
+  return 0;
+}
 
 extern "C" int oracle_kat(const char* name, int n, int width, float* records) {
   std::string nm(name);

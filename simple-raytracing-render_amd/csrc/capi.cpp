@@ -1171,6 +1171,82 @@ int srr_device_kat(const char* name, int n, int width, float* records) {
   return rc;
 }
 
+int srr_device_mesh_kat(const char* scene_text, int variant, int quad_max, int stack_cap, int use_gstack, int n,
+                        int width, float* records) {
+  // every argument is checked before the first HIP call
+  if (!scene_text || !records || n <= 0 || n > 1 << 20 || width != kMeshKatWidth)
+    return fail(SRR_EINVAL, "bad mesh KAT arguments");
+  if (variant < kMeshKatBvh2 || variant > kMeshKatQuad) return fail(SRR_EINVAL, "no such mesh KAT variant");
+  if (stack_cap < 1 || stack_cap > paths_kernel_stack()) return fail(SRR_EINVAL, "mesh KAT: stack_cap out of range");
+  Scene sc;
+  std::string err;
+  int rc = scene_from_text(scene_text, sc, err);
+  if (rc < 0) return fail(rc, err);
+  Flat f;
+  if ((rc = flatten(sc, f, err)) < 0) return fail(rc, err);
+  // the world list's objects are the meshes, in order: mesh m of a record is world object m
+  if (!sc.valid_obj(sc.world) || sc.obj[sc.world].kind != H_LIST || (int)sc.obj[sc.world].kids.size() != f.n_world)
+    return fail(SRR_EINVAL, "mesh KAT: the world must be a list of bvh objects");
+  std::vector<int32_t> mesh_obj(f.n_world), tri_file(f.tri_shade.size(), -1);
+  for (int k = 0; k < f.n_world; ++k) {
+    const int h = sc.obj[sc.world].kids[k];
+    if (sc.obj[h].kind != H_BVH || f.objs[k].kind != OBJ_MESH || f.objs[k].xf_count != 0)
+      return fail(SRR_EINVAL, "mesh KAT: a world object is not a bare triangle mesh");
+    const HBvh& B = sc.bvhs[sc.obj[h].bvh];
+    const DMesh& m = f.meshes[f.objs[k].idx];
+    if (m.n_tris != (int)B.leaves.size() || m.tri_off < 0 || (size_t)m.tri_off + m.n_tris > tri_file.size())
+      return fail(SRR_EINVAL, "mesh KAT: mesh tables do not match the bvh");
+    std::map<int, int> pos;
+    for (size_t q = 0; q < B.input.size(); ++q) pos[B.input[q]] = (int)q;
+    for (size_t i = 0; i < B.leaves.size(); ++i) tri_file[m.tri_off + i] = pos.at(B.leaves[i]);
+    mesh_obj[k] = k;
+  }
+  for (int q = 0; q < n; ++q) {
+    const float mi = records[(size_t)q * width];
+    if (!(mi >= 0 && mi < (float)f.n_world && mi == (float)(int)mi)) return fail(SRR_EINVAL, "mesh KAT: a record names no mesh");
+  }
+  // the quad walk serves whole waves: pad with copies of the last record
+  const int n_run = variant == kMeshKatQuad ? (n + 63) / 64 * 64 : n;
+  std::vector<float> rec((size_t)n_run * width);
+  std::memcpy(rec.data(), records, (size_t)n * width * sizeof(float));
+  for (int q = n; q < n_run; ++q) std::memcpy(&rec[(size_t)q * width], &rec[(size_t)(n - 1) * width], width * sizeof(float));
+  srr_renderer* r = nullptr;  // uploads the tables exactly as a render does
+  if ((rc = renderer_create_flat(f, 0, &r, err)) < 0) return fail(rc, err);
+  std::unique_ptr<srr_renderer> keep(r);
+  SceneView S = r->view;
+  S.quad_max = quad_max;
+  MeshKatArgs A{};
+  A.n = n_run;
+  A.width = width;
+  A.stack_cap = stack_cap;
+  A.gst_cap = use_gstack ? kPathsGlobalStack : 0;
+  A.lanes = (n_run + 255) / 256 * 256;
+  float* d_rec = nullptr;
+  int2* d_gst = nullptr;
+  int32_t* d_mesh_obj = nullptr;
+  int32_t* d_tri_file = nullptr;
+  const size_t rb = rec.size() * sizeof(float);
+  if (hipMalloc((void**)&d_rec, rb) != hipSuccess ||
+      hipMalloc((void**)&d_mesh_obj, mesh_obj.size() * 4) != hipSuccess ||
+      hipMalloc((void**)&d_tri_file, tri_file.size() * 4) != hipSuccess ||
+      (use_gstack && hipMalloc((void**)&d_gst, (size_t)kPathsGlobalStack * A.lanes * sizeof(int2)) != hipSuccess))
+    rc = fail(SRR_ENOMEM, "device allocation failed");
+  if (!rc && (hipMemcpy(d_rec, rec.data(), rb, hipMemcpyHostToDevice) != hipSuccess ||
+              hipMemcpy(d_mesh_obj, mesh_obj.data(), mesh_obj.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+              hipMemcpy(d_tri_file, tri_file.data(), tri_file.size() * 4, hipMemcpyHostToDevice) != hipSuccess))
+    rc = fail(SRR_EIO, "copy to device failed");
+  A.rec = d_rec;
+  A.gst = d_gst;
+  A.mesh_obj = d_mesh_obj;
+  A.tri_file = d_tri_file;
+  if (!rc && launch_mesh_kat(S, variant, A) < 0) rc = fail(SRR_EIO, "mesh KAT kernel launch failed");
+  if (!rc && (hipDeviceSynchronize() != hipSuccess ||
+              hipMemcpy(records, d_rec, (size_t)n * width * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess))
+    rc = fail(SRR_EIO, "mesh KAT kernel failed");
+  for (void* p : {(void*)d_rec, (void*)d_gst, (void*)d_mesh_obj, (void*)d_tri_file}) (void)hipFree(p);
+  return rc;
+}
+
 int srr_device_libm(const char* fn, int64_t n, const void* x, const void* y, void* out0, void* out1) {
   // every argument is checked before the first HIP call, so a refusal needs no GPU
   // (tests/test_device_libm.py test_unknown_names_are_refused runs without one)

@@ -296,6 +296,25 @@ struct KatTables {
 };
 int launch_kat(int kind, int n, int w, float* d_rec, const float* d_aux, const DStandaloneTri* d_tris,
                const KatTables& kt);
+// the mesh-walk KAT (srr_device_mesh_kat, kernels.hip k_mesh_kat): every walker the release
+// build's basic_hit / list_hit reach -- mesh_hit<false> (SRR_TRAVERSAL=bvh2, and a medium's
+// boundary), mesh_hit4<false> (SRR_TRAVERSAL=bvh4), mesh_hit4<true> (the default) and
+// mesh_hit4_quad<true> (SRR_QUAD=1; the path kernel always prunes) -- with the
+// kTraceBlock stack stride (the 1,024-lane stride would need a second block shape)
+enum MeshKatVariant : int { kMeshKatBvh2 = 0, kMeshKatBvh4 = 1, kMeshKatBvh4Prune = 2, kMeshKatQuad = 3 };
+constexpr int kMeshKatWidth = 21;  // mesh o(3) d(3) tmin tmax is_medium | hit t tri p(3) n(3) u v
+struct MeshKatArgs {
+  int n, width;             // records (a multiple of 64 for the quad variant)
+  float* rec;               // device records, outputs written in place
+  int stack_cap;            // TraceCtx::st_cap, 1 .. kStack
+  int2* gst;                // TraceCtx::gst: [gst_cap][lanes], or nullptr with gst_cap 0
+  int gst_cap;
+  int lanes;                // TraceCtx::gst_stride: at least the launched lanes
+  const int32_t* mesh_obj;  // [mesh of the record] -> its object row (an OBJ_MESH)
+  const int32_t* tri_file;  // [DFS triangle index, over all meshes] -> index in its bvh command
+};
+// 0, -1 (bad arguments, nothing launched) or -5 (launch failed); SceneView::quad_max decides the quad variant's route
+int launch_mesh_kat(const SceneView& S, int variant, const MeshKatArgs& A);
 // device libm sweeps (srr_device_libm): routine kLibmFns[fn] over n elements, one per
 // thread; device pointers (d_y / d_out1 unused unless n_in / n_out is 2).  The switches
 // of kernels.hip k_libm_f32 / k_libm_f64 go by LibmId, and row i of the table is id i

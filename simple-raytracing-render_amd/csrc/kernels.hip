@@ -316,6 +316,13 @@ struct TraceCtx {
 // entry -- far beyond the few-ulp error of both computations.  (Pruning on the
 // tmin-clipped entry, as round 1 did, lost the nearer self-hits of rays leaving
 // the mesh's own surface: 1,115 world rays of the 512x512x1024 C2 frame.)
+// A medium ray (is_medium) is never pruned by its best hit: triangle::hit's back-face
+// retest (triangle.h:124-129) takes its edges from p1 but T from p0, so it accepts
+// points of the triangle (p0, 2 p0 - p1, p0 + p2 - p1), which lies in the same plane
+// OUTSIDE the leaf's box -- such a hit can be nearer than its box's entry, and a
+// bound taken from another hit would skip it (the mesh KAT's medium records: a
+// teapot wall's retest hit at t = 542.1 lost to a front hit at 574.6).  No caller of
+// the 4-wide walks passes is_medium today (a boundary's meshes take mesh_hit).
 constexpr float kPruneSlack = 1.0625f;
 
 // a value the compiler must keep in a VGPR (see TraceCtx::walk_thr)
@@ -453,7 +460,7 @@ SRR_D bool mesh_hit4(const SceneView& S, const DMesh& m, const Ray& r, float tmi
   const V3 inv = v3(1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z);
   const float len = length(r.d);
   const V3 dir = r.d / len;
-  const float to_param = kPruneSlack / len;
+  const float to_param = is_medium ? INFINITY : kPruneSlack / len;  // (a medium ray never shrinks its bound: kPruneSlack)
   bool found = false;
   float best_t = 0;
   int best_i = -1;
@@ -886,7 +893,7 @@ SRR_D bool mesh_hit4_quad(const SceneView& S, const DMesh& m, const Ray& r, floa
   const int lane = __lane_id(), q = lane >> 2, c = lane & 3;
   const float len = length(r.d);
   const V3 dir = r.d / len;
-  const float to_param = kPruneSlack / len;
+  const float to_param = is_medium ? INFINITY : kPruneSlack / len;  // (a medium ray never shrinks its bound: kPruneSlack)
   // quad lane 0's stacks serve its quad (entry e of lane l - c is cx.st_*[e * STRIDE - c])
   const int gslot = cx.slot - c;
   bool found_me = false, redo_me = false;
@@ -4512,6 +4519,74 @@ __global__ void k_kat(int kind, int n, int w, float* rec, const float* aux, cons
     for (int k = 0; k < out_n; ++k) r[out_at + k] = out[k];
 }
 
+// Test infrastructure (srr_device_mesh_kat): the mesh walkers on the reference's `mesh`
+// KAT records (tests/golden/README.md), one record per lane of a kTraceBlock block with
+// the LDS stacks of k_trace / k_probe.  in: mesh o d tmin tmax is_medium | out: hit t
+// tri p n u v (zeros and tri = -1 on a miss); tri is mapped from the walker's DFS
+// index to the file's order through A.tri_file.
+//
+// The walkers' wave-cooperative parts (the NaN-bound scan, the quads) read the mesh, and
+// the scan is_medium, as wave-uniform values, as every caller in the frames has them (the
+// object under test and an argument fixed per call chain): the wave takes its records'
+// (mesh, is_medium) pairs one after the other.  The per-lane variants call the walker from the
+// lanes of that pair alone (a partial wave, as behind a world list's dispatch); the quad
+// variant calls it from every lane, the other lanes with an empty range [0, -1] that
+// misses the root box, so the wave stays whole and the quads run.
+template <int VARIANT>
+__global__ void __launch_bounds__(kTraceBlock) k_mesh_kat(SceneView S, MeshKatArgs A) {
+  __shared__ int s_node[kStack * kTraceBlock];
+  __shared__ float s_t[kStack * kTraceBlock];
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  TraceCtx cx{nullptr, to_lds(s_node + threadIdx.x), to_lds(s_t + threadIdx.x)};
+  cx.st_cap = A.stack_cap;
+  cx.gst = A.gst;
+  cx.gst_cap = A.gst_cap;
+  cx.gst_stride = A.lanes;
+  cx.slot = q;
+  if (q >= A.n) return;
+  float* r = A.rec + (size_t)q * A.width;
+  const int mesh = (int)r[0];
+  const Ray ray{kat3(r + 1), kat3(r + 4), 0.0f};
+  const float tmin = r[7], tmax = r[8];
+  const bool med = r[9] != 0;
+  bool hit = false;
+  MeshHit mh{0.f, -1};
+  uint64_t todo = __ballot(true);
+  const int key = 2 * mesh + (med ? 1 : 0);
+  while (todo) {  // wave-uniform: the (mesh, is_medium) pairs of the wave's records, one at a time
+    const int kk = __shfl(key, __ffsll((unsigned long long)todo) - 1);
+    const bool mine = key == kk;
+    const int mm = kk >> 1;
+    todo &= ~__ballot(mine);
+    const DMesh m = S.meshes[S.objs[A.mesh_obj[mm]].idx];
+    if constexpr (VARIANT == kMeshKatQuad) {
+      const Ray rr = mine ? ray : Ray{v3(0.f), v3(1.f, 1.f, 1.f), 0.0f};
+      MeshHit h2{0.f, -1};
+      const bool h = mesh_hit4_quad<true>(S, m, rr, mine ? tmin : 0.0f, mine ? tmax : -1.0f, (kk & 1) != 0, h2, cx);
+      if (mine) { hit = h; mh = h2; }
+    } else if (mine) {
+      if constexpr (VARIANT == kMeshKatBvh2) hit = mesh_hit<false>(S, m, ray, tmin, tmax, med, mh, nullptr);
+      else hit = mesh_hit4<VARIANT == kMeshKatBvh4Prune>(S, m, ray, tmin, tmax, med, mh, cx);
+    }
+  }
+  float out[11];
+  for (int k = 0; k < 11; ++k) out[k] = 0;
+  out[2] = -1.f;
+  if (hit) {
+    HitRec hr;
+    hr.u = hr.v = 0;
+    prim_record<0>(S, S.objs[A.mesh_obj[mesh]], ray, mh.t, mh.tri, hr);
+    out[0] = 1.f;
+    out[1] = mh.t;
+    out[2] = (float)A.tri_file[mh.tri];
+    kat_put3(out + 3, hr.p);
+    kat_put3(out + 6, hr.n);
+    out[9] = hr.u;
+    out[10] = hr.v;
+  }
+  for (int k = 0; k < 11; ++k) r[10 + k] = out[k];
+}
+
 // Test infrastructure (srr_device_libm): one libm routine of the device build over
 // an array, one element per thread.  fn is a LibmId (kernels.h).  The f32 entries are
 // the devmath.h wrappers the kernels call; the f64 ones the restatement of glibc's
@@ -4879,6 +4954,23 @@ int launch_kat(int kind, int n, int w, float* d_rec, const float* d_aux, const D
   // a thread per record; the scene KATs a wave per record
   const int blocks = kind >= dev::KAT_SPHERE ? n : (n + 63) / 64;
   hipLaunchKernelGGL(dev::k_kat, dim3(blocks), dim3(64), 0, 0, kind, n, w, d_rec, d_aux, d_tris, kt);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+int launch_mesh_kat(const SceneView& S, int variant, const MeshKatArgs& A) {
+  if (A.n <= 0 || A.width != kMeshKatWidth || A.stack_cap < 1 || A.stack_cap > dev::kStack || A.gst_cap < 0 ||
+      (A.gst_cap > 0 && !A.gst) || (variant == kMeshKatQuad && A.n % 64 != 0))
+    return -1;
+  const int blocks = (A.n + dev::kTraceBlock - 1) / dev::kTraceBlock;
+  if (A.lanes < blocks * dev::kTraceBlock) return -1;  // the global stack extension's stride covers every lane
+  const dim3 g(blocks), b(dev::kTraceBlock);
+  switch (variant) {
+    case kMeshKatBvh2: hipLaunchKernelGGL((dev::k_mesh_kat<kMeshKatBvh2>), g, b, 0, 0, S, A); break;
+    case kMeshKatBvh4: hipLaunchKernelGGL((dev::k_mesh_kat<kMeshKatBvh4>), g, b, 0, 0, S, A); break;
+    case kMeshKatBvh4Prune: hipLaunchKernelGGL((dev::k_mesh_kat<kMeshKatBvh4Prune>), g, b, 0, 0, S, A); break;
+    case kMeshKatQuad: hipLaunchKernelGGL((dev::k_mesh_kat<kMeshKatQuad>), g, b, 0, 0, S, A); break;
+    default: return -1;
+  }
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

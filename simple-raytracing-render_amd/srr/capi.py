@@ -403,6 +403,22 @@ def scene_digest(text: str) -> str:
     return f"{d.value:016x}"
 
 
+MESH_KAT_VARIANTS = {"bvh2": 0, "bvh4": 1, "bvh4prune": 2, "quad": 3}
+
+
+def device_mesh_kat(scene_text: str, rec: np.ndarray, variant: str, quad_max: int = 64, stack_cap: int = 8,
+                    use_gstack: bool = True) -> np.ndarray:
+    """srr_device_mesh_kat (test infrastructure): the `mesh` KAT's records with the
+    outputs of the walker `variant` (MESH_KAT_VARIANTS) over scene_text's meshes."""
+    L = lib()
+    L.srr_device_mesh_kat.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    out = np.ascontiguousarray(rec, np.float32).copy()
+    _check(L.srr_device_mesh_kat(scene_text.encode(), MESH_KAT_VARIANTS[variant], quad_max, stack_cap,
+                                 1 if use_gstack else 0, out.shape[0], out.shape[1], _ptr(out)))
+    return out
+
+
 def write_ppm(path: str, nx: int, ny: int, img8: np.ndarray) -> None:
     img8 = np.ascontiguousarray(img8, np.uint8)
     _check(lib().srr_write_ppm(path.encode(), nx, ny, _ptr(img8)))

@@ -47,7 +47,9 @@ KATS = [("erf", 512), ("beckmann11", 512), ("beckmann_dist", 512), ("beckmann_pd
         ("camera", 256), ("lights", 256), ("light_list", 256), ("merl", 2048), ("merl_same", 4096),
         # scene KATs: a constructed half of edge blocks and a pseudo-random half (README.md)
         ("sphere", 1024), ("moving_sphere", 1024), ("rect", 1024), ("box", 1024), ("xform", 1024), ("medium", 1024),
-        ("isotropic", 1024), ("texture_checker", 1024), ("texture_noise", 1024), ("texture_image", 1024)]
+        ("isotropic", 1024), ("texture_checker", 1024), ("texture_noise", 1024), ("texture_image", 1024),
+        # the mesh walk: bvh_node::hit over the ten meshes of kat_mesh.scene (README.md)
+        ("mesh", 1024)]
 
 
 # The MERL KATs' out == in records are decided by the last-ulp rounding of glibc's
@@ -77,6 +79,100 @@ def run(*args):
     return out.stdout
 
 
+MESH_SCENE = os.path.join(HERE, "kat_mesh.scene")
+N_KAT_MESHES = 10
+
+
+def mesh_scene_text():
+    """The ten fixture meshes of the `mesh` KAT (README.md): `bvh` objects over
+    triangles, vertices on the quarter-integer lattice except for the two teapots."""
+    import math
+    import tempfile
+
+    import numpy as np
+
+    def h(i, j):  # height of the 8 x 8 field's vertex (i, j): quarters in [0, 1.75]
+        return 0.25 * (((i * 7 + j * 13 + i * j * 5) ^ (i + 3 * j)) % 8)
+
+    def grid(z):
+        tris = []
+        for j in range(8):
+            for i in range(8):
+                a, b, c, d = ((i, j), (i + 1, j), (i + 1, j + 1), (i, j + 1))
+                v = lambda p: (float(p[0]), float(p[1]), float(z(*p)))  # noqa: E731
+                tris += [(v(a), v(b), v(c)), (v(a), v(c), v(d))]
+        return tris
+
+    def teapot(scale, off):
+        with tempfile.TemporaryDirectory() as tmp:
+            path = os.path.join(tmp, "t.f32")
+            run("teapot", scale, 3, path)
+            p = np.fromfile(path, np.float32).reshape(-1, 12)[:, :9].reshape(-1, 3, 3)
+        p = (p + np.float32(off)).astype(np.float32)
+        return [tuple(tuple(float(x) for x in vtx) for vtx in t) for t in p]
+
+    field = grid(h)
+    fan = []
+    for k in range(96):  # rim points of radius about 64, snapped to the lattice, heights in [-2, 2]
+        rim = [(round(4 * 64 * math.cos(2 * math.pi * q / 96)) / 4, round(4 * 64 * math.sin(2 * math.pi * q / 96)) / 4,
+                0.25 * ((q * 5) % 17 - 8)) for q in (k, (k + 1) % 96)]
+        fan.append(((0.0, 0.0, 0.0), rim[0], rim[1]))
+    zero_area = [((float(k), 1.0, 0.5), (float(k), 1.0, 0.5), (k + 1.0, 2.0, 0.75)) if k % 2 == 0 else
+                 ((float(k), 0.0, 0.25), (k + 1.0, 1.0, 0.5), (k + 2.0, 2.0, 0.75)) for k in range(8)]
+    meshes = [
+        [((0.0, 0.0, 0.0), (4.0, 0.0, 0.5), (0.0, 4.0, 1.0))],  # (tilted: a flat triangle's box is never entered)
+        [((0.0, 0.0, 0.0), (4.0, 0.0, 0.0), (0.0, 4.0, 0.0)), ((4.0, 0.0, 0.0), (4.0, 4.0, 1.0), (0.0, 4.0, 0.0))],
+        [((0.0, 0.0, 0.0), (4.0, 0.0, 0.0), (0.0, 4.0, 0.0)), ((4.0, 0.0, 0.0), (4.0, 4.0, 1.0), (0.0, 4.0, 0.0)),
+         ((4.0, 0.0, 0.0), (8.0, 0.0, 0.5), (4.0, 4.0, 1.0))],
+        [((0.0, 0.0, 0.0), (4.0, 0.0, 0.0), (0.0, 4.0, 0.0)), ((4.0, 0.0, 0.0), (4.0, 4.0, 1.0), (0.0, 4.0, 0.0)),
+         ((4.0, 0.0, 0.0), (8.0, 0.0, 0.5), (4.0, 4.0, 1.0)), ((8.0, 0.0, 0.5), (8.0, 4.0, 0.25), (4.0, 4.0, 1.0)),
+         ((0.0, 4.0, 0.0), (4.0, 4.0, 1.0), (2.0, 8.0, 0.75))],
+        field,
+        grid(lambda i, j: 2.0),
+        field[:32] + field[:32] + zero_area,
+        fan,
+        teapot(1e-3, 1000.0),
+        teapot(60.0, 0.0),
+    ]
+    f32 = lambda x: repr(float(np.float32(x)))  # noqa: E731  (shortest decimal that reads back as the float32)
+    out = ["srr_scene 1", "# the `mesh` KAT's fixture meshes (README.md): obj 100000 + m is mesh m",
+           "tex 0 const 0.5 0.5 0.5", "mat 0 lambertian 0"]
+    nid = 0
+    roots = []
+    for m, tris in enumerate(meshes):
+        ids = []
+        for t in tris:
+            pts = " ".join(f32(x) for vtx in t for x in vtx)
+            if m < 8:  # texture coordinates (0,0) (1,0) (0,1): the record's u, v are the barycentrics
+                out.append(f"obj {nid} triangle_uv {pts} 0 0.0 0.0 0.0 1.0 0.0 0.0 0.0 1.0 0.0")
+            else:
+                out.append(f"obj {nid} triangle {pts} 0")
+            ids.append(nid)
+            nid += 1
+        out.append(f"obj {100000 + m} bvh 0.0 1.0 {len(ids)} " + " ".join(map(str, ids)))
+        roots.append(100000 + m)
+    out.append(f"obj 200000 list {len(roots)} " + " ".join(map(str, roots)))
+    out += ["world 200000", "camera 0.0 0.0 -100.0 0.0 0.0 0.0 0.0 1.0 0.0 40.0 1.0 0.0 10.0 0.0 1.0",
+            "obj 200001 xz_rect 0.0 1.0 0.0 1.0 500.0 -1", "obj 200002 list 1 200001", "lights 200002"]
+    return "\n".join(out) + "\n"
+
+
+def make_mesh_kat(n):
+    """kat_mesh.scene, the reference's records over it, and its topology dumps."""
+    with open(MESH_SCENE, "w") as f:
+        f.write(mesh_scene_text())
+    run("kat", "mesh", n, 1234567, os.path.join(HERE, "kat_mesh.bin"), MESH_SCENE)
+    dumps = []
+    for m in range(N_KAT_MESHES):
+        tmp = os.path.join(HERE, f".bvh_kat_mesh_{m}.tmp")
+        run("bvh", MESH_SCENE, 100000 + m, tmp)
+        with open(tmp) as f:
+            dumps.append(f"mesh {m}\n" + f.read())
+        os.remove(tmp)
+    with open(os.path.join(HERE, "bvh_kat_mesh.txt"), "w") as f:
+        f.write("".join(dumps))
+
+
 def only_kats(names):
     """Generate the named KATs alone and add their entries to golden.json."""
     sizes = dict(KATS)
@@ -87,7 +183,10 @@ def only_kats(names):
     with open(path) as f:
         meta = json.load(f)
     for name in names:
-        run("kat", name, sizes[name], 1234567, os.path.join(HERE, f"kat_{name}.bin"))
+        if name == "mesh":
+            make_mesh_kat(sizes[name])
+        else:
+            run("kat", name, sizes[name], 1234567, os.path.join(HERE, f"kat_{name}.bin"))
         meta["kats"][name] = sizes[name]
     with open(path, "w") as f:
         json.dump(meta, f, indent=1, sort_keys=True)
@@ -115,7 +214,10 @@ def main():
             print(f"kat_{name}.bin NOT regenerated: this host's libm {libm} is not the pinned {MERL_LIBM_PIN}")
             meta["kats"][name] = n
             continue
-        run("kat", name, n, 1234567, os.path.join(HERE, f"kat_{name}.bin"))
+        if name == "mesh":
+            make_mesh_kat(n)
+        else:
+            run("kat", name, n, 1234567, os.path.join(HERE, f"kat_{name}.bin"))
         meta["kats"][name] = n
     run("teapot", 60.0, 10, os.path.join(HERE, "teapot_s60_d10.f32"))
     for n in (64, 1024, 4096):

@@ -1,18 +1,23 @@
 """Edge classes of the scene KAT records (tests/golden/kat_{sphere, moving_sphere,
 rect, box, xform, medium, isotropic, texture_checker, texture_noise,
-texture_image}.bin), worked out from the committed records alone: the inputs,
-the reference's outputs and float32 arithmetic in numpy.  No device code and no
-restatement code is involved.  Layouts: tests/golden/README.md.
+texture_image, mesh}.bin), worked out from the committed records alone: the inputs,
+the reference's outputs and float32 arithmetic in numpy (the mesh KAT also reads its
+committed scene text, kat_mesh.scene, and places lattice points in exact float64).
+No device code and no restatement code is involved.  Layouts: tests/golden/README.md.
 
 classify(name, rec) -> {class name: boolean mask over the records}; a record may
 be in several classes.  HIT[name] is the column of the record's hit flag.
 """
+import functools
+import os
+
 import numpy as np
 
 F = np.float32
-HIT = {"sphere": 12, "moving_sphere": 18, "rect": 15, "box": 14, "xform": 27, "medium": 18}
+HIT = {"sphere": 12, "moving_sphere": 18, "rect": 15, "box": 14, "xform": 27, "medium": 18, "mesh": 10}
 NEW_KATS = ("sphere", "moving_sphere", "rect", "box", "xform", "medium", "isotropic", "texture_checker",
-            "texture_noise", "texture_image")
+            "texture_noise", "texture_image", "mesh")
+MESH_SCENE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kat_mesh.scene")
 
 
 def _dot(a, b):  # vec3.h dot: ((x x' + y y') + z z') in float32
@@ -280,7 +285,187 @@ def _texture_image(rec):
     }
 
 
-_CLASSIFIERS = {"sphere": _sphere, "moving_sphere": _moving_sphere, "rect": _rect, "box": _box, "xform": _xform,
+@functools.lru_cache(maxsize=None)
+def mesh_scene():
+    """The meshes of kat_mesh.scene: per `bvh` command, its triangles in the
+    command's order, float32 [n][3 vertices][3]."""
+    tri, meshes = {}, []
+    with open(MESH_SCENE) as f:
+        for line in f:
+            w = line.split("#")[0].split()
+            if len(w) > 2 and w[0] == "obj" and w[2] in ("triangle", "triangle_uv"):
+                tri[int(w[1])] = np.array([float(x) for x in w[3:12]], F).reshape(3, 3)
+            elif len(w) > 2 and w[0] == "obj" and w[2] == "bvh":
+                meshes.append(np.stack([tri[int(k)] for k in w[6:6 + int(w[5])]]))
+    return meshes
+
+
+def _root_slab(lo, hi, o, d, tmin, tmax, shift=None):
+    """aabb::hit (aabb.h:33-49) in float32 on the box [lo, hi], per record."""
+    o = o.copy()
+    if shift is not None:  # (axis, ulps): the origin moved by that many ulps on the axis
+        a, k = shift
+        for _ in range(abs(k)):
+            o[:, a] = np.nextafter(o[:, a], F(np.inf if k > 0 else -np.inf))
+    ok = np.ones(len(o), bool)
+    tmin, tmax = tmin.copy(), tmax.copy()
+    with np.errstate(all="ignore"):
+        for a in range(3):
+            inv = F(1) / d[:, a]
+            t0, t1 = (lo[a] - o[:, a]) * inv, (hi[a] - o[:, a]) * inv
+            sw = inv < 0
+            t0, t1 = np.where(sw, t1, t0), np.where(sw, t0, t1)
+            tmin = np.where(t0 > tmin, t0, tmin)
+            tmax = np.where(t1 < tmax, t1, tmax)
+            ok &= ~(tmax <= tmin)
+    return ok, tmin
+
+
+def _mesh_lines(rec):
+    """Per record, against every triangle of its mesh, in float64 on the line o + t d
+    (exact for the lattice meshes and lattice rays): Moller-Trumbore numerators with
+    det > 0 -- nu, nv, det, the parameter t -- as lists of [records of mesh m][triangles]."""
+    out = {}
+    mesh = rec[:, 0].astype(int)
+    for m, tris in enumerate(mesh_scene()):
+        idx = np.flatnonzero(mesh == m)
+        if not len(idx):
+            continue
+        T3 = tris.astype(np.float64)
+        p0, e1, e2 = T3[:, 0], T3[:, 1] - T3[:, 0], T3[:, 2] - T3[:, 0]
+        o, d = rec[idx, 1:4].astype(np.float64)[:, None, :], rec[idx, 4:7].astype(np.float64)[:, None, :]
+        with np.errstate(all="ignore"):
+            P = np.cross(d, e2[None])
+            det = (e1[None] * P).sum(-1)
+            sg = np.where(det < 0, -1.0, 1.0)
+            Tv = o - p0[None]
+            nu = (Tv * P).sum(-1) * sg
+            Q = np.cross(Tv, e1[None])
+            nv = (d * Q).sum(-1) * sg
+            nt = (e2[None] * Q).sum(-1) * sg
+            det = det * sg
+            t = nt / det
+            nrm = np.cross(e1, e2)
+            sin = np.abs((d * nrm[None]).sum(-1)) / (np.linalg.norm(d, axis=-1) * np.linalg.norm(nrm, axis=-1)[None])
+        out[m] = dict(idx=idx, nu=nu, nv=nv, det=det, t=t, sin=sin, facing=(d * nrm[None]).sum(-1))
+    return out
+
+
+def mesh_front_hit_sure(rec):
+    """Records whose winning triangle (column tri) the line meets well inside
+    (barycentrics 1e-4 from every edge, in float64): the front test of triangle::hit
+    accepted it, so the record's p, n, u, v are the front test's."""
+    sure = np.zeros(len(rec), bool)
+    tri = rec[:, 12].astype(int)
+    for m, L in _mesh_lines(rec).items():
+        i = L["idx"]
+        k = np.clip(tri[i], 0, L["nu"].shape[1] - 1)
+        r = np.arange(len(i))
+        with np.errstate(all="ignore"):
+            u, v = L["nu"][r, k] / L["det"][r, k], L["nv"][r, k] / L["det"][r, k]
+            sure[i] = (tri[i] >= 0) & (u > 1e-4) & (v > 1e-4) & (u + v < 1 - 1e-4)
+    return sure
+
+
+def _mesh(rec):
+    n = len(rec)
+    mesh, o, d, tmin, tmax = rec[:, 0].astype(int), rec[:, 1:4], rec[:, 4:7], rec[:, 7], rec[:, 8]
+    med, hit, tri, p = rec[:, 9] != 0, rec[:, 10] == 1, rec[:, 12].astype(int), rec[:, 13:16]
+    fin_d = np.isfinite(d).all(axis=1)
+    z = lambda: np.zeros(n, bool)  # noqa: E731
+    shared, apex, first_t, second_t, graze, back, retest = z(), z(), np.full(n, np.inf), np.full(n, np.inf), z(), z(), z()
+    in_plane, root_miss, root_near, at_entry = z(), z(), z(), z()
+    zero = (d == 0) & fin_d[:, None]
+    sure = mesh_front_hit_sure(rec)
+    for m, L in _mesh_lines(rec).items():
+        i, nu, nv, det, t = L["idx"], L["nu"], L["nv"], L["det"], L["t"]
+        with np.errstate(all="ignore"):
+            closed = (det > 0) & (nu >= 0) & (nv >= 0) & (nu + nv <= det) & (t > 0)
+            edge = closed & ((nu == 0) | (nv == 0) | (nu + nv == det))
+            strict = (det > 0) & (nu > 0) & (nv > 0) & (nu + nv < det) & (t > 0)
+        te = np.where(edge, t, np.inf)
+        tie = (edge & (te == te.min(axis=1, keepdims=True))).sum(axis=1)
+        if m != 6:  # (mesh 6 lists its triangles twice: a tie there is the duplicates' class)
+            shared[i] = (tie >= 2) & (tie < 90)
+        apex[i] = tie >= 90
+        ts = np.sort(np.where(strict, t, np.inf), axis=1)
+        first_t[i] = ts[:, 0]
+        if ts.shape[1] > 1:
+            second_t[i] = ts[:, 1]
+        r = np.arange(len(i))
+        k = np.clip(tri[i], 0, nu.shape[1] - 1)
+        graze[i] = hit[i] & (L["sin"][r, k] < 1e-3)
+        back[i] = med[i] & hit[i] & (L["facing"][r, k] > 0)
+        retest[i] = med[i] & hit[i] & ~sure[i] & np.isfinite(rec[i, 11])
+        tris = mesh_scene()[m]
+        lo_t, hi_t = tris.min(axis=1), tris.max(axis=1)  # each triangle's box
+        lo, hi = lo_t.min(axis=0), hi_t.max(axis=0)      # the root's
+        for a in range(3):
+            planes = np.unique(np.concatenate([lo_t[:, a], hi_t[:, a]]))
+            in_plane[i] |= zero[i, a] & np.isin(o[i, a], planes)
+        ok, entry = _root_slab(lo, hi, o[i], d[i], tmin[i], tmax[i])
+        fin = fin_d[i] & ~np.isnan(tmax[i])
+        root_miss[i] = fin & ~ok
+        at_entry[i] = fin & (tmax[i] == entry) & (entry > tmin[i])
+        near = np.zeros(len(i), bool)
+        for a in range(3):
+            for k2 in (-4, -3, -2, -1, 1, 2, 3, 4):
+                near |= _root_slab(lo, hi, o[i], d[i], tmin[i], tmax[i], shift=(a, k2))[0]
+        root_near[i] = fin & ~ok & near
+    seen, on_surface = {}, z()
+    for q in range(n):
+        on_surface[q] = seen.get((mesh[q], o[q].tobytes()), False)
+        if hit[q] and np.isfinite(p[q]).all():
+            seen[(mesh[q], p[q].tobytes())] = True
+    with np.errstate(all="ignore"):
+        length = np.sqrt((d.astype(np.float64) ** 2).sum(axis=1))
+    big = F(np.finfo(np.float32).max)
+    nan_bound = np.isnan(tmax)
+    out = {
+        "through a shared edge or vertex": shared,
+        "through a shared edge or vertex, hit": shared & hit,
+        "duplicated triangle, hit": (mesh == 6) & hit & (tri < 64),
+        "the fan's apex: 96 triangles tie": apex & hit,
+        "one component of d is +-0": zero.sum(axis=1) == 1,
+        "two components of d are +-0": zero.sum(axis=1) == 2,
+        "a component -0": (zero & np.signbit(d)).any(axis=1),
+        "zero component with the origin in a box plane": in_plane,
+        "zero component with the origin in a box plane, hit": in_plane & hit,
+        "origin on an earlier hit point": on_surface,
+        "origin on an earlier hit point, hit": on_surface & hit,
+        "tmax before the first hit": np.isfinite(first_t) & (tmax > 0) & (tmax < first_t) & ~root_miss,
+        "tmax between two hits": np.isfinite(second_t) & (tmax > first_t) & (tmax < second_t),
+        "tmax at the root box's entry": at_entry,
+        "tmin = -FLT_MAX, tmax = FLT_MAX": (tmin == -big) & (tmax == big),
+        "tmin after an earlier hit": tmin > F(0.001),
+        "NaN tmax": nan_bound,
+        "NaN tmax, hit": nan_bound & hit,
+        "NaN in d": ~fin_d,
+        "medium ray arriving at a back face, hit": back,
+        "medium ray, the front test not sure to have hit": retest,
+        "|d| < 0.03, hit": hit & (length < 0.03),
+        "|d| > 30, hit": hit & (length > 30),
+        "grazing (within 1e-3 rad of the hit triangle's plane)": (mesh == 7) & graze,
+        "root box missed": root_miss,
+        "root box missed by at most 4 ulps of the origin": root_near,
+    }
+    for m in range(10):
+        out[f"mesh {m}"] = mesh == m
+        # (mesh 8's triangles are below triangle::hit's det threshold, and aabb::hit never enters mesh 5's
+        # zero-thickness boxes unless a slab is NaN: neither is ever hit by a finite ray)
+        if m not in (5, 8):
+            out[f"mesh {m}, hit"] = (mesh == m) & hit
+    return out
+
+
+def mesh_nan_waves(rec):
+    """Wave-aligned groups of 64 records that hold a NaN bound (tmax) without a
+    finite one beside it (none expected)."""
+    nanb = np.isnan(rec[:, 8])
+    return [g for g in range(0, len(rec), 64) if nanb[g:g + 64].any() and nanb[g:g + 64].all()]
+
+
+_CLASSIFIERS = {"mesh": _mesh, "sphere": _sphere, "moving_sphere": _moving_sphere, "rect": _rect, "box": _box, "xform": _xform,
                 "medium": _medium, "isotropic": _isotropic, "texture_checker": _texture_checker,
                 "texture_noise": _texture_noise, "texture_image": _texture_image}
 

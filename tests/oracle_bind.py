@@ -28,6 +28,8 @@ def lib():
                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         L.oracle_kat.restype = ctypes.c_int
         L.oracle_kat.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+        L.oracle_kat_scene.restype = ctypes.c_int
+        L.oracle_kat_scene.argtypes = [ctypes.c_char_p]
         L.oracle_last_error.restype = ctypes.c_char_p
         L.oracle_sobol.argtypes = [ctypes.c_int, ctypes.c_void_p]
         L.oracle_teapot.argtypes = [ctypes.c_float, ctypes.c_int, ctypes.c_void_p]
@@ -71,6 +73,10 @@ def read_kat(name: str):
 
 def replay_kat(name: str, rec: np.ndarray) -> np.ndarray:
     out = np.ascontiguousarray(rec.copy())
+    if name == "mesh":  # replayed over the fixture meshes
+        with open(os.path.join(GOLDEN, "kat_mesh.scene"), "rb") as f:
+            if lib().oracle_kat_scene(f.read()) != 0:
+                raise RuntimeError(lib().oracle_last_error().decode())
     rc = lib().oracle_kat(name.encode(), out.shape[0], out.shape[1], _p(out))
     if rc != 0:
         raise RuntimeError(lib().oracle_last_error().decode())

@@ -69,6 +69,23 @@ def test_bvh_topology_matches_reference():
     np.testing.assert_allclose(gb, wb, rtol=1e-5)
 
 
+def test_kat_mesh_topology_matches_reference():
+    """The ten fixture meshes of the mesh KAT (tests/golden/README.md): Scene::bvh's
+    DFS leaf order is the reference's, also where the sort keys are equal (the flat
+    grid, mesh 5, and the duplicated triangles, mesh 6) and for 1, 2, 3 and 5 triangles."""
+    text = open(os.path.join(ob.GOLDEN, "kat_mesh.scene")).read()
+    want = open(os.path.join(ob.GOLDEN, "bvh_kat_mesh.txt")).read().split("mesh ")[1:]
+    assert len(want) == 10
+    for m, block in enumerate(want):
+        lines = block.splitlines()
+        assert lines[0] == str(m)
+        got = _bvh_text(text, 100000 + m).splitlines()
+        assert got[1:] == lines[2:], f"mesh {m}: leaf order differs"
+        gb = [float(x) for x in got[0].split()[1:]]
+        wb = [float(x) for x in lines[1].split()[1:]]
+        np.testing.assert_allclose(gb, wb, rtol=1e-5)
+
+
 def test_sobol_matches_reference():
     for n in (64, 1024, 4096):
         g = np.fromfile(os.path.join(ob.GOLDEN, f"sobol_{n}.f64"), np.float64).reshape(n, 2)

@@ -1,5 +1,5 @@
 """The edge cases the scene KATs were built for are really in the committed
-files.  Every record of tests/golden/kat_{sphere ... texture_image}.bin is
+files.  Every record of tests/golden/kat_{sphere ... texture_image, mesh}.bin is
 classified from its inputs and the reference's outputs alone (tests/kat_classes.py:
 float32 arithmetic in numpy, no device and no restatement code): each class of the
 issue's table holds at least 8 records, and each KAT with a hit flag has between a
@@ -28,5 +28,9 @@ def test_kat_edge_classes_populated():
             report.append(f"{name}: hits {frac:.3f}")
             if not 0.25 <= frac <= 0.75:
                 short.append(f"{name}: hit fraction {frac:.3f}")
+        if name == "mesh":  # the NaN-bound scan is wave-cooperative: every wave mixes NaN and finite lanes
+            bad = kc.mesh_nan_waves(rec)
+            if bad:
+                short.append(f"mesh: records {bad} onwards: a wave of 64 with NaN bounds only")
     print("\n".join(report))
     assert not short, "classes with fewer than 8 records, or a hit fraction outside [0.25, 0.75]: " + "; ".join(short)
