@@ -459,6 +459,28 @@ int srr_device_kat(const char* name, int n, int width, float* records);
 int srr_device_mesh_kat(const char* scene_text, int variant, int quad_max, int stack_cap, int use_gstack, int n,
                         int width, float* records);
 
+/* Test infrastructure: the world-list walk on the `world` KAT's records (width 24:
+ * world o(3) d(3) time tmin tmax is_medium | hit t obj p(3) n(3) u v, two spare;
+ * layouts and the fixture scene: tests/golden/README.md).  Text object 100000 + w of
+ * scene_text, a list, is world w.  Each world that a record names is flattened and
+ * uploaded on its own, exactly as a render of a scene with that world would be
+ * (sphere runs grouped, object BVHs built), and one kernel per world runs the
+ * frames' world hit and hit record on its records over [tmin, tmax]; an is_medium
+ * record runs the list walk a medium makes over its boundary, which gives hit and t
+ * only (refused on a world with a sphere group: a boundary's spheres are never
+ * grouped).  tables 0 reads the world tables from global memory, 1 from the copy
+ * staged in LDS (the default of the path kernel; each world must fit it).  obj is the
+ * winning primitive's position in the depth-first listing of its world's leaves in
+ * the file's order (a box is six rects), -1 on a miss.  Outputs are written in
+ * place.  Needs a GPU. */
+int srr_device_world_kat(const char* scene_text, int tables, int n, int width, float* records);
+
+/* Test infrastructure, no GPU: how world `world` of a world-KAT scene flattens.
+ * counts[0] objects in the flattened world list, [1] sphere groups among them,
+ * [2] object BVHs among them, [3] primitives (leaves), [4] bytes of the packed
+ * world tables (staged in LDS up to 8 KiB). */
+int srr_world_kat_counts(const char* scene_text, int world, int32_t* counts);
+
 /* Test infrastructure: one math routine of the device build over n elements
  * (host buffers; one thread per element).  float elements: the wrappers the
  * kernels call, "rsin", "rcos", "rexp", "rlog", "rpow" (x, y), "racos", "rasin",

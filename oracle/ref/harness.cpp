@@ -16,7 +16,7 @@
 //   bvh    <scene.txt> <obj_id> <out.txt>          reference BVH topology
 //   teapot <scale> <divs> <out.f32>                tessellated vertices
 //   sobol  <N> <out.f64>
-//   kat    <name> <n> <seed> <out.bin> [scene]     per-function known answers (kat mesh: its scene file)
+//   kat    <name> <n> <seed> <out.bin> [scene]     per-function known answers (kat mesh, kat world: its scene file)
 //   image  <file> <req_comp> <out.raw>             stbi_load (stb_image v2.19)
 //   builder <name> <nx> <ny> <ns> <maxdepth> <out_prefix>   a reference scene builder
 #define private public

@@ -600,6 +600,12 @@ struct List : Hitable {  // hitable_list.h:7-67
   }
 };
 
+struct Box : Hitable {  // box.h:5-34: own bbox (pmin, pmax), hit via the list of its six rects
+  const Hitable* l; AABB b;
+  bool hit(const Ray& r, float a, float bb, Hit& rec, bool m) const override { return l->hit(r, a, bb, rec, m); }
+  bool bbox(float, float, AABB& o) const override { o = b; return true; }
+};
+
 struct Flip : Hitable {  // aarect.h:149-171
   const Hitable* p;
   bool hit(const Ray& r, float tmin, float tmax, Hit& rec, bool med) const override {
@@ -1382,11 +1388,6 @@ std::unique_ptr<Scene> build(const std::string& text) {
                 mk(1, 0, 2, p0.x(), p1.x(), p0.z(), p1.z(), p0.y(), true),
                 mk(0, 1, 2, p0.y(), p1.y(), p0.z(), p1.z(), p1.x(), false),
                 mk(0, 1, 2, p0.y(), p1.y(), p0.z(), p1.z(), p0.x(), true)};
-        struct Box : Hitable {  // box.h:5-34: own bbox (pmin, pmax), hit via the list
-          const Hitable* l; AABB b;
-          bool hit(const Ray& r, float a, float bb, Hit& rec, bool m) const override { return l->hit(r, a, bb, rec, m); }
-          bool bbox(float, float, AABB& o) const override { o = b; return true; }
-        };
         Box* bx = St.add(new Box());
         bx->l = l;
         bx->b = AABB{p0, p1};

@@ -50,9 +50,54 @@ static const Hitable* kat_box(Store& St, V p0, V p1) {
 // command + 1 (never dereferenced), as in oracle/ref/kat.inc
 static std::unique_ptr<Scene> g_kat_scene;
 static std::vector<const Hitable*> g_kat_meshes;
+// the world KAT's scene (tests/golden/kat_world.scene): obj 100000 + w is world w; every
+// primitive under it carries its position in the depth-first listing of the world's leaves
+// (the file's order; a box is its six rects) + 1 as material pointer, as in oracle/ref/kat.inc
+struct KatWorld {
+  const Hitable* root;
+  std::vector<bool> moving;  // per leaf: a moving sphere (its record's u, v are defined as 0)
+};
+static std::vector<KatWorld> g_kat_worlds;
+static void kat_world_tags(const std::string& text) {
+  std::map<long long, srr_text::Cmd> by_id;
+  for (const auto& c : srr_text::parse(text))
+    if (c.at(0) == "obj") by_id[c.i(1)] = c;
+  for (int w = 0; by_id.count(100000 + w) && by_id.at(100000 + w).at(2) == "list"; ++w) {
+    KatWorld kw;
+    kw.root = g_kat_scene->obj.at(100000 + w);
+    std::function<void(const Hitable*)> prim = [&](const Hitable* h) {
+      const Material* tag = (const Material*)(uintptr_t)(kw.moving.size() + 1);
+      if (auto* f = dynamic_cast<const Flip*>(h)) return prim(f->p);
+      bool mv = false;
+      if (auto* s = dynamic_cast<const Sphere*>(h)) const_cast<Sphere*>(s)->mat = tag;
+      else if (auto* m = dynamic_cast<const MovingSphere*>(h)) { const_cast<MovingSphere*>(m)->mat = tag; mv = true; }
+      else if (auto* q = dynamic_cast<const Rect*>(h)) const_cast<Rect*>(q)->mat = tag;
+      else if (auto* t = dynamic_cast<const Triangle*>(h)) const_cast<Triangle*>(t)->mat = tag;
+      else throw std::runtime_error("kat world: a primitive of an unknown class");
+      kw.moving.push_back(mv);
+    };
+    std::function<void(long long)> walk = [&](long long id) {
+      const srr_text::Cmd& c = by_id.at(id);
+      const std::string& t = c.at(2);
+      if (t == "list") for (long long k = 0; k < c.i(3); ++k) walk(c.i(4 + k));
+      else if (t == "bvh") for (long long k = 0; k < c.i(5); ++k) walk(c.i(6 + k));
+      else if (t == "flip" || t == "translate" || t == "rotate_y" || t == "rotate_x") walk(c.i(3));
+      else if (t == "box") {
+        const List* l = dynamic_cast<const List*>(dynamic_cast<const Box*>(g_kat_scene->obj.at(id))->l);
+        for (const Hitable* k : l->l) prim(k);
+      } else prim(g_kat_scene->obj.at(id));
+    };
+    walk(100000 + w);
+    g_kat_worlds.push_back(kw);
+  }
+}
+
 static void kat_scene(const std::string& text) {
   g_kat_meshes.clear();
+  g_kat_worlds.clear();
   g_kat_scene = build(text);
+  kat_world_tags(text);
+  if (!g_kat_worlds.empty()) return;  // (the world KAT's scene; the mesh KAT's has no list 100000)
   for (const auto& c : srr_text::parse(text))
     if (c.at(0) == "obj" && c.at(2) == "bvh") {
       g_kat_meshes.push_back(g_kat_scene->obj.at(c.i(1)));
@@ -80,6 +125,24 @@ static int kat_one(const std::string& name, float* r) {
     wr3(o, hit ? h.normal : V(0.f));
     *o++ = hit ? h.u : 0;
     *o++ = hit ? h.v : 0;
+  } else if (name == "world") {
+    // in: world o d time tmin tmax is_medium | out: hit t obj p n u v, two spare
+    const int wi = (int)r[0];
+    if (wi < 0 || wi >= (int)g_kat_worlds.size()) return -1;
+    Hit h{};
+    const bool hit = g_kat_worlds[wi].root->hit(Ray(rd3(r + 1), rd3(r + 4), r[7]), r[8], r[9], h, r[10] != 0);
+    const int obj = hit ? (int)(uintptr_t)h.mat - 1 : -1;
+    if (hit && g_kat_worlds[wi].moving.at(obj)) h.u = h.v = 0;  // moving_sphere::hit leaves u, v unset: defined as 0
+    o = r + 11;
+    *o++ = hit ? 1.f : 0.f;
+    *o++ = hit ? h.t : 0;
+    *o++ = (float)obj;
+    wr3(o, hit ? h.p : V(0.f));
+    wr3(o, hit ? h.normal : V(0.f));
+    *o++ = hit ? h.u : 0;
+    *o++ = hit ? h.v : 0;
+    *o++ = 0;
+    *o++ = 0;
   } else if (name == "erf") {
     o = r + 1;
     *o++ = Erf(r[0]);

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -1245,6 +1246,197 @@ int srr_device_mesh_kat(const char* scene_text, int variant, int quad_max, int s
     rc = fail(SRR_EIO, "mesh KAT kernel failed");
   for (void* p : {(void*)d_rec, (void*)d_gst, (void*)d_mesh_obj, (void*)d_tri_file}) (void)hipFree(p);
   return rc;
+}
+
+}  // extern "C"
+
+namespace {
+constexpr long long kWorldKatBaseId = 100000;  // text obj 100000 + w is world w of the `world` KAT's scene
+
+// World w of a world-KAT scene flattened as a render of it would be (the scene's world
+// set to the list, then the same flatten, group_sphere_runs included), and leaf_of: per
+// DObj row that is a primitive, its position in the depth-first listing of the world's
+// leaves in the FILE's order (a list's and a bvh command's children as written, a box's
+// six rects, a wrapper's child) -- the order in which the reference harness numbers them.
+int world_kat_flatten(Scene& sc, int w, Flat& f, std::vector<int32_t>& leaf_of, int& n_leaves, std::string& err) {
+  int h = -1;
+  for (auto& kv : sc.text_ids)
+    if (kv.first == kWorldKatBaseId + w) h = kv.second;
+  if (!sc.valid_obj(h) || sc.obj[h].kind != H_LIST) {
+    err = "world KAT: no list object " + std::to_string(kWorldKatBaseId + w);
+    return SRR_EINVAL;
+  }
+  sc.world = h;
+  int rc = flatten(sc, f, err);
+  if (rc < 0) return rc;
+  // leaves under each handle, then flatten's emission order in file numbering: `top` for the
+  // world list's own rows (-1 where an object BVH stands), `inner` for the BVHs' children
+  std::function<int(int)> count = [&](int k) -> int {
+    const HObj& o = sc.obj[k];
+    switch (o.kind) {
+      case H_LIST: case H_BOX: { int n = 0; for (int c : o.kids) n += count(c); return n; }
+      case H_BVH: { int n = 0; for (int c : sc.bvhs[o.bvh].input) n += count(c); return n; }
+      case H_FLIP: case H_TRANSLATE: case H_ROTY: case H_ROTX: return count(o.child);
+      case H_MEDIUM: return -(1 << 20);  // (refused below)
+      default: return 1;
+    }
+  };
+  n_leaves = count(h);
+  if (n_leaves <= 0) {
+    err = "world KAT: a world holds a medium or nothing";
+    return SRR_EINVAL;
+  }
+  std::vector<int32_t> top, inner;
+  std::function<void(int, int, std::vector<int32_t>&)> emit = [&](int k, int base, std::vector<int32_t>& out) {
+    const HObj& o = sc.obj[k];
+    switch (o.kind) {
+      case H_LIST: case H_BOX:
+        for (int c : o.kids) { emit(c, base, out); base += count(c); }
+        break;
+      case H_BVH: {
+        const HBvh& B = sc.bvhs[o.bvh];
+        std::map<int, int> at;  // child handle -> first leaf number (children are distinct objects)
+        for (int c : B.input) { at[c] = base; base += count(c); }
+        if (&out == &top) top.push_back(-1);
+        for (int l : B.leaves) emit(l, at.at(l), inner);
+        break;
+      }
+      case H_FLIP: case H_TRANSLATE: case H_ROTY: case H_ROTX: emit(o.child, base, out); break;
+      default: out.push_back(base);
+    }
+  };
+  emit(h, 0, top);
+  leaf_of.assign(f.objs.size(), -1);
+  size_t tc = 0, ic = 0;
+  bool ok = true;
+  for (int k = 0; k < f.n_world && ok; ++k) {
+    const DObj& d = f.objs[k];
+    if (d.kind == OBJ_SGROUP) {
+      const DSGroup& g = f.sgroups[d.idx];
+      ok = tc + g.n_items <= top.size();
+      for (int i = g.item_off; ok && i < g.item_off + g.n_items; ++i) {
+        const DSGItem& it = f.sg_items[i];
+        ok = it.pos >= 0 && it.pos < g.n_items && it.obj >= 0 && it.obj < (int)f.objs.size() && top[tc + it.pos] >= 0;
+        if (ok) leaf_of[it.obj] = top[tc + it.pos];
+      }
+      tc += g.n_items;
+    } else if (d.kind == OBJ_OBVH) {
+      ok = tc < top.size() && top[tc] == -1;
+      ++tc;
+      const DObvh& o = f.obvhs[d.idx];
+      for (int c = o.child_off; ok && c < o.child_off + o.n_children; ++c)
+        for (int j = 0; ok && j < f.obvh_children[c].obj_count; ++j) {
+          const int row = f.obvh_children[c].obj_begin + j;
+          ok = ic < inner.size() && row >= 0 && row < (int)f.objs.size();
+          if (ok) leaf_of[row] = inner[ic++];
+        }
+    } else {
+      ok = (d.kind == OBJ_SPHERE || d.kind == OBJ_MSPHERE || d.kind == OBJ_RECT || d.kind == OBJ_TRI) && tc < top.size() &&
+           top[tc] >= 0;
+      if (ok) leaf_of[k] = top[tc++];
+    }
+  }
+  if (!ok || tc != top.size() || ic != inner.size()) {
+    err = "world KAT: the flattened world does not match the scene's leaves (a mesh, or an object used twice)";
+    return SRR_EINVAL;
+  }
+  return 0;
+}
+
+size_t world_table_bytes(const Flat& f) {  // renderer.cpp's packed world tables, each padded to 16 bytes
+  auto pad = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  return pad(f.objs.size() * sizeof(DObj)) + pad(f.xforms.size() * sizeof(DXform)) + pad(f.spheres.size() * sizeof(DSphere)) +
+         pad(f.rects.size() * sizeof(DRect)) + pad(f.stris.size() * sizeof(DStandaloneTri)) +
+         pad(f.meshes.size() * sizeof(DMesh)) + pad(f.media.size() * sizeof(DMedium)) + pad(f.mats.size() * sizeof(DMat)) +
+         pad(f.texs.size() * sizeof(DTex)) + pad(f.lights.size() * sizeof(DLight));
+}
+}  // namespace
+
+extern "C" {
+
+int srr_world_kat_counts(const char* scene_text, int world, int32_t* counts) {
+  if (!scene_text || !counts || world < 0) return fail(SRR_EINVAL, "bad world KAT arguments");
+  Scene sc;
+  std::string err;
+  int rc = scene_from_text(scene_text, sc, err);
+  if (rc < 0) return fail(rc, err);
+  Flat f;
+  std::vector<int32_t> leaf_of;
+  int n_leaves = 0;
+  if ((rc = world_kat_flatten(sc, world, f, leaf_of, n_leaves, err)) < 0) return fail(rc, err);
+  int ng = 0, nb = 0;
+  for (int k = 0; k < f.n_world; ++k) {
+    ng += f.objs[k].kind == OBJ_SGROUP;
+    nb += f.objs[k].kind == OBJ_OBVH;
+  }
+  counts[0] = f.n_world;
+  counts[1] = ng;
+  counts[2] = nb;
+  counts[3] = n_leaves;
+  counts[4] = (int32_t)world_table_bytes(f);
+  return 0;
+}
+
+int srr_device_world_kat(const char* scene_text, int tables, int n, int width, float* records) {
+  // every argument is checked before the first HIP call
+  if (!scene_text || !records || n <= 0 || n > 1 << 20 || width != kWorldKatWidth || tables < 0 || tables > 1)
+    return fail(SRR_EINVAL, "bad world KAT arguments");
+  Scene sc;
+  std::string err;
+  int rc = scene_from_text(scene_text, sc, err);
+  if (rc < 0) return fail(rc, err);
+  std::map<int, std::vector<int>> by_world;  // a launch holds the records of one world: its objects are wave-uniform
+  for (int q = 0; q < n; ++q) {
+    const float wf = records[(size_t)q * width];
+    if (!(wf >= 0 && wf < 1024.f && wf == (float)(int)wf)) return fail(SRR_EINVAL, "world KAT: a record names no world");
+    by_world[(int)wf].push_back(q);
+  }
+  struct Job { Flat f; std::vector<int32_t> leaf_of; };
+  std::map<int, Job> jobs;
+  for (auto& kv : by_world) {
+    Job& j = jobs[kv.first];
+    int n_leaves = 0;
+    if ((rc = world_kat_flatten(sc, kv.first, j.f, j.leaf_of, n_leaves, err)) < 0) return fail(rc, err);
+    if (tables == 1 && world_table_bytes(j.f) > (size_t)kPathsWorldLdsBytes)
+      return fail(SRR_EINVAL, "world KAT: a world's tables do not fit the LDS copy");
+    bool grouped = false;
+    for (int k = 0; k < j.f.n_world; ++k) grouped = grouped || j.f.objs[k].kind == OBJ_SGROUP;
+    for (int q : kv.second)  // list_hit is a medium's boundary walk, and a boundary's spheres are never grouped
+      if (grouped && records[(size_t)q * width + 10] != 0)
+        return fail(SRR_EINVAL, "world KAT: an is_medium record on a world with a sphere group");
+  }
+  for (auto& kv : by_world) {
+    Job& j = jobs[kv.first];
+    const std::vector<int>& idx = kv.second;
+    std::vector<float> rec(idx.size() * (size_t)width);
+    for (size_t i = 0; i < idx.size(); ++i)
+      std::memcpy(&rec[i * width], &records[(size_t)idx[i] * width], width * sizeof(float));
+    srr_renderer* r = nullptr;  // uploads the tables exactly as a render does
+    if ((rc = renderer_create_flat(j.f, 0, &r, err)) < 0) return fail(rc, err);
+    std::unique_ptr<srr_renderer> keep(r);
+    float* d_rec = nullptr;
+    int32_t* d_leaf = nullptr;
+    const size_t rb = rec.size() * sizeof(float), lb = j.leaf_of.size() * sizeof(int32_t);
+    rc = 0;
+    if (hipMalloc((void**)&d_rec, rb) != hipSuccess || hipMalloc((void**)&d_leaf, lb) != hipSuccess)
+      rc = fail(SRR_ENOMEM, "device allocation failed");
+    if (!rc && (hipMemcpy(d_rec, rec.data(), rb, hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(d_leaf, j.leaf_of.data(), lb, hipMemcpyHostToDevice) != hipSuccess))
+      rc = fail(SRR_EIO, "copy to device failed");
+    WorldKatArgs A{};
+    A.n = (int)idx.size();
+    A.width = width;
+    A.rec = d_rec;
+    A.leaf_of = d_leaf;
+    if (!rc && launch_world_kat(r->view, tables, A) < 0) rc = fail(SRR_EIO, "world KAT kernel launch failed");
+    if (!rc && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(rec.data(), d_rec, rb, hipMemcpyDeviceToHost) != hipSuccess))
+      rc = fail(SRR_EIO, "world KAT kernel failed");
+    for (void* p : {(void*)d_rec, (void*)d_leaf}) (void)hipFree(p);
+    if (rc) return rc;
+    for (size_t i = 0; i < idx.size(); ++i)
+      std::memcpy(&records[(size_t)idx[i] * width], &rec[i * width], width * sizeof(float));
+  }
+  return 0;
 }
 
 int srr_device_libm(const char* fn, int64_t n, const void* x, const void* y, void* out0, void* out1) {

@@ -315,6 +315,18 @@ struct MeshKatArgs {
 };
 // 0, -1 (bad arguments, nothing launched) or -5 (launch failed); SceneView::quad_max decides the quad variant's route
 int launch_mesh_kat(const SceneView& S, int variant, const MeshKatArgs& A);
+// the world-walk KAT (srr_device_world_kat, kernels.hip k_world_kat): world_hit<false, TR> and
+// world_record<TR> (is_medium records: list_hit<TR> over the world's objects) on the records of
+// one uploaded world, with TR = TR_BVH4_PRUNE, and | TR_WL with the tables staged in LDS
+constexpr int kWorldKatWidth = 24;  // world o(3) d(3) time tmin tmax is_medium | hit t obj p(3) n(3) u v, 2 spare
+struct WorldKatArgs {
+  int n, width;            // records, all of the uploaded world
+  float* rec;              // device records, outputs written in place
+  const int32_t* leaf_of;  // [DObj row] -> the primitive's position in the world's depth-first leaf listing
+};
+// 0, -1 (bad arguments, nothing launched) or -5 (launch failed); tables: 0 global, 1 staged in LDS
+// (S.world_words * 16 <= kPathsWorldLdsBytes)
+int launch_world_kat(const SceneView& S, int tables, const WorldKatArgs& A);
 // device libm sweeps (srr_device_libm): routine kLibmFns[fn] over n elements, one per
 // thread; device pointers (d_y / d_out1 unused unless n_in / n_out is 2).  The switches
 // of kernels.hip k_libm_f32 / k_libm_f64 go by LibmId, and row i of the table is id i

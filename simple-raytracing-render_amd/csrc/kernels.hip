@@ -1421,10 +1421,11 @@ SRR_D void world_objs(const SceneView& S, const Ray& r, Rng& rng, const TraceCtx
 // mesh walk would reuse the lane's traversal stack, which holds the suspended walk.
 // The objects stay in list order for every lane, so the result is the same.
 template <bool MEDIA, int TR>
-SRR_D WorldHit world_hit(const SceneView& S, const Ray& r, Rng& rng, const TraceCtx& cx) {
+SRR_D WorldHit world_hit(const SceneView& S, const Ray& r, Rng& rng, const TraceCtx& cx, const float tmin = 0.001f,
+                         const float tmax = FLT_MAX) {
+  // (the frames' range: 0.001, numeric_limits<float>::max(), Raytracing_n.cpp:58; only the world KAT passes another)
   WorldHit w{-1, -1, 0};
-  float closest = FLT_MAX;  // numeric_limits<float>::max(), Raytracing_n.cpp:58
-  const float tmin = 0.001f;
+  float closest = tmax;
   constexpr bool SUSP = (TR & TR_SUSP) != 0;
   const bool skip = MEDIA || S.mesh_obj < 0;  // (wave-uniform) the list state is saved, see above
   int k_res = -1;  // (SUSP, skip) the object whose walk this lane resumes
@@ -4587,6 +4588,67 @@ __global__ void __launch_bounds__(kTraceBlock) k_mesh_kat(SceneView S, MeshKatAr
   for (int k = 0; k < 11; ++k) r[10 + k] = out[k];
 }
 
+// Test infrastructure (srr_device_world_kat): the world-list walk on the reference's
+// `world` KAT records (tests/golden/README.md), one record per lane, all of the one
+// uploaded world -- the objects world_hit reads are wave-uniform (uni()), as in a frame,
+// while the lanes' rays diverge inside a sphere group or an object BVH.  in: world o d
+// time tmin tmax is_medium | out: hit t obj p n u v (zeros and obj = -1 on a miss).  A
+// record runs the frames' own world_hit<false, TR> and world_record<TR>; an is_medium
+// record the call a medium's boundary makes, list_hit<TR> over the world's objects,
+// which gives hit and t alone.  obj is the winning primitive's DObj row (through the
+// group's item or the object BVH's child) mapped to the file's order by A.leaf_of.
+template <int TR>
+__global__ void __launch_bounds__(kTraceBlock) k_world_kat(SceneView S0, WorldKatArgs A) {
+  SceneView S = S0;
+  if constexpr ((TR & TR_WL) != 0) {  // world tables -> LDS, once per block (as k_trace)
+    __shared__ uint4 s_world[kWorldLdsBytes / 16];
+    for (int i = threadIdx.x; i < S0.world_words; i += blockDim.x) s_world[i] = S0.world_blob[i];
+    __syncthreads();
+    const char* b = (const char*)s_world;
+    S.objs = (const DObj*)(b + S0.world_off[0]);
+    S.xforms = (const DXform*)(b + S0.world_off[1]);
+    S.spheres = (const DSphere*)(b + S0.world_off[2]);
+    S.rects = (const DRect*)(b + S0.world_off[3]);
+    S.stris = (const DStandaloneTri*)(b + S0.world_off[4]);
+    S.meshes = (const DMesh*)(b + S0.world_off[5]);
+    S.media = (const DMedium*)(b + S0.world_off[6]);
+  }
+  __shared__ int s_node[kStack * kTraceBlock];
+  __shared__ float s_t[kStack * kTraceBlock];
+  TraceCtx cx{nullptr, to_lds(s_node + threadIdx.x), to_lds(s_t + threadIdx.x)};
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= A.n) return;
+  float* r = A.rec + (size_t)q * A.width;
+  const Ray ray{kat3(r + 1), kat3(r + 4), r[7]};
+  const float tmin = r[8], tmax = r[9];
+  float out[11];
+  for (int k = 0; k < 11; ++k) out[k] = 0;
+  out[2] = -1.f;
+  if (r[10] != 0) {
+    float t = 0;
+    if (list_hit<TR>(S, 0, S.n_world, ray, tmin, tmax, t, cx)) {
+      out[0] = 1.f;
+      out[1] = t;
+    }
+  } else {
+    Rng rng{0, 0};
+    const WorldHit w = world_hit<false, TR>(S, ray, rng, cx, tmin, tmax);
+    if (w.obj >= 0) {
+      const HitRec hr = world_record<TR>(S, ray, w);
+      const DObj ob = S.objs[w.obj];
+      const int row = ob.kind == OBJ_OBVH ? w.prim : (ob.kind == OBJ_SGROUP ? S.sg_items[w.prim].obj : w.obj);
+      out[0] = 1.f;
+      out[1] = w.t;
+      out[2] = (float)A.leaf_of[row];
+      kat_put3(out + 3, hr.p);
+      kat_put3(out + 6, hr.n);
+      out[9] = hr.u;
+      out[10] = hr.v;
+    }
+  }
+  for (int k = 0; k < 11; ++k) r[11 + k] = out[k];
+}
+
 // Test infrastructure (srr_device_libm): one libm routine of the device build over
 // an array, one element per thread.  fn is a LibmId (kernels.h).  The f32 entries are
 // the devmath.h wrappers the kernels call; the f64 ones the restatement of glibc's
@@ -4971,6 +5033,15 @@ int launch_mesh_kat(const SceneView& S, int variant, const MeshKatArgs& A) {
     case kMeshKatQuad: hipLaunchKernelGGL((dev::k_mesh_kat<kMeshKatQuad>), g, b, 0, 0, S, A); break;
     default: return -1;
   }
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+int launch_world_kat(const SceneView& S, int tables, const WorldKatArgs& A) {
+  if (A.n <= 0 || A.width != kWorldKatWidth || !A.rec || !A.leaf_of || tables < 0 || tables > 1) return -1;
+  if (tables == 1 && S.world_words * 16 > dev::kWorldLdsBytes) return -1;  // the tables must fit the LDS copy
+  const dim3 g((A.n + dev::kTraceBlock - 1) / dev::kTraceBlock), b(dev::kTraceBlock);
+  if (tables == 1) hipLaunchKernelGGL((dev::k_world_kat<dev::TR_BVH4_PRUNE | dev::TR_WL>), g, b, 0, 0, S, A);
+  else hipLaunchKernelGGL((dev::k_world_kat<dev::TR_BVH4_PRUNE>), g, b, 0, 0, S, A);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

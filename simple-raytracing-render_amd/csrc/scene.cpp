@@ -1424,6 +1424,9 @@ static std::vector<DObj> group_sphere_runs(const Scene& S, Flat& F, const std::v
     }
     // items and their boxes (the center's whole path over the ray times, widened by
     // a relative 1e-5 for the float center arithmetic; sgroup_hit adds the per-ray pad)
+    // (the world KAT places origins in these boxes' face planes: the widening below is restated, only to
+    // aim rays and to classify them, in oracle/ref/kat.inc kat_sgroup_plane and tests/kat_classes.py
+    // _sgroup_plane -- change all three together)
     struct It { DSGItem it; double mn[3], mx[3], c[3]; };
     std::vector<It> items;
     for (size_t k = i; k < j; ++k) {

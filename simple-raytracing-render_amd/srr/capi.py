@@ -419,6 +419,27 @@ def device_mesh_kat(scene_text: str, rec: np.ndarray, variant: str, quad_max: in
     return out
 
 
+def device_world_kat(scene_text: str, rec: np.ndarray, tables: int) -> np.ndarray:
+    """srr_device_world_kat (test infrastructure): the `world` KAT's records with the
+    outputs of the world-list walk; tables 0 reads the world tables from global
+    memory, 1 from their copy in LDS."""
+    L = lib()
+    L.srr_device_world_kat.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    out = np.ascontiguousarray(rec, np.float32).copy()
+    _check(L.srr_device_world_kat(scene_text.encode(), tables, out.shape[0], out.shape[1], _ptr(out)))
+    return out
+
+
+def world_kat_counts(scene_text: str, world: int) -> dict:
+    """srr_world_kat_counts (test infrastructure, no GPU): how a world of the `world`
+    KAT's scene flattens."""
+    L = lib()
+    L.srr_world_kat_counts.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p]
+    c = np.zeros(5, np.int32)
+    _check(L.srr_world_kat_counts(scene_text.encode(), world, _ptr(c)))
+    return dict(objects=int(c[0]), sgroups=int(c[1]), obvhs=int(c[2]), leaves=int(c[3]), table_bytes=int(c[4]))
+
+
 def write_ppm(path: str, nx: int, ny: int, img8: np.ndarray) -> None:
     img8 = np.ascontiguousarray(img8, np.uint8)
     _check(lib().srr_write_ppm(path.encode(), nx, ny, _ptr(img8)))

@@ -49,7 +49,9 @@ KATS = [("erf", 512), ("beckmann11", 512), ("beckmann_dist", 512), ("beckmann_pd
         ("sphere", 1024), ("moving_sphere", 1024), ("rect", 1024), ("box", 1024), ("xform", 1024), ("medium", 1024),
         ("isotropic", 1024), ("texture_checker", 1024), ("texture_noise", 1024), ("texture_image", 1024),
         # the mesh walk: bvh_node::hit over the ten meshes of kat_mesh.scene (README.md)
-        ("mesh", 1024)]
+        ("mesh", 1024),
+        # the world-list walk: hitable_list::hit over the seven worlds of kat_world.scene (README.md)
+        ("world", 1024)]
 
 
 # The MERL KATs' out == in records are decided by the last-ulp rounding of glibc's
@@ -172,6 +174,133 @@ def make_mesh_kat(n):
     with open(os.path.join(HERE, "bvh_kat_mesh.txt"), "w") as f:
         f.write("".join(dumps))
 
+WORLD_SCENE = os.path.join(HERE, "kat_world.scene")
+
+
+def world_scene_text():
+    """The seven fixture worlds of the `world` KAT (README.md): obj 100000 + w is
+    world w, a hitable_list; no object is used twice.  Coordinates are quarters except
+    where a comment says otherwise; the camera's shutter is [0, 1]."""
+    out = ["srr_scene 1", "# the `world` KAT's fixture worlds (README.md): obj 100000 + w is world w",
+           "tex 0 const 0.5 0.5 0.5", "mat 0 lambertian 0"]
+    nid = [0]
+    state = [12345]
+
+    def rnd(lo, hi):  # quarters in [lo, hi], a small LCG of this file's own
+        state[0] = (state[0] * 1103515245 + 12345) % (1 << 31)
+        return lo + 0.25 * ((state[0] >> 8) % int((hi - lo) * 4 + 1))
+
+    def obj(text):
+        out.append(f"obj {nid[0]} {text}")
+        nid[0] += 1
+        return nid[0] - 1
+
+    def sphere(c, r):
+        return obj(f"sphere {c[0]!r} {c[1]!r} {c[2]!r} {r!r} 0")
+
+    def msphere(c0, c1, t0, t1, r):
+        return obj("moving_sphere " + " ".join(repr(float(x)) for x in (*c0, *c1, t0, t1, r)) + " 0")
+
+    def rect(kind, a0, a1, b0, b1, k):
+        return obj(f"{kind} {a0!r} {a1!r} {b0!r} {b1!r} {k!r} 0")
+
+    def box(p0, p1):
+        return obj("box " + " ".join(repr(float(x)) for x in (*p0, *p1)) + " 0")
+
+    def tri(p):
+        return obj("triangle " + " ".join(repr(float(x)) for x in p) + " 0")
+
+    def lst(kids, at=None):
+        line = f"list {len(kids)} " + " ".join(map(str, kids))
+        if at is None:
+            return obj(line)
+        out.append(f"obj {at} {line}")
+        return at
+
+    def bvh(kids):
+        return obj(f"bvh 0.0 1.0 {len(kids)} " + " ".join(map(str, kids)))
+
+    def cloud(n, lo=-6.0, hi=6.0, r=(0.5, 1.5)):
+        return [sphere((rnd(lo, hi), rnd(lo, hi), rnd(lo, hi)), rnd(*r)) for _ in range(n)]
+
+    worlds = []
+    worlds.append(cloud(7))                                     # 0: below kSGroupMinRun
+    worlds.append(cloud(8))                                     # 1: the threshold
+    # 2: rect | the run of 40 | box, rect
+    w2 = [rect("xy_rect", -8.0, 8.0, -3.0, 8.0, 0.0)]
+    dup = [((2.0, 1.0, 4.0), 1.0), ((-3.0, 2.0, -2.0), 1.25), ((4.0, -1.0, -4.0), 0.75)]
+    run = [sphere(*dup[0]), sphere((0.0, 0.0, 3.0), 2.0), sphere((0.0, 0.0, 3.0), 1.0)]           # shells, outer first
+    for k in range(5):                                                                            # moving spheres
+        c = (rnd(-6, 6), rnd(-2, 5), rnd(-6, 6))
+        run.append(msphere(c, (c[0], c[1] + 0.5, c[2] + 0.25 * k), 0.0, 1.0, 0.5))
+    run += [sphere(*dup[1]), sphere((0.0, -1004.0, 0.0), 1000.0)]                                 # the ground
+    for k in range(12):                                                                           # tiny and far
+        run.append(sphere((64.0 + 2.0 * (k % 3), 2.0 * (k % 4) - 3.0, 2.0 * (k // 4) - 2.0), 0.02))
+    run += [sphere((0.0, 0.0, 3.0), -1.25), sphere((0.0, 0.0, 3.0), 1.5)]                         # shells: negative, middle
+    run += [sphere((5.0, 3.0, 2.0), -0.75), sphere((-5.0, 4.0, -3.0), -0.75), sphere(*dup[2])]
+    for k in range(5):
+        c = (rnd(-6, 6), rnd(-2, 5), rnd(-6, 6))
+        run.append(msphere(c, (c[0] + 0.5, c[1], c[2] - 0.25 * k), 0.0, 1.0, 0.75))
+    run += cloud(5, r=(0.5, 1.0))
+    run += [sphere(*dup[0]), sphere(*dup[1]), sphere(*dup[2])]                                    # the duplicates, late
+    assert len(run) == 40
+    w2 += run + [box((-7.0, -3.0, 5.0), (-5.0, -1.0, 7.0)), rect("xz_rect", -10.0, 10.0, -10.0, 10.0, -3.5)]
+    worlds.append(w2)
+    # 3: run of 10 | translate(sphere) | run of 9 | moving sphere with t0 == t1 | run of 8
+    w3 = cloud(10)
+    w3.append(obj(f"translate {sphere((0.0, 0.0, 0.0), 1.0)} 1.5 -2.0 0.25"))
+    w3 += cloud(9)
+    w3.append(msphere((1.0, 1.0, 1.0), (2.0, 1.0, 1.0), 0.5, 0.5, 1.0))
+    w3 += cloud(8)
+    worlds.append(w3)
+    # 4: object BVHs over 1, 2, 3 and 5 children
+    worlds.append([
+        bvh([sphere((-9.0, 0.0, 0.0), 1.0)]),
+        bvh([sphere((-4.0, 0.0, 0.0), 1.0), rect("xy_rect", -5.0, -2.0, -1.0, 2.0, -0.5)]),
+        bvh([sphere((1.0, 0.0, 0.0), 1.0), sphere((2.0, 0.5, 0.25), 1.0), box((0.0, -2.0, -1.0), (2.0, -1.0, 1.0))]),
+        bvh([sphere((7.0, 0.0, 0.0), 1.0), msphere((9.0, 0.0, 0.0), (9.0, 0.5, 0.0), 0.0, 1.0, 0.75),
+             rect("yz_rect", -1.0, 1.0, -1.0, 1.0, 6.5), tri((6.0, 1.5, -1.0, 9.0, 1.5, -1.0, 7.5, 2.5, 1.0)),
+             sphere((8.0, -1.5, 0.5), 0.5)])])
+    # 5: one object BVH over 24 mixed children
+    k5 = []
+    for k in range(3):
+        k5.append(sphere((rnd(-6, 6), rnd(-4, 4), rnd(-6, 6)), rnd(0.5, 1.25)))
+    for k in range(3):
+        c = (rnd(-6, 6), rnd(-4, 4), rnd(-6, 6))
+        k5.append(msphere(c, (c[0], c[1] + 0.75, c[2]), 0.0, 1.0, 0.5))
+    k5 += [rect("xy_rect", -2.0, 1.0, -1.0, 2.0, -5.0), rect("xz_rect", 2.0, 5.0, -3.0, 0.0, -4.0),
+           rect("yz_rect", -1.0, 2.0, 1.0, 4.0, -6.5)]
+    k5 += [box((-5.0, -1.0, 2.0), (-3.0, 1.0, 4.0)), box((3.0, 1.0, 3.0), (4.5, 2.0, 5.0)),
+           box((-1.0, -5.0, -1.0), (1.0, -4.0, 1.0))]
+    k5 += [tri((0.0, 3.0, -2.0, 3.0, 3.5, -2.0, 1.0, 5.0, -0.5)), tri((-6.0, 2.0, 0.0, -4.0, 2.0, 1.0, -5.0, 4.0, -1.0)),
+           tri((2.0, -2.0, 5.5, 5.0, -2.0, 5.5, 3.0, 0.0, 6.5))]
+    k5.append(obj(f"translate {obj(f'rotate_y {box((-1.0, -1.0, -1.0), (1.0, 0.5, 1.0))} 30.0')} 4.0 -1.0 -4.0"))
+    k5.append(obj(f"flip {rect('xz_rect', -6.0, -3.0, -6.0, -3.0, 3.0)}"))
+    k5.append(obj(f"rotate_x {sphere((0.0, 2.0, 6.0), 1.0)} 20.0"))
+    k5 += [sphere((5.0, 4.0, -5.0), 1.0), sphere((-2.0, -2.0, -6.0), 0.75)]      # two children, each listed again below:
+    k5 += [sphere((-6.0, -4.0, 5.0), 1.0), sphere((6.0, -4.0, 1.0), 0.75)]
+    k5 += [sphere((5.0, 4.0, -5.0), 1.0), sphere((-2.0, -2.0, -6.0), 0.75)]      # the duplicates (other objects, same values)
+    assert len(k5) == 24
+    worlds.append([bvh(k5)])
+    # 6: translate(rotate_y(bvh(32 small spheres))) beside two rects and a box
+    small = [sphere((0.5 * (k % 4) + rnd(0, 0.25), 0.5 * ((k // 4) % 4) + rnd(0, 0.25), 0.75 * (k // 16) + rnd(0, 0.25)), 0.25)
+             for k in range(32)]
+    inst = obj(f"translate {obj(f'rotate_y {bvh(small)} 15.0')} -1.0 0.5 -1.0")
+    worlds.append([rect("xz_rect", -5.0, 5.0, -5.0, 5.0, -1.0), inst, rect("yz_rect", -1.0, 4.0, -4.0, 4.0, 4.0),
+                   box((-4.0, -1.0, -4.0), (-2.5, 1.0, -2.5))])
+    for w, kids in enumerate(worlds):
+        lst(kids, at=100000 + w)
+    out += ["world 100000", "camera 0.0 0.0 -100.0 0.0 0.0 0.0 0.0 1.0 0.0 40.0 1.0 0.0 10.0 0.0 1.0",
+            "obj 200001 xz_rect 0.0 1.0 0.0 1.0 500.0 -1", "obj 200002 list 1 200001", "lights 200002"]
+    return "\n".join(out) + "\n"
+
+
+def make_world_kat(n):
+    """kat_world.scene and the reference's records over it."""
+    with open(WORLD_SCENE, "w") as f:
+        f.write(world_scene_text())
+    run("kat", "world", n, 1234567, os.path.join(HERE, "kat_world.bin"), WORLD_SCENE)
+
 
 def only_kats(names):
     """Generate the named KATs alone and add their entries to golden.json."""
@@ -185,6 +314,8 @@ def only_kats(names):
     for name in names:
         if name == "mesh":
             make_mesh_kat(sizes[name])
+        elif name == "world":
+            make_world_kat(sizes[name])
         else:
             run("kat", name, sizes[name], 1234567, os.path.join(HERE, f"kat_{name}.bin"))
         meta["kats"][name] = sizes[name]
@@ -216,6 +347,8 @@ def main():
             continue
         if name == "mesh":
             make_mesh_kat(n)
+        elif name == "world":
+            make_world_kat(n)
         else:
             run("kat", name, n, 1234567, os.path.join(HERE, f"kat_{name}.bin"))
         meta["kats"][name] = n

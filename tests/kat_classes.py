@@ -1,6 +1,6 @@
 """Edge classes of the scene KAT records (tests/golden/kat_{sphere, moving_sphere,
 rect, box, xform, medium, isotropic, texture_checker, texture_noise,
-texture_image, mesh}.bin), worked out from the committed records alone: the inputs,
+texture_image, mesh, world}.bin), worked out from the committed records alone: the inputs,
 the reference's outputs and float32 arithmetic in numpy (the mesh KAT also reads its
 committed scene text, kat_mesh.scene, and places lattice points in exact float64).
 No device code and no restatement code is involved.  Layouts: tests/golden/README.md.
@@ -14,9 +14,9 @@ import os
 import numpy as np
 
 F = np.float32
-HIT = {"sphere": 12, "moving_sphere": 18, "rect": 15, "box": 14, "xform": 27, "medium": 18, "mesh": 10}
+HIT = {"sphere": 12, "moving_sphere": 18, "rect": 15, "box": 14, "xform": 27, "medium": 18, "mesh": 10, "world": 11}
 NEW_KATS = ("sphere", "moving_sphere", "rect", "box", "xform", "medium", "isotropic", "texture_checker",
-            "texture_noise", "texture_image", "mesh")
+            "texture_noise", "texture_image", "mesh", "world")
 MESH_SCENE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kat_mesh.scene")
 
 
@@ -465,7 +465,393 @@ def mesh_nan_waves(rec):
     return [g for g in range(0, len(rec), 64) if nanb[g:g + 64].any() and nanb[g:g + 64].all()]
 
 
-_CLASSIFIERS = {"mesh": _mesh, "sphere": _sphere, "moving_sphere": _moving_sphere, "rect": _rect, "box": _box, "xform": _xform,
+WORLD_SCENE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kat_world.scene")
+WORLD_T_ONLY_CAP = 0.08  # at most this share of the world KAT's records compares hit and t alone
+
+
+@functools.lru_cache(maxsize=None)
+def world_scene():
+    """kat_world.scene: per world (obj 100000 + w) its top-level children as (kind,
+    values) in list order, and every rect plane (axis, k) under it."""
+    objs, worlds = {}, []
+    with open(WORLD_SCENE) as f:
+        for line in f:
+            w = line.split("#")[0].split()
+            if len(w) > 2 and w[0] == "obj":
+                objs[int(w[1])] = w[2:]
+
+    def rects(i, out):
+        o = objs[i]
+        if o[0] in ("xy_rect", "xz_rect", "yz_rect"):
+            out.append(({"xy_rect": 2, "xz_rect": 1, "yz_rect": 0}[o[0]], float(o[5])))
+        elif o[0] == "list":
+            for k in o[2:2 + int(o[1])]:
+                rects(int(k), out)
+        elif o[0] == "bvh":
+            for k in o[4:4 + int(o[3])]:
+                rects(int(k), out)
+        elif o[0] == "flip":
+            rects(int(o[1]), out)
+        return out
+
+    def prims(i, out):  # the primitives under i that no wrapper moves: (kind, values); a box is kept whole
+        o = objs[i]
+        if o[0] == "list":
+            for k in o[2:2 + int(o[1])]:
+                prims(int(k), out)
+        elif o[0] == "bvh":
+            for k in o[4:4 + int(o[3])]:
+                prims(int(k), out)
+        elif o[0] in ("sphere", "moving_sphere", "xy_rect", "xz_rect", "yz_rect", "box", "triangle"):
+            out.append((o[0], [float(x) for x in o[1:-1]]))
+        return out
+
+    w = 0
+    while 100000 + w in objs:
+        kids = [int(k) for k in objs[100000 + w][2:]]
+        tops = [(objs[k][0], [float(x) for x in objs[k][1:-1]] if objs[k][0] in ("sphere", "moving_sphere") else None)
+                for k in kids]
+        worlds.append(dict(tops=tops, rect_planes=rects(100000 + w, []), prims=prims(100000 + w, []),
+                           bvh_prims=[prims(k, []) for k in kids if objs[k][0] == "bvh"]))
+        w += 1
+    return worlds
+
+
+def _prim_box(kind, v):
+    """The reference's bounding_box(0, 1) of an unwrapped primitive, in float32 (sphere.h:31-34,
+    moving_sphere.h:53-59, aarect.h:11-14, :41-44, :72-75, box.h:10-13, triangle.h:53-70)."""
+    v = [F(x) for x in v]
+    if kind == "sphere":
+        c, r = np.array(v[:3], F), v[3]
+        return c - r, c + r
+    if kind == "moving_sphere":
+        c0, c1, r = np.array(v[:3], F), np.array(v[3:6], F), v[8]
+        return np.minimum(c0 - r, c1 - r), np.maximum(c0 + r, c1 + r)  # (t0 = 0, t1 = 1: the centers themselves)
+    if kind == "box":
+        return np.array(v[:3], F), np.array(v[3:6], F)
+    if kind == "triangle":
+        p = np.array(v[:9], F).reshape(3, 3)
+        return p.min(axis=0), p.max(axis=0)
+    ax, (a0, a1) = {"xy_rect": (2, (0, 1)), "xz_rect": (1, (0, 2)), "yz_rect": (0, (1, 2))}[kind]
+    lo, hi = np.zeros(3, F), np.zeros(3, F)
+    lo[a0], hi[a0], lo[a1], hi[a1] = v[0], v[1], v[2], v[3]
+    lo[ax], hi[ax] = F(float(v[4]) - 0.0001), F(float(v[4]) + 0.0001)
+    return lo, hi
+
+
+def _line_hits(prims, o, d, time):
+    """Parameters t at which the lines o + t d (float64, per record) meet the unwrapped
+    primitives, [records][candidates] with inf where there is none: both roots of a sphere
+    (a moving one at the record's time), a rect's or box face's plane crossing inside its
+    bounds, a triangle's plane crossing inside it."""
+    cols = []
+    with np.errstate(all="ignore"):
+        for kind, v in prims:
+            if kind in ("sphere", "moving_sphere"):
+                if kind == "sphere":
+                    c, r = np.array(v[:3])[None, :], v[3]
+                else:
+                    c = np.array(v[:3]) + ((time[:, None] - v[6]) / (v[7] - v[6])) * (np.array(v[3:6]) - np.array(v[:3]))
+                    r = v[8]
+                oc = o - c
+                a, b, cc = (d * d).sum(1), (oc * d).sum(1), (oc * oc).sum(1) - r * r
+                disc = b * b - a * cc
+                sq = np.sqrt(np.where(disc > 0, disc, 0))
+                cols += [np.where(disc > 0, (-b - sq) / a, np.inf), np.where(disc > 0, (-b + sq) / a, np.inf)]
+            elif kind == "triangle":
+                p0, p1, p2 = np.array(v[0:3]), np.array(v[3:6]), np.array(v[6:9])
+                e1, e2 = p1 - p0, p2 - p0
+                P = np.cross(d, e2[None])
+                det = (e1[None] * P).sum(1)
+                T = o - p0
+                u = (T * P).sum(1) / det
+                Q = np.cross(T, e1[None])
+                vv = (d * Q).sum(1) / det
+                t = (e2[None] * Q).sum(1) / det
+                cols.append(np.where((u > 0) & (vv > 0) & (u + vv < 1), t, np.inf))
+            else:
+                if kind == "box":
+                    faces = [(ax, v[s * 3 + ax], [(a, v[a], v[3 + a]) for a in range(3) if a != ax])
+                             for ax in range(3) for s in (0, 1)]
+                else:
+                    ax, (a0, a1) = {"xy_rect": (2, (0, 1)), "xz_rect": (1, (0, 2)), "yz_rect": (0, (1, 2))}[kind]
+                    faces = [(ax, v[4], [(a0, v[0], v[1]), (a1, v[2], v[3])])]
+                for ax, k, bounds in faces:
+                    t = (k - o[:, ax]) / d[:, ax]
+                    ok = np.isfinite(t)
+                    for a, lo, hi in bounds:
+                        x = o[:, a] + t * d[:, a]
+                        ok &= (x > lo) & (x < hi)
+                    cols.append(np.where(ok, t, np.inf))
+    return np.stack(cols, axis=1)
+
+
+def world_t_only(rec):
+    """Records of the world KAT that compare hit and t alone: the is_medium ones (the
+    boundary walk, list_hit, yields no more)."""
+    return np.asarray(rec)[:, 10] != 0
+
+
+def _sgroup_plane(c, r, hi):  # csrc/scene.cpp group_sphere_runs: the item box of a static sphere on one axis, as a float
+    r = abs(r)
+    lo, up = c - r, c + r
+    w = 1e-5 * (max(abs(lo), abs(up)) + r) + 1e-30
+    v = up + w if hi else lo - w
+    f = F(v)
+    if (float(f) < v) if hi else (float(f) > v):
+        f = np.nextafter(f, F(np.inf if hi else -np.inf))
+    return f
+
+
+def _world(rec):
+    n = len(rec)
+    world, o, d, time, tmin, tmax = rec[:, 0].astype(int), rec[:, 1:4], rec[:, 4:7], rec[:, 7], rec[:, 8], rec[:, 9]
+    med, hit, t, obj, p = rec[:, 10] != 0, rec[:, 11] == 1, rec[:, 12], rec[:, 13].astype(int), rec[:, 14:17]
+    z = lambda: np.zeros(n, bool)  # noqa: E731
+    big = F(np.finfo(np.float32).max)
+    fin_d = np.isfinite(d).all(axis=1)
+    zero = (d == 0) & fin_d[:, None]
+    run_w, bvh_w = np.isin(world, (1, 2, 3)), world >= 4
+    tang = {10: z(), 1000: z(), 100000: z()}
+    tang_pos, tang_neg = {k: z() for k in tang}, {k: z() for k in tang}
+    dup_ray, ulp_sides, mov_aim = z(), z(), z()
+    tiny, inside, dup_hit, root_tmin, root_tmax, between, late, in_plane = z(), np.zeros(n, int), z(), z(), z(), z(), z(), z()
+    rect_near, rect_between, mov_hit, rect_plane = z(), z(), z(), z()
+    o64, d64 = o.astype(np.float64), d.astype(np.float64)
+    for w, W in enumerate(world_scene()):
+        idx = np.flatnonzero((world == w) & fin_d)
+        for a, kk in W["rect_planes"]:
+            rect_plane[idx] |= zero[idx, a] & (o[idx, a] == F(kk))
+        if w not in (1, 2, 3) or not len(idx):
+            continue
+        sph = [(pos, kind, v) for pos, (kind, v) in enumerate(W["tops"]) if v is not None]
+        first_pos = min(pos for pos, _, _ in sph)
+        firsts = []  # per sphere: its first root above tmin and below tmax, float64
+        for pos, kind, v in sph:
+            if kind == "sphere":
+                c, r = np.array(v[:3]), v[3]
+                cc = np.broadcast_to(c, (len(idx), 3))
+            else:
+                c0, c1, t0, t1, r = np.array(v[:3]), np.array(v[3:6]), v[6], v[7], v[8]
+                if t0 == t1:
+                    continue
+                cc = c0 + ((time[idx, None].astype(np.float64) - t0) / (t1 - t0)) * (c1 - c0)
+            oc = o64[idx] - cc
+            with np.errstate(all="ignore"):
+                a_ = (d64[idx] ** 2).sum(1)
+                b_ = (oc * d64[idx]).sum(1)
+                c_ = (oc ** 2).sum(1) - r * r
+                disc = b_ * b_ - a_ * c_
+                sq = np.sqrt(np.where(disc > 0, disc, 0))
+                r1, r2 = (-b_ - sq) / a_, (-b_ + sq) / a_
+                impact = np.sqrt(np.maximum((oc ** 2).sum(1) - b_ * b_ / a_, 0))
+                dist = np.sqrt((oc ** 2).sum(1))
+                near = np.abs(impact - abs(r)) <= np.maximum(4e-7 * abs(r), 2.4e-7 * dist)  # a few ulps of r, or of the origin's coordinates
+                for k in tang:
+                    tang[k][idx] |= near & (dist > 0.3 * k) & (dist < 3 * k) & (abs(r) < 100)
+                if r == 0.02:
+                    tiny[idx] |= (impact < 0.03) & (dist >= 999)
+                inside[idx] += (dist < abs(r)) & (abs(r) < 100)
+                # float32 roots by sphere::hit's own arithmetic, for the equality classes (static spheres)
+                if kind == "sphere":
+                    ocf = o[idx] - c.astype(F)
+                    af, bf = _dot(d[idx], d[idx]), _dot(ocf, d[idx])
+                    cf = _dot(ocf, ocf) - F(r) * F(r)
+                    df = bf * bf - af * cf
+                    sf = np.sqrt(np.where(df > 0, df, F(0)))
+                    f1, f2 = (-bf - sf) / af, (-bf + sf) / af
+                    for k in tang:  # the float32 discriminant of sphere::hit on either side of 0
+                        at_k = near & (dist > 0.3 * k) & (dist < 3 * k) & (abs(r) < 100)
+                        tang_pos[k][idx] |= at_k & (df > 0)
+                        tang_neg[k][idx] |= at_k & ~(df > 0)
+                    for f in (f1, f2):
+                        ulp_sides[idx] |= (df > 0) & (np.nextafter(f, F(0)) == tmin[idx]) & (np.nextafter(f, big) == tmax[idx])
+                    root_tmin[idx] |= (df > 0) & ((f1 == tmin[idx]) | (f2 == tmin[idx]))
+                    root_tmax[idx] |= (df > 0) & ((f1 == tmax[idx]) | (f2 == tmax[idx]))
+                    for ax in range(3):
+                        for hi in (False, True):
+                            in_plane[idx] |= zero[idx, ax] & (o[idx, ax] == _sgroup_plane(v[ax], r, hi))
+                ok = disc > 0
+                v1 = np.where(ok & (r1 > tmin[idx]), r1, np.where(ok & (r2 > tmin[idx]), r2, np.inf))
+            firsts.append((pos, kind, tuple(v), v1))
+            if kind == "moving_sphere":
+                mov_hit[idx] |= hit[idx] & (obj[idx] == pos)
+                mov_aim[idx] |= np.isfinite(v1)
+        V = np.stack([f[3] for f in firsts], axis=1)
+        order = np.sort(V, axis=1)
+        with np.errstate(all="ignore"):
+            between[idx] = np.isfinite(order[:, 1]) & (tmax[idx] < big) & (order[:, 0] < tmax[idx]) & (tmax[idx] < order[:, 1])
+        pos_of = np.array([f[0] for f in firsts])
+        for j, (pos, kind, v, v1) in enumerate(firsts):
+            # from the inputs alone: this sphere's first root is the nearest of the run's roots below tmax,
+            # and a sphere earlier in the list has a farther one
+            with np.errstate(all="ignore"):
+                in_range = np.where(V < tmax[idx, None], V, np.inf)
+                nearest = np.isfinite(in_range[:, j]) & (in_range[:, j] == in_range.min(axis=1))
+                earlier_farther = (np.isfinite(in_range[:, :j]) & (in_range[:, :j] > in_range[:, j:j + 1])).any(axis=1)
+            late[idx] |= nearest & earlier_farther
+            twins = [i for i in range(len(firsts)) if i != j and firsts[i][1] == kind and firsts[i][2] == v]
+            if twins:
+                dup_ray[idx] |= np.isfinite(v1) & (v1 < tmax[idx])
+                dup_hit[idx] |= np.isfinite(v1) & (v1 < tmax[idx]) & hit[idx] & np.isin(obj[idx], pos_of[[j] + twins])
+        if w == 2:  # the xy_rect at z = 0 before the run: x in [-8, 8], y in [-3, 8]
+            with np.errstate(all="ignore"):
+                tr = -o64[idx, 2] / d64[idx, 2]
+                px, py = o64[idx, 0] + tr * d64[idx, 0], o64[idx, 1] + tr * d64[idx, 1]
+                on = (tr > 0.001) & (tr < tmax[idx]) & (px > -8) & (px < 8) & (py > -3) & (py < 8)
+                below = (V < tr[:, None]).sum(1)
+                some = np.isfinite(V).sum(1)
+            rect_near[idx] = on & (below == 0) & (some > 0)
+            rect_between[idx] = on & (below > 0) & (below < some)
+        assert first_pos >= 0
+    # object BVHs whose children no wrapper moves (world 4; world 5's triangles and duplicated spheres)
+    W4, W5 = world_scene()[4], world_scene()[5]
+    root_ulp, before_first, between_hits, back_tri, dup_child = z(), z(), z(), z(), z()
+    i4 = np.flatnonzero((world == 4) & fin_d)
+    for bp in W4["bvh_prims"]:  # the reference's root box of each of the four BVHs: the union of its children's
+        boxes = [_prim_box(kind, v) for kind, v in bp]
+        lo, hi = np.min([b[0] for b in boxes], axis=0), np.max([b[1] for b in boxes], axis=0)
+        for a in range(3):
+            root_ulp[i4] |= zero[i4, a] & ((o[i4, a] == np.nextafter(lo[a], F(-np.inf))) | (o[i4, a] == np.nextafter(hi[a], F(np.inf))))
+    ts = np.sort(_line_hits(W4["prims"], o64[i4], d64[i4], time[i4].astype(np.float64)), axis=1)
+    ts = np.where(ts > 0.001, ts, np.inf)
+    ts = np.sort(ts, axis=1)
+    with np.errstate(all="ignore"):
+        before_first[i4] = ~med[i4] & np.isfinite(ts[:, 0]) & (tmax[i4] > 0.001) & (tmax[i4] < ts[:, 0])
+        between_hits[i4] = ~med[i4] & np.isfinite(ts[:, 1]) & (tmax[i4] > ts[:, 0]) & (tmax[i4] < ts[:, 1]) & (ts[:, 0] < ts[:, 1])
+    for w, W in ((4, W4), (5, W5)):
+        iw = np.flatnonzero((world == w) & fin_d & med)
+        for kind, v in W["prims"]:
+            if kind != "triangle":
+                continue
+            th = _line_hits([(kind, v)], o64[iw], d64[iw], time[iw].astype(np.float64))[:, 0]
+            nrm = np.cross(np.array(v[3:6]) - np.array(v[0:3]), np.array(v[6:9]) - np.array(v[0:3]))
+            back_tri[iw] |= np.isfinite(th) & (th > 0) & ((d64[iw] * nrm[None]).sum(1) > 0)
+    i5 = np.flatnonzero((world == 5) & fin_d)
+    twice = [pv for pv in W5["prims"] if pv[0] == "sphere" and sum(q == pv for q in W5["prims"]) == 2]
+    if len(i5) and twice:
+        th = _line_hits(twice, o64[i5], d64[i5], time[i5].astype(np.float64))
+        dup_child[i5] = (np.isfinite(th) & (th > tmin[i5, None]) & (th < tmax[i5, None])).any(axis=1)
+    seen, on_surface, along_n = {}, z(), z()
+    for q in range(n):
+        was = seen.get((world[q], o[q].tobytes()))
+        on_surface[q] = was is not None
+        if was is not None:  # d parallel to the normal of a hit recorded at this point
+            for nn in was:
+                c = np.cross(d64[q], nn)
+                along_n[q] |= bool((c * c).sum() <= 1e-10 * (d64[q] ** 2).sum() * (nn ** 2).sum())
+        if hit[q] and np.isfinite(p[q]).all():
+            seen.setdefault((world[q], p[q].tobytes()), []).append(rec[q, 17:20].astype(np.float64))
+    with np.errstate(all="ignore"):
+        length = np.sqrt((d64 ** 2).sum(axis=1))
+        edge_pt = o64 + 8 * d64  # the constructed box-edge rays meet the edge at t = 8
+    lo5, hi5 = np.array([-5.0, -1.0, 2.0]), np.array([-3.0, 1.0, 4.0])
+    with np.errstate(all="ignore"):
+        on_bound = ((edge_pt == lo5) | (edge_pt == hi5)).sum(1)
+        in_box = ((edge_pt >= lo5) & (edge_pt <= hi5)).all(1)
+    nan_t = np.isnan(tmax)
+    fin_t = ~nan_t & (tmax < big)
+    dup5 = np.isin(obj, (38, 39, 42, 43))  # world 5's duplicated spheres: leaves 38, 39 and their copies 42, 43
+    out = {f"sphere run: near-tangent from about {k}": m & run_w for k, m in tang.items()}
+    out.update({f"sphere run: near-tangent from about {k}, float32 disc > 0": m & run_w for k, m in tang_pos.items()})
+    out.update({f"sphere run: near-tangent from about {k}, float32 disc <= 0": m & run_w for k, m in tang_neg.items()})
+    out.update({
+        "sphere run: a 0.02-radius sphere from >= 1e3 away": tiny,
+        "sphere run: a 0.02-radius sphere from >= 1e3 away, hit": tiny & hit,
+        "sphere run: origin inside one sphere": run_w & (inside == 1),
+        "sphere run: origin inside two spheres": run_w & (inside == 2),
+        "sphere run: origin inside three or more spheres": run_w & (inside >= 3),
+        "sphere run: the line meets a duplicated pair in range": dup_ray,
+        "sphere run: a duplicated pair is hit": dup_hit,
+        "sphere run: tmin and tmax an ulp to either side of a root": ulp_sides,
+        "sphere run: one zero component, the origin in a node box's face plane": in_plane & run_w & (zero.sum(axis=1) == 1),
+        "sphere run: two zero components, the origin in a node box's face plane": in_plane & run_w & (zero.sum(axis=1) == 2),
+        "sphere run: |d| < 0.03": run_w & fin_d & (length < 0.03),
+        "sphere run: |d| > 30": run_w & fin_d & (length > 30),
+        "sphere run: the line meets a moving sphere at time 0": mov_aim & (time == 0),
+        "sphere run: the line meets a moving sphere at time 1": mov_aim & (time == 1),
+        "sphere run: the line meets a moving sphere inside the shutter": mov_aim & (time > 0) & (time < 1),
+        "sphere run: a root == tmin": root_tmin,
+        "sphere run: a root == tmax": root_tmax,
+        "sphere run: tmax between two spheres' roots": between,
+        "sphere run: the nearest sphere is later in the list than a farther one the line meets": late,
+        "sphere run: the rect before the run is nearer than every root": rect_near,
+        "sphere run: the rect before the run lies between two roots": rect_between,
+        "sphere run: zero component with the origin in a node box's face plane": in_plane & run_w,
+        "sphere run: NaN in d": run_w & ~fin_d,
+        "sphere run: NaN tmax": run_w & nan_t,
+        "sphere run: |d| < 0.03, hit": run_w & hit & (length < 0.03),
+        "sphere run: |d| > 30, hit": run_w & hit & (length > 30),
+        "sphere run: a moving sphere wins at time 0": mov_hit & (time == 0),
+        "sphere run: a moving sphere wins at time 1": mov_hit & (time == 1),
+        "sphere run: a moving sphere wins inside the shutter": mov_hit & (time > 0) & (time < 1),
+        "object BVH: a duplicated child wins (equal t in two leaves)": (world == 5) & hit & ~med & dup5,
+        "object BVH: through a box edge inside a leaf": (world == 5) & in_box & (on_bound == 2),
+        "object BVH: the line meets a duplicated child in range": dup_child,
+        "object BVH: root box missed by an ulp of the origin, that component of d zero": root_ulp,
+        "object BVH: tmax before the first hit": before_first,
+        "object BVH: tmax between the first two hits": between_hits,
+        "object BVH: one zero component": bvh_w & (zero.sum(axis=1) == 1),
+        "object BVH: two zero components": bvh_w & (zero.sum(axis=1) == 2),
+        "object BVH: is_medium, the line meets a triangle child from behind": back_tri,
+        "origin on an earlier hit point, d along its normal": on_surface & along_n,
+        "origin on an earlier hit point, d not along its normal": on_surface & ~along_n,
+        "object BVH: a zero component, miss": bvh_w & zero.any(axis=1) & ~hit,
+        "object BVH: a zero component, hit": bvh_w & zero.any(axis=1) & hit,
+        "object BVH: finite tmax, miss": bvh_w & fin_t & ~hit,
+        "object BVH: finite tmax, hit": bvh_w & fin_t & hit,
+        "object BVH: NaN tmax": bvh_w & nan_t,
+        "object BVH: a ray in a rect's plane": bvh_w & rect_plane,
+        "object BVH: is_medium, hit": bvh_w & med & hit,
+        "object BVH: is_medium, tmin = -FLT_MAX": bvh_w & med & (tmin == -big),
+        "origin on an earlier hit point": on_surface,
+        "origin on an earlier hit point, hit": on_surface & hit,
+        "time inside the shutter": (time > 0) & (time <= 1),
+    })
+    for w in range(7):
+        out[f"world {w}"] = world == w
+        out[f"world {w}, hit"] = (world == w) & hit
+    return out
+
+
+# The world KAT's classes are held to the number of records its generator constructs for them
+# (oracle/ref/kat.inc kat_world_record: blocks of 32, a block split k ways gives 32 / k, rounded
+# down; 64 origin-reuse records in two halves); every other class to test_kat_edges' 8.
+# The sign of the float32 discriminant of a near-tangent ray is decided by rounding, not by
+# construction: each sign must be present at each distance.
+WORLD_MIN = {
+    "sphere run: near-tangent from about 10": 10, "sphere run: near-tangent from about 1000": 10,
+    "sphere run: near-tangent from about 100000": 10,
+    **{f"sphere run: near-tangent from about {k}, float32 disc {sg} 0": 1 for k in (10, 1000, 100000) for sg in (">", "<=")},
+    "sphere run: a 0.02-radius sphere from >= 1e3 away": 32,
+    "sphere run: origin inside one sphere": 8, "sphere run: origin inside two spheres": 8,
+    "sphere run: origin inside three or more spheres": 16,
+    "sphere run: the line meets a duplicated pair in range": 32,
+    "sphere run: a root == tmin": 8, "sphere run: a root == tmax": 8, "sphere run: tmax between two spheres' roots": 8,
+    "sphere run: tmin and tmax an ulp to either side of a root": 8,
+    "sphere run: the nearest sphere is later in the list than a farther one the line meets": 32,
+    "sphere run: the rect before the run is nearer than every root": 16,
+    "sphere run: the rect before the run lies between two roots": 16,
+    "sphere run: zero component with the origin in a node box's face plane": 32,
+    "sphere run: one zero component, the origin in a node box's face plane": 18,
+    "sphere run: two zero components, the origin in a node box's face plane": 14,
+    "sphere run: NaN in d": 16, "sphere run: NaN tmax": 16,
+    "sphere run: |d| < 0.03": 10, "sphere run: |d| > 30": 8,
+    "sphere run: the line meets a moving sphere at time 0": 8, "sphere run: the line meets a moving sphere at time 1": 16,
+    "sphere run: the line meets a moving sphere inside the shutter": 8,
+    "object BVH: the line meets a duplicated child in range": 16, "object BVH: through a box edge inside a leaf": 16,
+    "object BVH: root box missed by an ulp of the origin, that component of d zero": 32,
+    "object BVH: tmax before the first hit": 16, "object BVH: tmax between the first two hits": 16,
+    "object BVH: one zero component": 8, "object BVH: two zero components": 8, "object BVH: NaN tmax": 8,
+    "object BVH: a ray in a rect's plane": 8,
+    "object BVH: is_medium, the line meets a triangle child from behind": 32,
+    "object BVH: is_medium, tmin = -FLT_MAX": 16,
+    "origin on an earlier hit point": 64,
+    "origin on an earlier hit point, d along its normal": 32, "origin on an earlier hit point, d not along its normal": 32,
+}
+MIN_COUNTS = {"world": WORLD_MIN}
+
+_CLASSIFIERS = {"world": _world, "mesh": _mesh, "sphere": _sphere, "moving_sphere": _moving_sphere, "rect": _rect, "box": _box, "xform": _xform,
                 "medium": _medium, "isotropic": _isotropic, "texture_checker": _texture_checker,
                 "texture_noise": _texture_noise, "texture_image": _texture_image}
 

@@ -73,8 +73,8 @@ def read_kat(name: str):
 
 def replay_kat(name: str, rec: np.ndarray) -> np.ndarray:
     out = np.ascontiguousarray(rec.copy())
-    if name == "mesh":  # replayed over the fixture meshes
-        with open(os.path.join(GOLDEN, "kat_mesh.scene"), "rb") as f:
+    if name in ("mesh", "world"):  # replayed over the fixture meshes / worlds
+        with open(os.path.join(GOLDEN, f"kat_{name}.scene"), "rb") as f:
             if lib().oracle_kat_scene(f.read()) != 0:
                 raise RuntimeError(lib().oracle_last_error().decode())
     rc = lib().oracle_kat(name.encode(), out.shape[0], out.shape[1], _p(out))

@@ -1,8 +1,9 @@
 """The edge cases the scene KATs were built for are really in the committed
-files.  Every record of tests/golden/kat_{sphere ... texture_image, mesh}.bin is
+files.  Every record of tests/golden/kat_{sphere ... texture_image, mesh, world}.bin is
 classified from its inputs and the reference's outputs alone (tests/kat_classes.py:
 float32 arithmetic in numpy, no device and no restatement code): each class of the
-issue's table holds at least 8 records, and each KAT with a hit flag has between a
+issue's table holds at least 8 records (a class of the world KAT: the number of records
+its generator constructs for it, kat_classes.WORLD_MIN), and each KAT with a hit flag has between a
 quarter and three quarters of hits.  This is what lets the bit-exact comparisons
 (test_oracle_pins.py, test_device_kat.py) fail where the code can go wrong."""
 import numpy as np
@@ -20,7 +21,10 @@ def test_kat_edge_classes_populated():
         assert 512 <= len(rec) <= 1024, (name, len(rec))
         counts = {k: int(m.sum()) for k, m in kc.classify(name, rec).items()}
         report.append(f"{name} ({len(rec)} records): " + ", ".join(f"{k}: {v}" for k, v in counts.items()))
-        short += [f"{name}: {k}: {v}" for k, v in counts.items() if v < MIN_PER_CLASS]
+        need = kc.MIN_COUNTS.get(name, {})  # (the world KAT: the counts its generator constructs, kat_classes.WORLD_MIN)
+        assert set(need) <= set(counts), (name, set(need) - set(counts))
+        short += [f"{name}: {k}: {v} < {need.get(k, MIN_PER_CLASS)}" for k, v in counts.items()
+                  if v < need.get(k, MIN_PER_CLASS)]
         if name in kc.HIT:
             flag = rec[:, kc.HIT[name]]
             assert np.isin(flag, (0.0, 1.0)).all(), name
@@ -32,5 +36,10 @@ def test_kat_edge_classes_populated():
             bad = kc.mesh_nan_waves(rec)
             if bad:
                 short.append(f"mesh: records {bad} onwards: a wave of 64 with NaN bounds only")
+        if name == "world":  # the share of records the device test compares on hit and t alone is capped
+            share = float(kc.world_t_only(rec).mean())
+            report.append(f"world: hit-and-t-only records {share:.3f}")
+            if share > kc.WORLD_T_ONLY_CAP:
+                short.append(f"world: {share:.3f} of the records compare hit and t only (cap {kc.WORLD_T_ONLY_CAP})")
     print("\n".join(report))
-    assert not short, "classes with fewer than 8 records, or a hit fraction outside [0.25, 0.75]: " + "; ".join(short)
+    assert not short, "classes with fewer records than required, or a hit fraction outside [0.25, 0.75]: " + "; ".join(short)
