@@ -481,6 +481,27 @@ int srr_device_world_kat(const char* scene_text, int tables, int n, int width, f
  * world tables (staged in LDS up to 8 KiB). */
 int srr_world_kat_counts(const char* scene_text, int world, int32_t* counts);
 
+/* Test infrastructure: one shading bounce on the `bounce` KAT's records (width 43:
+ * l m p(3) n(3) u v o(3) d(3) time depth maxDepth lcg(2) pcg(4) | scattered
+ * origin(3) dir(3) time colour(3) attempts lcg(2) pcg(4); layouts and the fixture
+ * scene: tests/golden/README.md).  Text object 200000 + l of scene_text, a list, is
+ * light list l, and material m is the scene's m-th `mat` line (every material must
+ * be placed in the world, so that flattening keeps it).  Each light list that a
+ * record names is flattened and uploaded with the scene's materials and textures
+ * exactly as a render would, and one kernel per list runs its records: variant 0
+ * through the wavefront engine's family_of, hit_emitted and scatter<family>, variant
+ * 1 with diffuse records going through the path kernel's split bounce (set-up,
+ * bsdf_dead, one skip_mixture round, coop_mixture with deep_tries, record), 64
+ * records to a wave.  colour is the bounce record folded over a white next colour
+ * as the path kernel folds it (a terminal record: its emission).  The attempts
+ * column is left as it is.  Outputs are written in place.  Needs a GPU. */
+int srr_device_bounce_kat(const char* scene_text, int variant, int deep_tries, int n, int width, float* records);
+
+/* Test infrastructure, no GPU: how light list `list` of a bounce-KAT scene
+ * flattens.  counts[0] lights, counts[1 + k] those of LightKind k (0 none: pdf 0
+ * and no draws, 1 xz_rect, 2 sphere, 3 triangle), counts[5] materials kept. */
+int srr_bounce_kat_counts(const char* scene_text, int list, int32_t* counts);
+
 /* Test infrastructure: one math routine of the device build over n elements
  * (host buffers; one thread per element).  float elements: the wrappers the
  * kernels call, "rsin", "rcos", "rexp", "rlog", "rpow" (x, y), "racos", "rasin",

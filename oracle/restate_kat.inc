@@ -109,9 +109,79 @@ static void kat_scene(const std::string& text) {
     }
 }
 
+// the bounce KAT's probe world (oracle/ref/kat.inc KatBounceProbe): the first hit() hands color() the
+// record's hit, the second keeps the scattered ray and answers with a white emitter facing it
+struct KatBounceProbe : Hitable {
+  Hit first;
+  const Material* white;
+  mutable int calls = 0;
+  mutable Ray second;
+  bool hit(const Ray& r, float, float, Hit& rec, bool) const override {
+    if (calls++ == 0) { rec = first; return true; }
+    second = r;
+    rec.t = 1;
+    rec.p = r.at(1);
+    rec.normal = -r.B;
+    rec.u = rec.v = 0;
+    rec.mat = white;
+    return true;
+  }
+  bool bbox(float, float, AABB&) const override { return false; }
+};
+
+// ... and its light list (KatBounceLights): pdf_value is called once per mixture attempt
+struct KatBounceLights : List {
+  const List* in;
+  mutable int calls = 0;
+  explicit KatBounceLights(const List* p) : in(p) { l = p->l; }
+  float pdf_value(const V& o, const V& v) const override {
+    ++calls;
+    return in->pdf_value(o, v);
+  }
+  V random(const V& o) const override { return in->random(o); }
+};
+
 static int kat_one(const std::string& name, float* r) {
   float* o;
-  if (name == "mesh") {
+  if (name == "bounce") {
+    // in: l m p n u v o d time depth maxDepth lcg pcg | out: scattered origin dir time colour attempts lcg pcg
+    static const ConstTex one(V(1, 1, 1));
+    static DiffuseLight white;
+    white.emit = &one;
+    if (!g_kat_scene) return -1;
+    const auto li = g_kat_scene->obj.find(200000 + (long long)r[0]);
+    const auto mi = g_kat_scene->mat.find((long long)r[1]);
+    if (li == g_kat_scene->obj.end() || mi == g_kat_scene->mat.end() || !dynamic_cast<const List*>(li->second)) return -1;
+    KatBounceProbe probe;
+    probe.white = &white;
+    probe.first.t = 1;
+    probe.first.p = rd3(r + 2);
+    probe.first.normal = rd3(r + 5);
+    probe.first.u = r[8];
+    probe.first.v = r[9];
+    probe.first.mat = mi->second;
+    Scene S;
+    S.world = &probe;
+    const KatBounceLights lights(dynamic_cast<const List*>(li->second));
+    S.lights = &lights;
+    R.lcg = rd_lcg(r + 19);
+    R.pcg = rd_pcg(r + 21);
+    R.inc = 0xda3e39cb94b95bdbULL;
+    int depth = (int)r[17];
+    const V col = color(S, Ray(rd3(r + 10), rd3(r + 13), r[16]), &depth, (int)r[18]);
+    const bool sc = probe.calls == 2;
+    o = r + 25;
+    *o++ = sc ? 1.f : 0.f;
+    wr3(o, sc ? probe.second.A : V(0.f));
+    wr3(o, sc ? probe.second.B : V(0.f));
+    *o++ = sc ? probe.second.tm : 0;
+    wr3(o, col);
+    *o++ = (float)lights.calls;  // attempts
+    wr_lcg(o, R.lcg);
+    wr_pcg(o, R.pcg);
+    for (float* c = r + 25; c < o; ++c)  // NaN outputs are canonical in the file (kat.inc kat_bounce_record)
+      if (*c != *c) { const uint32_t u = 0x7fc00000u; std::memcpy(c, &u, 4); }
+  } else if (name == "mesh") {
     // in: mesh o d tmin tmax is_medium | out: hit t tri p n u v
     const int mi = (int)r[0];
     if (mi < 0 || mi >= (int)g_kat_meshes.size()) return -1;

@@ -1439,6 +1439,104 @@ int srr_device_world_kat(const char* scene_text, int tables, int n, int width, f
   return 0;
 }
 
+}  // extern "C"
+
+namespace {
+constexpr long long kBounceKatBaseId = 200000;  // text obj 200000 + l is light list l of the `bounce` KAT's scene
+
+// The scene flattened as a render of it with light list l would be.  Every material of the
+// scene must survive flattening (each is placed in the world), so that material m of a record
+// is row m of the device table.
+int bounce_kat_flatten(Scene& sc, int l, Flat& f, std::string& err) {
+  int h = -1;
+  for (auto& kv : sc.text_ids)
+    if (kv.first == kBounceKatBaseId + l) h = kv.second;
+  if (!sc.valid_obj(h) || sc.obj[h].kind != H_LIST) {
+    err = "bounce KAT: no list object " + std::to_string(kBounceKatBaseId + l);
+    return SRR_EINVAL;
+  }
+  sc.lights = h;
+  const int rc = flatten(sc, f, err);
+  if (rc < 0) return rc;
+  if (f.mats.size() != sc.mat.size()) {
+    err = "bounce KAT: a material of the scene is not placed in its world";
+    return SRR_EINVAL;
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int srr_bounce_kat_counts(const char* scene_text, int list, int32_t* counts) {
+  if (!scene_text || !counts || list < 0) return fail(SRR_EINVAL, "bad bounce KAT arguments");
+  Scene sc;
+  std::string err;
+  int rc = scene_from_text(scene_text, sc, err);
+  if (rc < 0) return fail(rc, err);
+  Flat f;
+  if ((rc = bounce_kat_flatten(sc, list, f, err)) < 0) return fail(rc, err);
+  for (int k = 0; k < 6; ++k) counts[k] = 0;
+  counts[0] = (int32_t)f.lights.size();
+  for (const DLight& L : f.lights) {
+    if (L.kind < LIGHT_NONE || L.kind > LIGHT_TRI) return fail(SRR_EINVAL, "bounce KAT: a light of an unknown kind");
+    ++counts[1 + L.kind];
+  }
+  counts[5] = (int32_t)f.mats.size();
+  return 0;
+}
+
+int srr_device_bounce_kat(const char* scene_text, int variant, int deep_tries, int n, int width, float* records) {
+  // every argument is checked before the first HIP call
+  if (!scene_text || !records || n <= 0 || n > 1 << 20 || width != kBounceKatWidth || variant < 0 || variant > 1 ||
+      deep_tries < 0)
+    return fail(SRR_EINVAL, "bad bounce KAT arguments");
+  Scene sc;
+  std::string err;
+  int rc = scene_from_text(scene_text, sc, err);
+  if (rc < 0) return fail(rc, err);
+  std::map<int, std::vector<int>> by_list;  // a launch holds the records of one light list (a wave keeps their order)
+  for (int q = 0; q < n; ++q) {
+    const float* r = records + (size_t)q * width;
+    if (!(r[0] >= 0 && r[0] < 1024.f && r[0] == (float)(int)r[0])) return fail(SRR_EINVAL, "bounce KAT: a record names no light list");
+    if (!(r[1] >= 0 && r[1] < (float)sc.mat.size() && r[1] == (float)(int)r[1]))
+      return fail(SRR_EINVAL, "bounce KAT: a record names no material");
+    if (!(r[17] >= 0 && r[17] <= 1e6f && r[18] >= 0 && r[18] <= 1e6f)) return fail(SRR_EINVAL, "bounce KAT: a record's depth is out of range");
+    by_list[(int)r[0]].push_back(q);
+  }
+  std::map<int, Flat> flats;
+  for (auto& kv : by_list)
+    if ((rc = bounce_kat_flatten(sc, kv.first, flats[kv.first], err)) < 0) return fail(rc, err);
+  for (auto& kv : by_list) {
+    const std::vector<int>& idx = kv.second;
+    std::vector<float> rec(idx.size() * (size_t)width);
+    for (size_t i = 0; i < idx.size(); ++i)
+      std::memcpy(&rec[i * width], &records[(size_t)idx[i] * width], width * sizeof(float));
+    srr_renderer* r = nullptr;  // uploads the tables exactly as a render does
+    if ((rc = renderer_create_flat(flats[kv.first], 0, &r, err)) < 0) return fail(rc, err);
+    std::unique_ptr<srr_renderer> keep(r);
+    float* d_rec = nullptr;
+    const size_t rb = rec.size() * sizeof(float);
+    rc = 0;
+    if (hipMalloc((void**)&d_rec, rb) != hipSuccess) rc = fail(SRR_ENOMEM, "device allocation failed");
+    if (!rc && hipMemcpy(d_rec, rec.data(), rb, hipMemcpyHostToDevice) != hipSuccess) rc = fail(SRR_EIO, "copy to device failed");
+    BounceKatArgs A{};
+    A.n = (int)idx.size();
+    A.width = width;
+    A.rec = d_rec;
+    A.variant = variant;
+    A.deep_tries = deep_tries;
+    if (!rc && launch_bounce_kat(r->view, A) < 0) rc = fail(SRR_EIO, "bounce KAT kernel launch failed");
+    if (!rc && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(rec.data(), d_rec, rb, hipMemcpyDeviceToHost) != hipSuccess))
+      rc = fail(SRR_EIO, "bounce KAT kernel failed");
+    (void)hipFree(d_rec);
+    if (rc) return rc;
+    for (size_t i = 0; i < idx.size(); ++i)
+      std::memcpy(&records[(size_t)idx[i] * width], &rec[i * width], width * sizeof(float));
+  }
+  return 0;
+}
+
 int srr_device_libm(const char* fn, int64_t n, const void* x, const void* y, void* out0, void* out1) {
   // every argument is checked before the first HIP call, so a refusal needs no GPU
   // (tests/test_device_libm.py test_unknown_names_are_refused runs without one)

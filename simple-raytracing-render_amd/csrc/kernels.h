@@ -327,6 +327,21 @@ struct WorldKatArgs {
 // 0, -1 (bad arguments, nothing launched) or -5 (launch failed); tables: 0 global, 1 staged in LDS
 // (S.world_words * 16 <= kPathsWorldLdsBytes)
 int launch_world_kat(const SceneView& S, int tables, const WorldKatArgs& A);
+// the bounce KAT (srr_device_bounce_kat, kernels.hip k_bounce_kat): one shading bounce per record over
+// the one uploaded light list; variant 0 the wavefront engine's family_of / hit_emitted / scatter<family>,
+// variant 1 k_paths' split diffuse bounce (skip_mixture, then coop_mixture with deep_tries) for diffuse
+// records with lights
+// l m p(3) n(3) u v o(3) d(3) time depth maxDepth lcg(2) pcg(4) | scattered origin(3) dir(3) time colour(3)
+// attempts lcg(2) pcg(4)
+constexpr int kBounceKatWidth = 43;
+struct BounceKatArgs {
+  int n, width;  // records, all of the uploaded light list; material m of a record is row m of SceneView::mats
+  float* rec;    // device records, outputs written in place (the attempts column is left alone)
+  int variant;
+  int deep_tries;
+};
+// 0, -1 (bad arguments, nothing launched) or -5 (launch failed)
+int launch_bounce_kat(const SceneView& S, const BounceKatArgs& A);
 // device libm sweeps (srr_device_libm): routine kLibmFns[fn] over n elements, one per
 // thread; device pointers (d_y / d_out1 unused unless n_in / n_out is 2).  The switches
 // of kernels.hip k_libm_f32 / k_libm_f64 go by LibmId, and row i of the table is id i

@@ -3594,6 +3594,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
           C = hit_emitted(S, h.mat, r.d, h.p, h.n, h.u, h.v);
         } else if ((!ALLFAM || fam == FAM_DIFF) && S.n_lights > 0) {
           // scatter<FAM_DIFF> up to its resampling loop (Raytracing_n.cpp:73-75)
+          // (k_bounce_kat, the bounce KAT's kernel, restates these lines: keep the two alike)
           const DMat M = S.mats[h.mat];
           d_atten = tex_value(S, M.tex, h.u, h.v, h.p);
           Bsdf f;
@@ -3663,7 +3664,7 @@ __global__ void __launch_bounds__(BS, MINB) SRR_PATHS_VGPR_ATTR k_paths(PathsArg
       }
       max_rounds = max(max_rounds, (uint32_t)rounds);
     }
-    if (diff) {  // the rest of scatter<FAM_DIFF>: scattering_pdf and the record
+    if (diff) {  // the rest of scatter<FAM_DIFF>: scattering_pdf and the record (restated in k_bounce_kat: keep alike)
       const PathWork W = work();
       if (d_pdf == 0) n_events += kCapped;  // the loop reached kMixtureGuard
       float c = dot(d_n, unit_vector(d_dir));  // material.h:100-105, 134-138
@@ -4649,6 +4650,98 @@ __global__ void __launch_bounds__(kTraceBlock) k_world_kat(SceneView S0, WorldKa
   for (int k = 0; k < 11; ++k) r[11 + k] = out[k];
 }
 
+// Test infrastructure (srr_device_bounce_kat): one shading bounce on the reference's `bounce`
+// KAT records (tests/golden/README.md), one record per lane, all of the one uploaded light
+// list.  in: l m p n u v o d time depth maxDepth lcg pcg | out: scattered, the new ray's
+// origin, direction and time, the bounce record folded over a white next colour as k_paths
+// folds it (0 + (a * (1,1,1)) / w, or a * (1,1,1) under kSpecMark; a terminal hit: its
+// emission), the attempts column left as it is, the LCG and PCG states after.
+// VARIANT 0: family_of, then hit_emitted or scatter<family> -- the wavefront engine's code.
+// VARIANT 1: a diffuse record with lights runs k_paths' split bounce instead: the set-up
+// below restates the lines that sit inline in k_paths' shade step ("scatter<FAM_DIFF> up to
+// its resampling loop" and "the rest of scatter<FAM_DIFF>"; keep the two alike), around the
+// same diff_setup, bsdf_dead, skip_mixture(.., 1) and coop_mixture calls over the whole wave;
+// lanes past the last record stay in the wave with nothing pending, as finished paths do.
+template <int VARIANT>
+__global__ void __launch_bounds__(kTraceBlock) k_bounce_kat(SceneView S, BounceKatArgs A) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = q < A.n;
+  float* r = A.rec + (size_t)(live ? q : 0) * A.width;
+  const int mat = (int)r[1];
+  const V3 hp = kat3(r + 2), hn = kat3(r + 5);
+  const float hu = r[8], hv = r[9];
+  const Ray ray{kat3(r + 10), kat3(r + 13), r[16]};
+  const int depth = (int)r[17], max_depth = (int)r[18];
+  Rng rng{kat_lcg(r + 19), kat_pcg(r + 21)};
+  const int fam = live ? family_of(mat, mat >= 0 ? S.mats[mat].kind : -1, depth, max_depth) : -1;
+  bool scattered = false, sp = false;
+  V3 nd = v3(0.f), C = v3(0.f);
+  float nt = 0;
+  float4 rec = make_float4(0, 0, 0, 0);
+  bool diff = false, pend = false;
+  DiffSetup ds{};
+  V3 d_atten = v3(0.f), d_n = v3(0.f), d_dir = v3(0.f);
+  float d_pdf = 0;
+  int d_tries = 0;
+  bool d_dead = false;
+  if (fam == FAM_TERM) {
+    C = hit_emitted(S, mat, ray.d, hp, hn, hu, hv);
+  } else if (fam >= 0) {
+    const DMat M = S.mats[mat];
+    if (VARIANT == 1 && fam == FAM_DIFF && S.n_lights > 0) {
+      // scatter<FAM_DIFF> up to its resampling loop, as k_paths has it
+      d_atten = tex_value(S, M.tex, hu, hv, hp);
+      Bsdf f;
+      f.kind = M.kind;
+      f.n = hn;
+      f.uvw = onb_from_w(hn);
+      f.A = M.p[0];
+      f.B = M.p[1];
+      bsdf_prepare<false>(f, ray.d);
+      ds = diff_setup(f, hp);
+      d_dead = bsdf_dead(S, f, hp);
+      (void)drand(rng);  // mixture_pdf ctor (pdf.h:175)
+      d_n = hn;
+      diff = pend = true;
+    } else {
+      if (fam == FAM_DIFF) scatter<FAM_DIFF>(S, M, ray.d, ray.tm, hp, hn, hu, hv, rng, rec, sp, nd, nt);
+      else if (fam == FAM_BECK) scatter<FAM_BECK>(S, M, ray.d, ray.tm, hp, hn, hu, hv, rng, rec, sp, nd, nt);
+      else scatter<FAM_SPEC>(S, M, ray.d, ray.tm, hp, hn, hu, hv, rng, rec, sp, nd, nt);
+      scattered = true;
+    }
+  }
+  if (VARIANT == 1) {
+    if (__ballot(pend)) {
+      skip_mixture(S, ds, d_dead, pend, d_tries, rng.lcg, d_dir, d_pdf, 1);
+      if (__ballot(pend)) coop_mixture(S, ds, pend, d_tries, rng.lcg, d_dir, d_pdf, A.deep_tries);
+    }
+    if (diff) {  // the rest of scatter<FAM_DIFF>, as k_paths has it: scattering_pdf and the record
+      float c = dot(d_n, unit_vector(d_dir));  // material.h:100-105, 134-138
+      if (c < 0) c = 0;
+      const V3 as = d_atten * (c / kPi);
+      rec = make_float4(as.x, as.y, as.z, d_pdf);
+      nd = d_dir;
+      nt = ray.tm;
+      scattered = true;
+    }
+  }
+  if (!live) return;
+  if (scattered) {  // k_paths' fold of this record over a next colour of (1, 1, 1)
+    const V3 av = v3(rec.x, rec.y, rec.z);
+    C = v3(1, 1, 1);
+    if (__float_as_uint(rec.w) == kSpecMark) C = av * C;
+    else C = v3(0.f) + (av * C) / rec.w;
+  }
+  float* o = r + 25;
+  o[0] = scattered ? 1.f : 0.f;
+  kat_put3(o + 1, scattered ? hp : v3(0.f));
+  kat_put3(o + 4, nd);
+  o[7] = nt;
+  kat_put3(o + 8, C);
+  kat_put_lcg(o + 12, rng.lcg);
+  kat_put_pcg(o + 14, rng.pcg);
+}
+
 // Test infrastructure (srr_device_libm): one libm routine of the device build over
 // an array, one element per thread.  fn is a LibmId (kernels.h).  The f32 entries are
 // the devmath.h wrappers the kernels call; the f64 ones the restatement of glibc's
@@ -5042,6 +5135,14 @@ int launch_world_kat(const SceneView& S, int tables, const WorldKatArgs& A) {
   const dim3 g((A.n + dev::kTraceBlock - 1) / dev::kTraceBlock), b(dev::kTraceBlock);
   if (tables == 1) hipLaunchKernelGGL((dev::k_world_kat<dev::TR_BVH4_PRUNE | dev::TR_WL>), g, b, 0, 0, S, A);
   else hipLaunchKernelGGL((dev::k_world_kat<dev::TR_BVH4_PRUNE>), g, b, 0, 0, S, A);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+int launch_bounce_kat(const SceneView& S, const BounceKatArgs& A) {
+  if (A.n <= 0 || A.width != kBounceKatWidth || !A.rec || A.variant < 0 || A.variant > 1 || A.deep_tries < 0) return -1;
+  const dim3 g((A.n + dev::kTraceBlock - 1) / dev::kTraceBlock), b(dev::kTraceBlock);
+  if (A.variant == 1) hipLaunchKernelGGL((dev::k_bounce_kat<1>), g, b, 0, 0, S, A);
+  else hipLaunchKernelGGL((dev::k_bounce_kat<0>), g, b, 0, 0, S, A);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

@@ -440,6 +440,29 @@ def world_kat_counts(scene_text: str, world: int) -> dict:
     return dict(objects=int(c[0]), sgroups=int(c[1]), obvhs=int(c[2]), leaves=int(c[3]), table_bytes=int(c[4]))
 
 
+def device_bounce_kat(scene_text: str, rec: np.ndarray, variant: int, deep_tries: int = 32) -> np.ndarray:
+    """srr_device_bounce_kat (test infrastructure): the `bounce` KAT's records with the
+    outputs of one shading bounce; variant 0 the wavefront engine's scatter, 1 the path
+    kernel's split diffuse bounce with its wave-cooperative mixture loop."""
+    L = lib()
+    L.srr_device_bounce_kat.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_void_p]
+    out = np.ascontiguousarray(rec, np.float32).copy()
+    _check(L.srr_device_bounce_kat(scene_text.encode(), variant, deep_tries, out.shape[0], out.shape[1], _ptr(out)))
+    return out
+
+
+def bounce_kat_counts(scene_text: str, light_list: int) -> dict:
+    """srr_bounce_kat_counts (test infrastructure, no GPU): how a light list of the
+    `bounce` KAT's scene flattens."""
+    L = lib()
+    L.srr_bounce_kat_counts.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p]
+    c = np.zeros(6, np.int32)
+    _check(L.srr_bounce_kat_counts(scene_text.encode(), light_list, _ptr(c)))
+    return dict(lights=int(c[0]), none=int(c[1]), xz_rect=int(c[2]), sphere=int(c[3]), triangle=int(c[4]),
+                materials=int(c[5]))
+
+
 def write_ppm(path: str, nx: int, ny: int, img8: np.ndarray) -> None:
     img8 = np.ascontiguousarray(img8, np.uint8)
     _check(lib().srr_write_ppm(path.encode(), nx, ny, _ptr(img8)))

@@ -51,7 +51,10 @@ KATS = [("erf", 512), ("beckmann11", 512), ("beckmann_dist", 512), ("beckmann_pd
         # the mesh walk: bvh_node::hit over the ten meshes of kat_mesh.scene (README.md)
         ("mesh", 1024),
         # the world-list walk: hitable_list::hit over the seven worlds of kat_world.scene (README.md)
-        ("world", 1024)]
+        ("world", 1024),
+        # one shading bounce: the reference's color() over a probe world, the light lists and the
+        # materials of kat_bounce.scene (README.md)
+        ("bounce", 1536)]
 
 
 # The MERL KATs' out == in records are decided by the last-ulp rounding of glibc's
@@ -302,6 +305,68 @@ def make_world_kat(n):
     run("kat", "world", n, 1234567, os.path.join(HERE, "kat_world.bin"), WORLD_SCENE)
 
 
+BOUNCE_SCENE = os.path.join(HERE, "kat_bounce.scene")
+# the light lists of the `bounce` KAT: obj 200000 + l (README.md has the table)
+BOUNCE_LIGHT = "xz_rect 213.0 343.0 227.0 332.0 554.0 -1"
+BOUNCE_SPHERE = "sphere 278.0 300.0 280.0 60.0 -1"
+BOUNCE_TRI = "triangle 150.0 500.0 150.0 400.0 520.0 180.0 260.0 540.0 420.0 -1"
+
+
+def bounce_scene_text():
+    """Textures, materials (mat m is material m of a record; one placed sphere each, so
+    that flattening keeps them all) and the nine light lists of the `bounce` KAT."""
+    out = ["srr_scene 1", "# the `bounce` KAT's materials and light lists (README.md): obj 200000 + l is light list l",
+           "tex 0 const 0.73 0.73 0.73", "tex 1 const 0.2 0.3 0.1", "tex 2 const 0.9 0.9 0.9", "tex 3 checker 1 2",
+           "tex 4 image_gen 7 5 7 0", "tex 5 const 4.0 3.0 2.0",
+           "mat 0 lambertian 0", "mat 1 lambertian 3", "mat 2 lambertian 4",
+           "mat 3 orennayar 0 0.0", "mat 4 orennayar 0 20.0", "mat 5 orennayar 0 90.0",
+           "mat 6 beckmann 0 0.01 0.01", "mat 7 beckmann 0 0.5 0.5", "mat 8 beckmann 0 0.1 0.9",
+           "mat 9 metal 0.8 0.85 0.88 0.0", "mat 10 metal 0.8 0.85 0.88 0.3", "mat 11 metal 0.8 0.85 0.88 1.5",
+           "mat 12 dielectric 1.0", "mat 13 dielectric 1.5", "mat 14 dielectric 2.4",
+           "mat 15 isotropic 3", "mat 16 diffuse_light 5"]
+    n_mat = 17
+    for m in range(n_mat):
+        out.append(f"obj {m} sphere {2000.0 + 10.0 * m!r} 0.0 0.0 1.0 {m}")
+    out.append(f"obj 300000 list {n_mat} " + " ".join(map(str, range(n_mat))))
+    nid = [1000]
+
+    def obj(text):
+        out.append(f"obj {nid[0]} {text}")
+        nid[0] += 1
+        return nid[0] - 1
+
+    def flip(k):
+        return obj(f"flip {k}")
+
+    none = ["xy_rect 0.0 555.0 0.0 555.0 555.0 -1", "yz_rect 0.0 555.0 0.0 555.0 555.0 -1",
+            "box 130.0 0.0 65.0 295.0 165.0 230.0 -1"]
+    lists = [
+        [flip(obj(BOUNCE_LIGHT))],
+        [flip(obj(BOUNCE_LIGHT)), obj(BOUNCE_SPHERE), obj(BOUNCE_TRI)],
+        [obj(BOUNCE_SPHERE)],
+        [obj(none[0]), flip(obj(BOUNCE_LIGHT))],
+        [obj(none[1]), obj(none[2])],
+        [],
+        [obj(BOUNCE_LIGHT), obj("xz_rect 213.0 343.0 227.0 332.0 1.0 -1")],
+        # five lights, the first and the fourth equal; the small triangle lies in the plane y = 300
+        [flip(obj(BOUNCE_LIGHT)), obj(BOUNCE_SPHERE), obj("triangle 100.0 300.0 100.0 104.0 300.0 100.0 100.0 300.0 104.0 -1"),
+         flip(obj(BOUNCE_LIGHT)), obj(BOUNCE_TRI)],
+        [obj(none[0]), obj(none[1]), obj(none[2]), obj(none[0]), flip(obj(BOUNCE_LIGHT)), obj(none[1]), obj(none[2]),
+         obj(none[0])],
+    ]
+    for l, kids in enumerate(lists):
+        out.append(f"obj {200000 + l} list {len(kids)}" + "".join(f" {k}" for k in kids))
+    out += ["world 300000", "camera 278.0 278.0 -800.0 278.0 278.0 0.0 0.0 1.0 0.0 40.0 1.0 0.0 10.0 0.0 1.0", "lights 200000"]
+    return "\n".join(out) + "\n"
+
+
+def make_bounce_kat(n):
+    """kat_bounce.scene and the reference's records over it."""
+    with open(BOUNCE_SCENE, "w") as f:
+        f.write(bounce_scene_text())
+    run("kat", "bounce", n, 1234567, os.path.join(HERE, "kat_bounce.bin"), BOUNCE_SCENE)
+
+
 def only_kats(names):
     """Generate the named KATs alone and add their entries to golden.json."""
     sizes = dict(KATS)
@@ -316,6 +381,8 @@ def only_kats(names):
             make_mesh_kat(sizes[name])
         elif name == "world":
             make_world_kat(sizes[name])
+        elif name == "bounce":
+            make_bounce_kat(sizes[name])
         else:
             run("kat", name, sizes[name], 1234567, os.path.join(HERE, f"kat_{name}.bin"))
         meta["kats"][name] = sizes[name]
@@ -349,6 +416,8 @@ def main():
             make_mesh_kat(n)
         elif name == "world":
             make_world_kat(n)
+        elif name == "bounce":
+            make_bounce_kat(n)
         else:
             run("kat", name, n, 1234567, os.path.join(HERE, f"kat_{name}.bin"))
         meta["kats"][name] = n

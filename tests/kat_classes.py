@@ -1,6 +1,6 @@
 """Edge classes of the scene KAT records (tests/golden/kat_{sphere, moving_sphere,
 rect, box, xform, medium, isotropic, texture_checker, texture_noise,
-texture_image, mesh, world}.bin), worked out from the committed records alone: the inputs,
+texture_image, mesh, world, bounce}.bin), worked out from the committed records alone: the inputs,
 the reference's outputs and float32 arithmetic in numpy (the mesh KAT also reads its
 committed scene text, kat_mesh.scene, and places lattice points in exact float64).
 No device code and no restatement code is involved.  Layouts: tests/golden/README.md.
@@ -16,7 +16,7 @@ import numpy as np
 F = np.float32
 HIT = {"sphere": 12, "moving_sphere": 18, "rect": 15, "box": 14, "xform": 27, "medium": 18, "mesh": 10, "world": 11}
 NEW_KATS = ("sphere", "moving_sphere", "rect", "box", "xform", "medium", "isotropic", "texture_checker",
-            "texture_noise", "texture_image", "mesh", "world")
+            "texture_noise", "texture_image", "mesh", "world", "bounce")
 MESH_SCENE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kat_mesh.scene")
 
 
@@ -849,9 +849,242 @@ WORLD_MIN = {
     "origin on an earlier hit point": 64,
     "origin on an earlier hit point, d along its normal": 32, "origin on an earlier hit point, d not along its normal": 32,
 }
-MIN_COUNTS = {"world": WORLD_MIN}
+BOUNCE_SCENE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kat_bounce.scene")
+# the function whose inputs a class stresses, for a failure message (csrc/kernels.hip)
+BOUNCE_FAMILIES = ("terminal", "diffuse", "Beckmann", "specular")
+# every record with a mixture loop must be walked (tests/test_kat_edges.py): this class stays empty
+BOUNCE_WALK_MISSES = "mixture loop: the LCG walk does NOT reach the state after in the reference's attempts"
 
-_CLASSIFIERS = {"world": _world, "mesh": _mesh, "sphere": _sphere, "moving_sphere": _moving_sphere, "rect": _rect, "box": _box, "xform": _xform,
+
+@functools.lru_cache(maxsize=None)
+def bounce_scene():
+    """kat_bounce.scene: ({list l: [(kind, floats) per member, flips followed]}, {mat m: (kind, floats)})."""
+    objs, mats = {}, {}
+    for line in open(BOUNCE_SCENE):
+        t = line.split("#")[0].split()
+        if len(t) > 2 and t[0] == "obj":
+            objs[int(t[1])] = t[2:]
+        if len(t) > 2 and t[0] == "mat":
+            mats[int(t[1])] = (t[2], [float(x) for x in t[3:]])
+    lists = {}
+    for oid, t in objs.items():
+        if oid >= 200000 and oid < 300000 and t[0] == "list":
+            mem = []
+            for k in t[2:2 + int(t[1])]:
+                m = objs[int(k)]
+                while m[0] == "flip":
+                    m = objs[int(m[1])]
+                mem.append((m[0], [float(x) for x in m[1:-1]]))
+            lists[oid - 200000] = mem
+    return lists, mats
+
+
+def _bounce_light_points(kind, f):
+    """bsdf_dead()'s test points of a sampling light, its radius and the coordinate scale of its margin."""
+    if kind == "xz_rect":
+        x0, x1, z0, z1, k = f
+        return np.array([[x, k, z] for x in (x0, x1) for z in (z0, z1)]), 0.0, max(abs(v) for v in f)
+    if kind == "sphere":
+        return np.array([f[:3]]), abs(f[3]), max(abs(v) for v in f[:3]) + abs(f[3])
+    if kind == "triangle":
+        return np.array(f[:9]).reshape(3, 3), 0.0, max(abs(v) for v in f[:9])
+    return None
+
+
+def bounce_lcg_walk(rec, i):
+    """The mixture loop of diffuse or Beckmann record i replayed on the LCG alone (mathf.h:14-19,
+    pdf.h:175-189, hitable_list.h:63-67): (attempts, the last attempt's branch 'light' / 'bsdf',
+    the member index of its light or -1), or None when the walk does not reach the state after
+    within 5000 attempts.  A light attempt draws the index and two more if the member samples
+    (xz_rect, sphere, triangle); a cosine / Oren-Nayar BSDF attempt draws two, a Beckmann one none."""
+    lists, _ = bounce_scene()
+    mem = lists[int(rec[i, 0])]
+    beck = 6 <= rec[i, 1] <= 8
+    step = lambda s: (0x5DEECE66D * s + 0xB16) & 0xFFFFFFFFFFFF  # noqa: E731
+    s = int(rec[i, 19]) | (int(rec[i, 20]) << 24)
+    want = int(rec[i, 37]) | (int(rec[i, 38]) << 24)
+    s = step(s)
+    for a in range(1, 5001):
+        s = step(s)
+        which, idx = "bsdf", -1
+        if (s >> 16) / 4294967296.0 < 0.5:
+            s = step(s)
+            which, idx = "light", int((s >> 16) / 4294967296.0 * len(mem))
+            if mem[idx][0] in ("xz_rect", "sphere", "triangle"):
+                s = step(step(s))
+        elif not beck:
+            s = step(step(s))
+        if s == want and a == int(rec[i, 36]):
+            return a, which, idx
+    return None
+
+
+def _bounce(rec):
+    lists, mats = bounce_scene()
+    n_rec = len(rec)
+    l, m = rec[:, 0].astype(int), rec[:, 1].astype(int)
+    p, n, d = rec[:, 2:5].astype(np.float64), rec[:, 5:8].astype(np.float64), rec[:, 13:16].astype(np.float64)
+    time, depth, max_depth = rec[:, 16], rec[:, 17], rec[:, 18]
+    scattered, stime, col, att = rec[:, 25] == 1, rec[:, 32], rec[:, 33:36], rec[:, 36]
+    kind = np.array([mats[x][0] for x in m])
+    limit = depth >= max_depth
+    lamb, oren, beck = kind == "lambertian", kind == "orennayar", kind == "beckmann"
+    light = kind == "diffuse_light"
+    term = limit | light
+    diff, bk = (lamb | oren) & ~term, beck & ~term
+    spec = ~term & ~diff & ~bk
+    n_lights = np.array([len(lists[x]) for x in l])
+    sampling = np.array([sum(k in ("xz_rect", "sphere", "triangle") for k, _ in lists[x]) for x in l])
+    dn = (rec[:, 13] * rec[:, 5] + rec[:, 14] * rec[:, 6]) + rec[:, 15] * rec[:, 7]  # dot(d, n) in float32
+    front = dn < 0
+    dlen = np.sqrt((d * d).sum(axis=1))
+    w = n / np.sqrt((n * n).sum(axis=1))[:, None]
+    # the nearest light point beyond the tangent plane in margins of bsdf_dead (kernels.hip), per light kind
+    ratio = {k: np.full(n_rec, np.inf) for k in ("xz_rect", "sphere", "triangle")}
+    straddle, in_plane, inside, centre, edge_on = (np.zeros(n_rec, bool) for _ in range(5))
+    for i in range(n_rec):
+        ps = np.abs(p[i]).max() + 1.0
+        for k, f in lists[l[i]]:
+            lp = _bounce_light_points(k, f)
+            if lp is None:
+                continue
+            pts, r, scale = lp
+            s = (pts - p[i]) @ w[i] * (1.0 if front[i] else -1.0)  # the side the BSDF samples do not take is positive
+            ratio[k][i] = min(ratio[k][i], (s.min() - r) / (1e-3 * (ps + scale)))
+            straddle[i] |= (s.min() - r < 0) and (s.max() + r > 0)
+            if k == "xz_rect":
+                in_plane[i] |= rec[i, 3] == np.float32(f[4])
+            if k == "sphere":
+                dist = np.sqrt(((pts[0] - p[i]) ** 2).sum())
+                inside[i] |= 0 < dist < r
+                centre[i] |= dist == 0
+            if k == "triangle":
+                nn = np.cross(pts[1] - pts[0], pts[2] - pts[0])
+                to = pts.mean(axis=0) - p[i]
+                edge_on[i] |= abs(nn @ to) / np.sqrt(to @ to) < 1e-4  # triangle::hit's determinant towards the centroid
+    near = np.minimum(np.minimum(ratio["xz_rect"], ratio["sphere"]), ratio["triangle"])
+    dl = diff & (n_lights > 0)
+    out = {f"family: {f}": x for f, x in zip(BOUNCE_FAMILIES, (term, diff, bk, spec))}
+    names = {"xz_rect": "a rect light's corner", "sphere": "a sphere light's pole", "triangle": "a triangle light's vertex"}
+    for k, nm in names.items():
+        mine = dl & (ratio[k] == near)
+        out[f"bsdf_dead: tangent plane within 12 margins of {nm}"] = mine & (np.abs(near) <= 12)
+        out[f"bsdf_dead: {nm} inside the margin"] = mine & (near > 0) & (near < 1)
+        out[f"bsdf_dead: {nm} 1 to 2.5 margins beyond the plane"] = mine & (near >= 1) & (near <= 2.5)
+        out[f"bsdf_dead: {nm} 2.5 to 12 margins beyond the plane"] = mine & (near > 2.5) & (near <= 12)
+        out[f"bsdf_dead: {nm} on the samples' side by up to 12 margins"] = mine & (near <= 0) & (near >= -12)
+    loops = (dl | (bk & (n_lights > 0))) & scattered  # the records with a mixture loop
+    walk = {i: bounce_lcg_walk(rec, i) for i in np.flatnonzero(loops)}
+    last_bsdf = np.zeros(n_rec, bool)
+    last_none = np.zeros(n_rec, bool)
+    walked = np.zeros(n_rec, bool)
+    for i, wk in walk.items():
+        walked[i] = wk is not None
+        if wk:
+            last_bsdf[i] = wk[1] == "bsdf"
+            last_none[i] = wk[1] == "light" and lists[l[i]][wk[2]][0] not in ("xz_rect", "sphere", "triangle")
+    nx = np.abs(rec[:, 5])
+    p9 = np.float32(0.9)
+    axis = (np.abs(rec[:, 5:8]) == 1).sum(axis=1) == 1
+    axis &= (rec[:, 5:8] == 0).sum(axis=1) == 2
+    perp = (dn == 0) & axis
+    # refract's discriminant (material.h:21-32) in float32, for dielectric records
+    diel = (kind == "dielectric") & ~term
+    ri = np.array([mats[x][1][0] if mats[x][0] == "dielectric" else 1.0 for x in m], F)
+    with np.errstate(all="ignore"):
+        d32 = rec[:, 13:16]
+        ln = np.sqrt((d32[:, 0] * d32[:, 0] + d32[:, 1] * d32[:, 1]) + d32[:, 2] * d32[:, 2])
+        uv = d32 / ln[:, None]
+        inside_d = dn > 0
+        outward = np.where(inside_d[:, None], -rec[:, 5:8], rec[:, 5:8])
+        dt = _dot(uv, outward)
+        nint = np.where(inside_d, ri, (1.0 / ri.astype(np.float64)).astype(F))
+        disc = (1.0 - (nint * nint * (F(1) - dt * dt)).astype(np.float64)).astype(F)
+        cos_in = np.abs(dn.astype(np.float64)) / (dlen * np.sqrt((n * n).sum(axis=1)))
+        sn = (rec[:, 29] * rec[:, 5] + rec[:, 30] * rec[:, 6]) + rec[:, 31] * rec[:, 7]  # dot(scattered dir, n)
+    ulp1 = F(2.0 ** -24)
+    metal = (kind == "metal") & ~term
+    fuzz = np.array([mats[x][1][3] if mats[x][0] == "metal" else 0.0 for x in m])
+    checker_p = (np.sin(10 * rec[:, 2].astype(np.float64)) * np.sin(10 * rec[:, 3].astype(np.float64)) *
+                 np.sin(10 * rec[:, 4].astype(np.float64)))
+    out.update({
+        "bsdf_dead: a light straddles the tangent plane": dl & straddle,
+        "bsdf_dead: the hit point in an xz_rect light's plane, another sampling light in the list": dl & in_plane & (sampling > 1),
+        "sphere light: the hit point inside it": dl & inside,
+        "sphere light: the hit point at its centre": dl & centre,
+        "triangle light: edge-on, within triangle::hit's determinant threshold": dl & edge_on,
+        "mixture loop: exactly 1 attempt": dl & (att == 1),
+        "mixture loop: 2 to 8 attempts": dl & (att >= 2) & (att <= 8),
+        "mixture loop: 9 to 32 attempts": dl & (att >= 9) & (att <= 32),
+        "mixture loop: 33 to 64 attempts": dl & (att >= 33) & (att <= 64),
+        "mixture loop: more than 64 attempts": dl & (att > 64),
+        "mixture loop: the LCG walk reaches the state after in the reference's attempts": walked,
+        BOUNCE_WALK_MISSES: loops & ~walked,
+        "mixture loop: a BSDF-branch attempt of a front-face diffuse hit succeeds (a light's pdf)": dl & front & last_bsdf,
+        "mixture loop: a BSDF-branch attempt of a back-face Oren-Nayar hit succeeds": dl & oren & ~front & last_bsdf,
+        "mixture loop: a non-sampling member's (1, 0, 0) succeeds": last_none,
+        "skip_attempt: a list with non-sampling members, 2 or more attempts": dl & (sampling < n_lights) & (att >= 2),
+        "light list 3 (a non-sampling member first), diffuse": dl & (l == 3),
+        "light list 4 (non-sampling members only), back-face Oren-Nayar or Beckmann": (l == 4) & (oren | beck) & ~front & ~term,
+        "light list 5 (empty), diffuse": diff & (l == 5),
+        "light list 5 (empty), Beckmann": bk & (l == 5),
+        "light list 6 (rects above and below), diffuse": dl & (l == 6),
+        "light list 7 (five lights), diffuse": dl & (l == 7),
+        "light list 8 (seven non-sampling members), diffuse": dl & (l == 8),
+        "co == +0 (d perpendicular to an axis-aligned normal), lambertian": perp & ~np.signbit(dn) & lamb & ~term,
+        "co == -0 (d perpendicular to an axis-aligned normal), lambertian": perp & np.signbit(dn) & lamb & ~term,
+        "d perpendicular to the normal, not lambertian": perp & ~lamb & ~term,
+        **{f"{nm}, front face": x & front for nm, x in (("lambertian", lamb & ~term), ("Oren-Nayar", oren & ~term), ("Beckmann", bk))},
+        **{f"{nm}, back face": x & (dn > 0) for nm, x in (("lambertian", lamb & ~term), ("Oren-Nayar", oren & ~term), ("Beckmann", bk))},
+        "onb_from_w: |n.x| == 0.9f": ~term & ~spec & (nx == p9),
+        "onb_from_w: |n.x| an ulp below 0.9f": ~term & ~spec & (nx == np.nextafter(p9, F(0))),
+        "onb_from_w: |n.x| an ulp above 0.9f": ~term & ~spec & (nx == np.nextafter(p9, F(1))),
+        **{f"normal along {'-+'[sg > 0]}{'xyz'[a]}": ~term & axis & (rec[:, 5 + a] == sg) for a in range(3) for sg in (-1, 1)},
+        "|d| < 0.1": ~term & (dlen < 0.1),
+        "|d| > 100": ~term & (dlen > 100),
+        "|d| > 100, diffuse": dl & (dlen > 100),
+        "dielectric: normal incidence": diel & (cos_in > 0.999999),
+        "dielectric: total reflection": diel & (disc <= 0) & (ri > 1),
+        # (ulps of the discriminant's subtrahend ni^2 (1 - dt^2), a float just below 1: 2^-24)
+        "dielectric: discriminant within 4 ulps above 0": diel & (disc > 0) & (disc <= 4 * ulp1) & (ri > 1),
+        "dielectric: discriminant within 4 ulps at or below 0": diel & (disc <= 0) & (disc >= -4 * ulp1) & (ri > 1),
+        "dielectric: from inside": diel & (dn > 0),
+        "dielectric: from outside": diel & (dn < 0),
+        "dielectric: index 1.0": diel & (ri == 1),
+        "dielectric: index 1.0, grazing (discriminant 0)": diel & (ri == 1) & (disc == 0),
+        "metal: fuzz 0": metal & (fuzz == 0),
+        "metal: fuzz above 1": metal & (fuzz > 1),
+        "metal: the reflected ray ends below the surface": metal & front & (sn < 0),
+        "isotropic, checker albedo, sines < 0": (kind == "isotropic") & ~term & (checker_p < 0),
+        "isotropic, checker albedo, sines >= 0": (kind == "isotropic") & ~term & (checker_p >= 0),
+        "diffuse_light from the front": light & front,
+        "diffuse_light from the back": light & (dn > 0),
+        "depth == maxDepth on a scattering material": limit & ~light,
+        "time == 0, diffuse": dl & (time == 0),
+        "time == 1, diffuse": dl & (time == 1),
+        "time inside the shutter, diffuse": dl & (time > 0) & (time < 1),
+        "time != 0, specular (the new ray's time is 0)": spec & (time != 0) & (stime == 0),
+        "NaN in the colour": np.isnan(col).any(axis=1),
+    })
+    return out
+
+
+def bounce_waves_mixed(rec):
+    """The first record of a group of 64 consecutive records that lacks one of the four families (-1: none)."""
+    c = _bounce(np.asarray(rec, F))
+    fam = np.stack([c[f"family: {f}"] for f in BOUNCE_FAMILIES])
+    for i in range(0, len(rec) - 63):
+        if not fam[:, i:i + 64].any(axis=1).all():
+            return i
+    return -1
+
+
+# The bounce KAT's classes are held to test_kat_edges' 8; the two long loops to the 4 that the issue sets for them.
+BOUNCE_MIN = {"mixture loop: 33 to 64 attempts": 4, "mixture loop: more than 64 attempts": 4, BOUNCE_WALK_MISSES: 0}
+MIN_COUNTS = {"world": WORLD_MIN, "bounce": BOUNCE_MIN}
+MAX_RECORDS = {"bounce": 2048}  # (every other KAT: test_kat_edges' 1024)
+
+_CLASSIFIERS = {"bounce": _bounce, "world": _world, "mesh": _mesh, "sphere": _sphere, "moving_sphere": _moving_sphere, "rect": _rect, "box": _box, "xform": _xform,
                 "medium": _medium, "isotropic": _isotropic, "texture_checker": _texture_checker,
                 "texture_noise": _texture_noise, "texture_image": _texture_image}
 

@@ -73,7 +73,7 @@ def read_kat(name: str):
 
 def replay_kat(name: str, rec: np.ndarray) -> np.ndarray:
     out = np.ascontiguousarray(rec.copy())
-    if name in ("mesh", "world"):  # replayed over the fixture meshes / worlds
+    if name in ("mesh", "world", "bounce"):  # replayed over the fixture meshes / worlds / light lists and materials
         with open(os.path.join(GOLDEN, f"kat_{name}.scene"), "rb") as f:
             if lib().oracle_kat_scene(f.read()) != 0:
                 raise RuntimeError(lib().oracle_last_error().decode())
