@@ -1,5 +1,7 @@
-// C-ABI (include/srr_capi.h) and the host render driver: scene upload, the
-// wavefront bounce loop on one HIP stream, batch bookkeeping and timing.
+// The product's entry points of the C-ABI (include/srr_capi.h): scene building, renderers (the
+// render driver itself is renderer.cpp and multi.cpp), AOVs, the denoiser, image and mesh files,
+// MERL tables.  The test entry points (device KATs, libm sweeps) are in capi_kat.cpp, and
+// capi_internal.h holds what the two files share.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -7,14 +9,13 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
-#include "../../include/srr_capi.h"
+#include "capi_internal.h"
 #include "denoise.h"
 #include "imageio.h"
 #include "meshio.h"
@@ -24,32 +25,14 @@
 
 using namespace srr;
 
-struct srr_scene {
-  Scene s;
-};
-
 namespace {
 thread_local std::string g_err;
+}  // namespace
 
-int fail(int code, const std::string& msg) {
+int srr::fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-
-#define HIPCHK(x)                                                                         \
-  do {                                                                                    \
-    hipError_t e_ = (x);                                                                  \
-    if (e_ != hipSuccess) return fail(SRR_EIO, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-template <class T>
-int upload(T** dst, const std::vector<T>& v) {
-  size_t bytes = std::max<size_t>(v.size() * sizeof(T), 16);
-  HIPCHK(hipMalloc((void**)dst, bytes));
-  if (!v.empty()) HIPCHK(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  return 0;
-}
-}  // namespace
 
 extern "C" {
 
@@ -897,674 +880,6 @@ int srr_image_load(const char* path, int req_comp, int* x, int* y, int* comp, un
 
 void srr_image_free(unsigned char* pixels) { free(pixels); }
 
-int srr_device_kat(const char* name, int n, int width, float* records) {
-  if (!name || !records || n <= 0 || width <= 0) return fail(SRR_EINVAL, "bad KAT arguments");
-  static const char* kNames[] = {"erf",   "beckmann11", "beckmann_dist", "beckmann_pdf", "cosine_pdf",
-                                 "orennayar_pdf", "dielectric", "metal", "triangle", "aabb", "sqrt",
-                                 "camera", "lights", "light_list",
-                                 // scene KATs, kinds 14 .. 23 (kernels.hip KAT_SPHERE ...)
-                                 "sphere", "moving_sphere", "rect", "box", "xform", "medium", "isotropic",
-                                 "texture_checker", "texture_noise", "texture_image"};
-  static const int kWidth[] = {3, 5, 16, 21, 21, 21, 14, 14, 26, 15, 2, 23, 15, 15, 22, 26, 25, 24, 35, 22, 13, 7, 7, 5};
-  int kind = -1;
-  for (int k = 0; k < 24; ++k)
-    if (!strcmp(name, kNames[k])) kind = k;
-  if (kind < 0) return fail(SRR_EINVAL, std::string("no device KAT named ") + name);
-  if (width != kWidth[kind]) return fail(SRR_EINVAL, std::string("KAT ") + name + ": unexpected record width");
-  // host-side parameters the scene builder would compute (material ctors, face normals)
-  std::vector<float> aux(4 * (size_t)n, 0.f);
-  std::vector<DStandaloneTri> tris(kind == 8 ? n : 1);
-  Scene hs;
-  for (int q = 0; q < n; ++q) {
-    const float* r = records + (size_t)q * width;
-    if (kind == 2 || kind == 3) {
-      const float prm[4] = {r[0], r[1], 0, 0};
-      const HMat& m = hs.mat[hs.material(MAT_BECKMANN, -1, prm)];
-      aux[4 * q] = m.p[0];
-      aux[4 * q + 1] = m.p[1];
-    } else if (kind == 4 || kind == 5) {
-      const float prm[4] = {r[0], 0, 0, 0};
-      const HMat& m = hs.mat[hs.material(MAT_ORENNAYAR, -1, prm)];
-      aux[4 * q] = m.p[0];
-      aux[4 * q + 1] = m.p[1];
-    } else if (kind == 8) {  // triangle(p0, p1, p2, mat, uv0, uv1, uv2) with face normals (kat.inc)
-      const float uv9[9] = {0.1f, 0.2f, 0, 0.7f, 0.1f, 0, 0.3f, 0.9f, 0};
-      const int h = hs.triangle(r, -1, uv9, nullptr);
-      const HTri& t = hs.tris[hs.obj[h].tri];
-      DStandaloneTri& d = tris[q];
-      std::memcpy(d.p, t.p, 36);
-      std::memcpy(d.sh.n, t.n, 36);
-      for (int k = 0; k < 3; ++k) d.sh.uv[2 * k] = t.uv[3 * k], d.sh.uv[2 * k + 1] = t.uv[3 * k + 1];
-      d.sh.mat = -1;
-    }
-  }
-  // camera KAT: camera(lookfrom, lookat, (0,1,0), vfov, aspect, aperture, focus, 0, 1) per record, built
-  // by the host scene code exactly as a scene's camera (camera.h:33-48)
-  std::vector<DCamera> cams(kind == 11 ? n : 1);
-  if (kind == 11) {
-    for (int q = 0; q < n; ++q) {
-      const float* r = records + (size_t)q * width;
-      const float vup[3] = {0, 1, 0};
-      Scene cs;
-      cs.camera(r, r + 3, vup, r[6], r[7], r[8], r[9], 0.0f, 1.0f);
-      const HCamera& c = cs.cam;
-      DCamera& d = cams[q];
-      std::memcpy(d.origin, c.origin, 12);
-      std::memcpy(d.llc, c.llc, 12);
-      std::memcpy(d.horizontal, c.horizontal, 12);
-      std::memcpy(d.vertical, c.vertical, 12);
-      std::memcpy(d.u, c.u, 12);
-      std::memcpy(d.v, c.v, 12);
-      d.time0 = c.time0;
-      d.time1 = c.time1;
-      d.lens_radius = c.lens_radius;
-    }
-  }
-  // light KATs: the light list {flip(xz_rect(213,343,227,332,554)), sphere((278,700,280),50),
-  // triangle((150,500,150),(400,520,180),(260,540,420))} of oracle/ref/kat.inc, flattened like a scene's
-  Flat lf;
-  if (kind == 12 || kind == 13) {
-    Scene ls;
-    const int rect = ls.wrap(H_FLIP, ls.rect(H_XZ, 213, 343, 227, 332, 554, -1), nullptr);
-    const float c[3] = {278, 700, 280};
-    const int sph = ls.sphere(c, 50, -1);
-    const float p9[9] = {150, 500, 150, 400, 520, 180, 260, 540, 420};
-    const int tri = ls.triangle(p9, -1, nullptr, nullptr);
-    const int kids[3] = {rect, sph, tri};
-    ls.world = ls.lights = ls.list(kids, 3);
-    const float lf3[3] = {0, 0, -1}, la3[3] = {0, 0, 0}, up[3] = {0, 1, 0};
-    ls.camera(lf3, la3, up, 40, 1, 0, 1, 0, 1);
-    ls.has_camera = true;
-    std::string e;
-    if (flatten(ls, lf, e) < 0 || lf.lights.size() != 3) return fail(SRR_EINVAL, "light KAT scene: " + e);
-  }
-  // scene KATs: every object is built by the host scene calls and flattened, as a
-  // scene's are (rotation sines, a box's six faces and flips, a medium's boundary list
-  // and phase material, xf_count and its flip bit, the Perlin tables, texture rows).
-  // Kinds 14 .. 19 make one scene per record and concatenate the tables (`base`: each
-  // record's first rows, kernels.hip kat_scene); the texture kinds make one scene.
-  std::vector<int32_t> base;
-  std::vector<uint8_t> images;
-  std::vector<float> perlin_ranvec;
-  std::vector<int32_t> perlin_perm;
-  if (kind >= 14) {
-    std::string e;
-    Flat f;
-    auto flat_of = [&](Scene& s, int h) {  // world = hitable_list{h}, no lights, any camera
-      s.world = s.list(&h, 1);
-      s.lights = s.list(&h, 0);
-      const float lf3[3] = {0, 0, -1}, la3[3] = {0, 0, 0}, up[3] = {0, 1, 0};
-      s.camera(lf3, la3, up, 40, 1, 0, 1, 0, 1);
-      s.has_camera = true;
-      return flatten(s, f, e) >= 0;
-    };
-    auto prim = [](Scene& s, float kind_, const float* a, const float* b) {  // a sphere (a, b[0]) or a box (a, b)
-      return kind_ == 0 ? s.sphere(a, b[0], -1) : s.box(a, b, -1);
-    };
-    auto tex_of_sphere = [&](int k) { return f.mats[f.spheres[k].mat].tex; };
-    const float org[3] = {0, 0, 0};
-    if (kind <= 19) {
-      for (int q = 0; q < n; ++q) {
-        const float* r = records + (size_t)q * width;
-        Scene s;
-        int h = -1;
-        if (kind == 14) h = s.sphere(r, r[3], -1);
-        else if (kind == 15) h = s.moving_sphere(r, r + 3, r[6], r[7], r[8], -1);
-        else if (kind == 16) {
-          h = s.rect(r[0] == 0 ? H_XY : (r[0] == 1 ? H_XZ : H_YZ), r[2], r[3], r[4], r[5], r[6], -1);
-          if (r[1] != 0) h = s.wrap(H_FLIP, h, nullptr);
-        } else if (kind == 17) h = s.box(r, r + 3, -1);
-        else if (kind == 18) {
-          h = prim(s, r[0], r + 1, r + 4);
-          for (int l = 2; l >= 0; --l) {  // the wrappers are listed outermost first
-            const float* w = r + 7 + 4 * l;
-            if (w[0] == 1) h = s.wrap(H_TRANSLATE, h, w + 1);
-            else if (w[0] == 2 || w[0] == 3) h = s.rotate(w[0] == 2 ? H_ROTY : H_ROTX, h, w[1]);
-            else if (w[0] == 4) h = s.wrap(H_FLIP, h, nullptr);
-          }
-        } else {
-          const float one[3] = {1, 1, 1};
-          HTex t;
-          t.kind = TEX_CONST;
-          std::memcpy(t.c, one, 12);
-          h = s.medium(prim(s, r[0], r + 1, r + 4), r[7], s.add_tex(t));
-        }
-        if (!flat_of(s, h)) return fail(SRR_EINVAL, "KAT scene: " + e);
-        const int32_t b8[8] = {(int32_t)lf.objs.size(),  f.n_world,
-                               (int32_t)lf.xforms.size(), (int32_t)lf.spheres.size(),
-                               (int32_t)lf.rects.size(),  (int32_t)lf.media.size(),
-                               (int32_t)lf.mats.size(),   (int32_t)lf.texs.size()};
-        base.insert(base.end(), b8, b8 + 8);
-        lf.objs.insert(lf.objs.end(), f.objs.begin(), f.objs.end());
-        lf.xforms.insert(lf.xforms.end(), f.xforms.begin(), f.xforms.end());
-        lf.spheres.insert(lf.spheres.end(), f.spheres.begin(), f.spheres.end());
-        lf.rects.insert(lf.rects.end(), f.rects.begin(), f.rects.end());
-        lf.media.insert(lf.media.end(), f.media.begin(), f.media.end());
-        lf.mats.insert(lf.mats.end(), f.mats.begin(), f.mats.end());
-        lf.texs.insert(lf.texs.end(), f.texs.begin(), f.texs.end());
-      }
-    } else {
-      Scene s;
-      auto constant = [&](float x, float y, float z) {
-        HTex t;
-        t.kind = TEX_CONST;
-        t.c[0] = x, t.c[1] = y, t.c[2] = z;
-        return s.add_tex(t);
-      };
-      auto checker = [&](int even, int odd) {
-        HTex t;
-        t.kind = TEX_CHECKER;
-        t.even = even;
-        t.odd = odd;
-        return s.add_tex(t);
-      };
-      auto shown = [&](int tex) {  // a texture flattens only if a placed material reaches it
-        const float prm[4] = {0, 0, 0, 0};
-        return s.sphere(org, 1, s.material(MAT_LAMBERTIAN, tex, prm));
-      };
-      std::vector<int> hs;
-      std::vector<float> scales;
-      if (kind == 20) {  // the phase material of constant_medium(sphere, 1, checker(A, B))
-        hs.push_back(s.medium(s.sphere(org, 1, -1), 1.0f, checker(constant(0.2f, 0.3f, 0.1f), constant(0.9f, 0.9f, 0.9f))));
-      } else if (kind == 21) {  // checker(A, B) and checker(checker(A, B), checker(C, D))
-        const int A = constant(0.2f, 0.3f, 0.1f), B = constant(0.9f, 0.9f, 0.9f), C = constant(0.1f, 0.5f, 0.8f),
-                  D = constant(0.6f, 0.1f, 0.4f);
-        hs.push_back(shown(checker(A, B)));
-        hs.push_back(shown(checker(checker(A, B), checker(C, D))));
-      } else if (kind == 22) {  // one noise_texture per scale the records name
-        for (int q = 0; q < n; ++q) {
-          const float sc = records[(size_t)q * width];
-          size_t k = 0;
-          while (k < scales.size() && std::memcmp(&scales[k], &sc, 4) != 0) ++k;
-          if (k == scales.size()) {
-            if (scales.size() == 64) return fail(SRR_EINVAL, "noise KAT: more than 64 scales");
-            scales.push_back(sc);
-            HTex t;
-            t.kind = TEX_NOISE;
-            t.c[0] = sc;
-            hs.push_back(shown(s.add_tex(t)));
-          }
-          aux[4 * (size_t)q] = (float)k;
-        }
-      } else {  // the 7 x 5 synthetic image of oracle/ref/kat.inc
-        HTex t;
-        t.kind = TEX_IMAGE;
-        t.nx = 7;
-        t.ny = 5;
-        t.px = gen_image(7, 5, 7u, 0);
-        hs.push_back(shown(s.add_tex(std::move(t))));
-      }
-      // (a rect between the spheres keeps them plain list objects, not a sphere group)
-      std::vector<int> kids;
-      for (int h : hs) {
-        kids.push_back(h);
-        kids.push_back(s.rect(H_XY, 0, 1, 0, 1, 0, -1));
-      }
-      if (!flat_of(s, s.list(kids.data(), (int)kids.size()))) return fail(SRR_EINVAL, "KAT scene: " + e);
-      if (kind >= 21)  // aux: the record's texture row after flattening
-        for (int q = 0; q < n; ++q) {
-          const float* r = records + (size_t)q * width;
-          const int k = kind == 21 ? (r[0] != 0 ? 1 : 0) : (kind == 22 ? (int)aux[4 * (size_t)q] : 0);
-          aux[4 * (size_t)q] = (float)tex_of_sphere(k);
-        }
-      lf = f;
-    }
-    images = f.images;
-    perlin_ranvec = f.perlin_ranvec;
-    perlin_perm = f.perlin_perm;
-    if (kind != 23) images.clear();
-  }
-  float* d_rec = nullptr;
-  float* d_aux = nullptr;
-  DStandaloneTri* d_tris = nullptr;
-  DCamera* d_cams = nullptr;
-  DObj* d_objs = nullptr;
-  DXform* d_xforms = nullptr;
-  DMedium* d_media = nullptr;
-  DMat* d_mats = nullptr;
-  DTex* d_texs = nullptr;
-  uint8_t* d_images = nullptr;
-  float* d_ranvec = nullptr;
-  int32_t* d_perm = nullptr;
-  int32_t* d_base = nullptr;
-  DRect* d_rects = nullptr;
-  DSphere* d_sph = nullptr;
-  DStandaloneTri* d_stris = nullptr;
-  DLight* d_lights = nullptr;
-  const size_t rb = (size_t)n * width * sizeof(float);
-  int rc = 0;
-  if (hipMalloc((void**)&d_rec, rb) != hipSuccess || hipMalloc((void**)&d_aux, aux.size() * 4) != hipSuccess ||
-      hipMalloc((void**)&d_tris, tris.size() * sizeof(DStandaloneTri)) != hipSuccess)
-    rc = fail(SRR_ENOMEM, "device allocation failed");
-  if (!rc && (hipMemcpy(d_rec, records, rb, hipMemcpyHostToDevice) != hipSuccess ||
-              hipMemcpy(d_aux, aux.data(), aux.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-              hipMemcpy(d_tris, tris.data(), tris.size() * sizeof(DStandaloneTri), hipMemcpyHostToDevice) != hipSuccess))
-    rc = fail(SRR_EIO, "copy to device failed");
-  auto upload = [&rc](auto*& dst, const auto& v) {
-    if (rc || v.empty()) return;
-    const size_t b = v.size() * sizeof(v[0]);
-    if (hipMalloc((void**)&dst, b) != hipSuccess) rc = fail(SRR_ENOMEM, "device allocation failed");
-    else if (hipMemcpy(dst, v.data(), b, hipMemcpyHostToDevice) != hipSuccess) rc = fail(SRR_EIO, "copy to device failed");
-  };
-  upload(d_cams, cams);
-  upload(d_rects, lf.rects);
-  upload(d_sph, lf.spheres);
-  upload(d_stris, lf.stris);
-  upload(d_lights, lf.lights);
-  upload(d_objs, lf.objs);
-  upload(d_xforms, lf.xforms);
-  upload(d_media, lf.media);
-  upload(d_mats, lf.mats);
-  upload(d_texs, lf.texs);
-  upload(d_images, images);
-  upload(d_ranvec, perlin_ranvec);
-  upload(d_perm, perlin_perm);
-  upload(d_base, base);
-  const KatTables kt{d_cams, d_rects, d_sph, d_stris, d_lights, (int)lf.lights.size(), d_objs, d_xforms, d_media,
-                     d_mats, d_texs, d_images, d_ranvec, d_perm, d_base};
-  if (!rc && launch_kat(kind, n, width, d_rec, d_aux, d_tris, kt) < 0) rc = fail(SRR_EIO, "KAT kernel launch failed");
-  if (!rc && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(records, d_rec, rb, hipMemcpyDeviceToHost) != hipSuccess))
-    rc = fail(SRR_EIO, "KAT kernel failed");
-  for (void* p : {(void*)d_rec, (void*)d_aux, (void*)d_tris, (void*)d_cams, (void*)d_rects, (void*)d_sph,
-                  (void*)d_stris, (void*)d_lights, (void*)d_objs, (void*)d_xforms, (void*)d_media, (void*)d_mats,
-                  (void*)d_texs, (void*)d_images, (void*)d_ranvec, (void*)d_perm, (void*)d_base})
-    (void)hipFree(p);
-  return rc;
-}
-
-int srr_device_mesh_kat(const char* scene_text, int variant, int quad_max, int stack_cap, int use_gstack, int n,
-                        int width, float* records) {
-  // every argument is checked before the first HIP call
-  if (!scene_text || !records || n <= 0 || n > 1 << 20 || width != kMeshKatWidth)
-    return fail(SRR_EINVAL, "bad mesh KAT arguments");
-  if (variant < kMeshKatBvh2 || variant > kMeshKatQuad) return fail(SRR_EINVAL, "no such mesh KAT variant");
-  if (stack_cap < 1 || stack_cap > paths_kernel_stack()) return fail(SRR_EINVAL, "mesh KAT: stack_cap out of range");
-  Scene sc;
-  std::string err;
-  int rc = scene_from_text(scene_text, sc, err);
-  if (rc < 0) return fail(rc, err);
-  Flat f;
-  if ((rc = flatten(sc, f, err)) < 0) return fail(rc, err);
-  // the world list's objects are the meshes, in order: mesh m of a record is world object m
-  if (!sc.valid_obj(sc.world) || sc.obj[sc.world].kind != H_LIST || (int)sc.obj[sc.world].kids.size() != f.n_world)
-    return fail(SRR_EINVAL, "mesh KAT: the world must be a list of bvh objects");
-  std::vector<int32_t> mesh_obj(f.n_world), tri_file(f.tri_shade.size(), -1);
-  for (int k = 0; k < f.n_world; ++k) {
-    const int h = sc.obj[sc.world].kids[k];
-    if (sc.obj[h].kind != H_BVH || f.objs[k].kind != OBJ_MESH || f.objs[k].xf_count != 0)
-      return fail(SRR_EINVAL, "mesh KAT: a world object is not a bare triangle mesh");
-    const HBvh& B = sc.bvhs[sc.obj[h].bvh];
-    const DMesh& m = f.meshes[f.objs[k].idx];
-    if (m.n_tris != (int)B.leaves.size() || m.tri_off < 0 || (size_t)m.tri_off + m.n_tris > tri_file.size())
-      return fail(SRR_EINVAL, "mesh KAT: mesh tables do not match the bvh");
-    std::map<int, int> pos;
-    for (size_t q = 0; q < B.input.size(); ++q) pos[B.input[q]] = (int)q;
-    for (size_t i = 0; i < B.leaves.size(); ++i) tri_file[m.tri_off + i] = pos.at(B.leaves[i]);
-    mesh_obj[k] = k;
-  }
-  for (int q = 0; q < n; ++q) {
-    const float mi = records[(size_t)q * width];
-    if (!(mi >= 0 && mi < (float)f.n_world && mi == (float)(int)mi)) return fail(SRR_EINVAL, "mesh KAT: a record names no mesh");
-  }
-  // the quad walk serves whole waves: pad with copies of the last record
-  const int n_run = variant == kMeshKatQuad ? (n + 63) / 64 * 64 : n;
-  std::vector<float> rec((size_t)n_run * width);
-  std::memcpy(rec.data(), records, (size_t)n * width * sizeof(float));
-  for (int q = n; q < n_run; ++q) std::memcpy(&rec[(size_t)q * width], &rec[(size_t)(n - 1) * width], width * sizeof(float));
-  srr_renderer* r = nullptr;  // uploads the tables exactly as a render does
-  if ((rc = renderer_create_flat(f, 0, &r, err)) < 0) return fail(rc, err);
-  std::unique_ptr<srr_renderer> keep(r);
-  SceneView S = r->view;
-  S.quad_max = quad_max;
-  MeshKatArgs A{};
-  A.n = n_run;
-  A.width = width;
-  A.stack_cap = stack_cap;
-  A.gst_cap = use_gstack ? kPathsGlobalStack : 0;
-  A.lanes = (n_run + 255) / 256 * 256;
-  float* d_rec = nullptr;
-  int2* d_gst = nullptr;
-  int32_t* d_mesh_obj = nullptr;
-  int32_t* d_tri_file = nullptr;
-  const size_t rb = rec.size() * sizeof(float);
-  if (hipMalloc((void**)&d_rec, rb) != hipSuccess ||
-      hipMalloc((void**)&d_mesh_obj, mesh_obj.size() * 4) != hipSuccess ||
-      hipMalloc((void**)&d_tri_file, tri_file.size() * 4) != hipSuccess ||
-      (use_gstack && hipMalloc((void**)&d_gst, (size_t)kPathsGlobalStack * A.lanes * sizeof(int2)) != hipSuccess))
-    rc = fail(SRR_ENOMEM, "device allocation failed");
-  if (!rc && (hipMemcpy(d_rec, rec.data(), rb, hipMemcpyHostToDevice) != hipSuccess ||
-              hipMemcpy(d_mesh_obj, mesh_obj.data(), mesh_obj.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-              hipMemcpy(d_tri_file, tri_file.data(), tri_file.size() * 4, hipMemcpyHostToDevice) != hipSuccess))
-    rc = fail(SRR_EIO, "copy to device failed");
-  A.rec = d_rec;
-  A.gst = d_gst;
-  A.mesh_obj = d_mesh_obj;
-  A.tri_file = d_tri_file;
-  if (!rc && launch_mesh_kat(S, variant, A) < 0) rc = fail(SRR_EIO, "mesh KAT kernel launch failed");
-  if (!rc && (hipDeviceSynchronize() != hipSuccess ||
-              hipMemcpy(records, d_rec, (size_t)n * width * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess))
-    rc = fail(SRR_EIO, "mesh KAT kernel failed");
-  for (void* p : {(void*)d_rec, (void*)d_gst, (void*)d_mesh_obj, (void*)d_tri_file}) (void)hipFree(p);
-  return rc;
-}
-
-}  // extern "C"
-
-namespace {
-constexpr long long kWorldKatBaseId = 100000;  // text obj 100000 + w is world w of the `world` KAT's scene
-
-// World w of a world-KAT scene flattened as a render of it would be (the scene's world
-// set to the list, then the same flatten, group_sphere_runs included), and leaf_of: per
-// DObj row that is a primitive, its position in the depth-first listing of the world's
-// leaves in the FILE's order (a list's and a bvh command's children as written, a box's
-// six rects, a wrapper's child) -- the order in which the reference harness numbers them.
-int world_kat_flatten(Scene& sc, int w, Flat& f, std::vector<int32_t>& leaf_of, int& n_leaves, std::string& err) {
-  int h = -1;
-  for (auto& kv : sc.text_ids)
-    if (kv.first == kWorldKatBaseId + w) h = kv.second;
-  if (!sc.valid_obj(h) || sc.obj[h].kind != H_LIST) {
-    err = "world KAT: no list object " + std::to_string(kWorldKatBaseId + w);
-    return SRR_EINVAL;
-  }
-  sc.world = h;
-  int rc = flatten(sc, f, err);
-  if (rc < 0) return rc;
-  // leaves under each handle, then flatten's emission order in file numbering: `top` for the
-  // world list's own rows (-1 where an object BVH stands), `inner` for the BVHs' children
-  std::function<int(int)> count = [&](int k) -> int {
-    const HObj& o = sc.obj[k];
-    switch (o.kind) {
-      case H_LIST: case H_BOX: { int n = 0; for (int c : o.kids) n += count(c); return n; }
-      case H_BVH: { int n = 0; for (int c : sc.bvhs[o.bvh].input) n += count(c); return n; }
-      case H_FLIP: case H_TRANSLATE: case H_ROTY: case H_ROTX: return count(o.child);
-      case H_MEDIUM: return -(1 << 20);  // (refused below)
-      default: return 1;
-    }
-  };
-  n_leaves = count(h);
-  if (n_leaves <= 0) {
-    err = "world KAT: a world holds a medium or nothing";
-    return SRR_EINVAL;
-  }
-  std::vector<int32_t> top, inner;
-  std::function<void(int, int, std::vector<int32_t>&)> emit = [&](int k, int base, std::vector<int32_t>& out) {
-    const HObj& o = sc.obj[k];
-    switch (o.kind) {
-      case H_LIST: case H_BOX:
-        for (int c : o.kids) { emit(c, base, out); base += count(c); }
-        break;
-      case H_BVH: {
-        const HBvh& B = sc.bvhs[o.bvh];
-        std::map<int, int> at;  // child handle -> first leaf number (children are distinct objects)
-        for (int c : B.input) { at[c] = base; base += count(c); }
-        if (&out == &top) top.push_back(-1);
-        for (int l : B.leaves) emit(l, at.at(l), inner);
-        break;
-      }
-      case H_FLIP: case H_TRANSLATE: case H_ROTY: case H_ROTX: emit(o.child, base, out); break;
-      default: out.push_back(base);
-    }
-  };
-  emit(h, 0, top);
-  leaf_of.assign(f.objs.size(), -1);
-  size_t tc = 0, ic = 0;
-  bool ok = true;
-  for (int k = 0; k < f.n_world && ok; ++k) {
-    const DObj& d = f.objs[k];
-    if (d.kind == OBJ_SGROUP) {
-      const DSGroup& g = f.sgroups[d.idx];
-      ok = tc + g.n_items <= top.size();
-      for (int i = g.item_off; ok && i < g.item_off + g.n_items; ++i) {
-        const DSGItem& it = f.sg_items[i];
-        ok = it.pos >= 0 && it.pos < g.n_items && it.obj >= 0 && it.obj < (int)f.objs.size() && top[tc + it.pos] >= 0;
-        if (ok) leaf_of[it.obj] = top[tc + it.pos];
-      }
-      tc += g.n_items;
-    } else if (d.kind == OBJ_OBVH) {
-      ok = tc < top.size() && top[tc] == -1;
-      ++tc;
-      const DObvh& o = f.obvhs[d.idx];
-      for (int c = o.child_off; ok && c < o.child_off + o.n_children; ++c)
-        for (int j = 0; ok && j < f.obvh_children[c].obj_count; ++j) {
-          const int row = f.obvh_children[c].obj_begin + j;
-          ok = ic < inner.size() && row >= 0 && row < (int)f.objs.size();
-          if (ok) leaf_of[row] = inner[ic++];
-        }
-    } else {
-      ok = (d.kind == OBJ_SPHERE || d.kind == OBJ_MSPHERE || d.kind == OBJ_RECT || d.kind == OBJ_TRI) && tc < top.size() &&
-           top[tc] >= 0;
-      if (ok) leaf_of[k] = top[tc++];
-    }
-  }
-  if (!ok || tc != top.size() || ic != inner.size()) {
-    err = "world KAT: the flattened world does not match the scene's leaves (a mesh, or an object used twice)";
-    return SRR_EINVAL;
-  }
-  return 0;
-}
-
-size_t world_table_bytes(const Flat& f) {  // renderer.cpp's packed world tables, each padded to 16 bytes
-  auto pad = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  return pad(f.objs.size() * sizeof(DObj)) + pad(f.xforms.size() * sizeof(DXform)) + pad(f.spheres.size() * sizeof(DSphere)) +
-         pad(f.rects.size() * sizeof(DRect)) + pad(f.stris.size() * sizeof(DStandaloneTri)) +
-         pad(f.meshes.size() * sizeof(DMesh)) + pad(f.media.size() * sizeof(DMedium)) + pad(f.mats.size() * sizeof(DMat)) +
-         pad(f.texs.size() * sizeof(DTex)) + pad(f.lights.size() * sizeof(DLight));
-}
-}  // namespace
-
-extern "C" {
-
-int srr_world_kat_counts(const char* scene_text, int world, int32_t* counts) {
-  if (!scene_text || !counts || world < 0) return fail(SRR_EINVAL, "bad world KAT arguments");
-  Scene sc;
-  std::string err;
-  int rc = scene_from_text(scene_text, sc, err);
-  if (rc < 0) return fail(rc, err);
-  Flat f;
-  std::vector<int32_t> leaf_of;
-  int n_leaves = 0;
-  if ((rc = world_kat_flatten(sc, world, f, leaf_of, n_leaves, err)) < 0) return fail(rc, err);
-  int ng = 0, nb = 0;
-  for (int k = 0; k < f.n_world; ++k) {
-    ng += f.objs[k].kind == OBJ_SGROUP;
-    nb += f.objs[k].kind == OBJ_OBVH;
-  }
-  counts[0] = f.n_world;
-  counts[1] = ng;
-  counts[2] = nb;
-  counts[3] = n_leaves;
-  counts[4] = (int32_t)world_table_bytes(f);
-  return 0;
-}
-
-int srr_device_world_kat(const char* scene_text, int tables, int n, int width, float* records) {
-  // every argument is checked before the first HIP call
-  if (!scene_text || !records || n <= 0 || n > 1 << 20 || width != kWorldKatWidth || tables < 0 || tables > 1)
-    return fail(SRR_EINVAL, "bad world KAT arguments");
-  Scene sc;
-  std::string err;
-  int rc = scene_from_text(scene_text, sc, err);
-  if (rc < 0) return fail(rc, err);
-  std::map<int, std::vector<int>> by_world;  // a launch holds the records of one world: its objects are wave-uniform
-  for (int q = 0; q < n; ++q) {
-    const float wf = records[(size_t)q * width];
-    if (!(wf >= 0 && wf < 1024.f && wf == (float)(int)wf)) return fail(SRR_EINVAL, "world KAT: a record names no world");
-    by_world[(int)wf].push_back(q);
-  }
-  struct Job { Flat f; std::vector<int32_t> leaf_of; };
-  std::map<int, Job> jobs;
-  for (auto& kv : by_world) {
-    Job& j = jobs[kv.first];
-    int n_leaves = 0;
-    if ((rc = world_kat_flatten(sc, kv.first, j.f, j.leaf_of, n_leaves, err)) < 0) return fail(rc, err);
-    if (tables == 1 && world_table_bytes(j.f) > (size_t)kPathsWorldLdsBytes)
-      return fail(SRR_EINVAL, "world KAT: a world's tables do not fit the LDS copy");
-    bool grouped = false;
-    for (int k = 0; k < j.f.n_world; ++k) grouped = grouped || j.f.objs[k].kind == OBJ_SGROUP;
-    for (int q : kv.second)  // list_hit is a medium's boundary walk, and a boundary's spheres are never grouped
-      if (grouped && records[(size_t)q * width + 10] != 0)
-        return fail(SRR_EINVAL, "world KAT: an is_medium record on a world with a sphere group");
-  }
-  for (auto& kv : by_world) {
-    Job& j = jobs[kv.first];
-    const std::vector<int>& idx = kv.second;
-    std::vector<float> rec(idx.size() * (size_t)width);
-    for (size_t i = 0; i < idx.size(); ++i)
-      std::memcpy(&rec[i * width], &records[(size_t)idx[i] * width], width * sizeof(float));
-    srr_renderer* r = nullptr;  // uploads the tables exactly as a render does
-    if ((rc = renderer_create_flat(j.f, 0, &r, err)) < 0) return fail(rc, err);
-    std::unique_ptr<srr_renderer> keep(r);
-    float* d_rec = nullptr;
-    int32_t* d_leaf = nullptr;
-    const size_t rb = rec.size() * sizeof(float), lb = j.leaf_of.size() * sizeof(int32_t);
-    rc = 0;
-    if (hipMalloc((void**)&d_rec, rb) != hipSuccess || hipMalloc((void**)&d_leaf, lb) != hipSuccess)
-      rc = fail(SRR_ENOMEM, "device allocation failed");
-    if (!rc && (hipMemcpy(d_rec, rec.data(), rb, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(d_leaf, j.leaf_of.data(), lb, hipMemcpyHostToDevice) != hipSuccess))
-      rc = fail(SRR_EIO, "copy to device failed");
-    WorldKatArgs A{};
-    A.n = (int)idx.size();
-    A.width = width;
-    A.rec = d_rec;
-    A.leaf_of = d_leaf;
-    if (!rc && launch_world_kat(r->view, tables, A) < 0) rc = fail(SRR_EIO, "world KAT kernel launch failed");
-    if (!rc && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(rec.data(), d_rec, rb, hipMemcpyDeviceToHost) != hipSuccess))
-      rc = fail(SRR_EIO, "world KAT kernel failed");
-    for (void* p : {(void*)d_rec, (void*)d_leaf}) (void)hipFree(p);
-    if (rc) return rc;
-    for (size_t i = 0; i < idx.size(); ++i)
-      std::memcpy(&records[(size_t)idx[i] * width], &rec[i * width], width * sizeof(float));
-  }
-  return 0;
-}
-
-}  // extern "C"
-
-namespace {
-constexpr long long kBounceKatBaseId = 200000;  // text obj 200000 + l is light list l of the `bounce` KAT's scene
-
-// The scene flattened as a render of it with light list l would be.  Every material of the
-// scene must survive flattening (each is placed in the world), so that material m of a record
-// is row m of the device table.
-int bounce_kat_flatten(Scene& sc, int l, Flat& f, std::string& err) {
-  int h = -1;
-  for (auto& kv : sc.text_ids)
-    if (kv.first == kBounceKatBaseId + l) h = kv.second;
-  if (!sc.valid_obj(h) || sc.obj[h].kind != H_LIST) {
-    err = "bounce KAT: no list object " + std::to_string(kBounceKatBaseId + l);
-    return SRR_EINVAL;
-  }
-  sc.lights = h;
-  const int rc = flatten(sc, f, err);
-  if (rc < 0) return rc;
-  if (f.mats.size() != sc.mat.size()) {
-    err = "bounce KAT: a material of the scene is not placed in its world";
-    return SRR_EINVAL;
-  }
-  return 0;
-}
-}  // namespace
-
-extern "C" {
-
-int srr_bounce_kat_counts(const char* scene_text, int list, int32_t* counts) {
-  if (!scene_text || !counts || list < 0) return fail(SRR_EINVAL, "bad bounce KAT arguments");
-  Scene sc;
-  std::string err;
-  int rc = scene_from_text(scene_text, sc, err);
-  if (rc < 0) return fail(rc, err);
-  Flat f;
-  if ((rc = bounce_kat_flatten(sc, list, f, err)) < 0) return fail(rc, err);
-  for (int k = 0; k < 6; ++k) counts[k] = 0;
-  counts[0] = (int32_t)f.lights.size();
-  for (const DLight& L : f.lights) {
-    if (L.kind < LIGHT_NONE || L.kind > LIGHT_TRI) return fail(SRR_EINVAL, "bounce KAT: a light of an unknown kind");
-    ++counts[1 + L.kind];
-  }
-  counts[5] = (int32_t)f.mats.size();
-  return 0;
-}
-
-int srr_device_bounce_kat(const char* scene_text, int variant, int deep_tries, int n, int width, float* records) {
-  // every argument is checked before the first HIP call
-  if (!scene_text || !records || n <= 0 || n > 1 << 20 || width != kBounceKatWidth || variant < 0 || variant > 1 ||
-      deep_tries < 0)
-    return fail(SRR_EINVAL, "bad bounce KAT arguments");
-  Scene sc;
-  std::string err;
-  int rc = scene_from_text(scene_text, sc, err);
-  if (rc < 0) return fail(rc, err);
-  std::map<int, std::vector<int>> by_list;  // a launch holds the records of one light list (a wave keeps their order)
-  for (int q = 0; q < n; ++q) {
-    const float* r = records + (size_t)q * width;
-    if (!(r[0] >= 0 && r[0] < 1024.f && r[0] == (float)(int)r[0])) return fail(SRR_EINVAL, "bounce KAT: a record names no light list");
-    if (!(r[1] >= 0 && r[1] < (float)sc.mat.size() && r[1] == (float)(int)r[1]))
-      return fail(SRR_EINVAL, "bounce KAT: a record names no material");
-    if (!(r[17] >= 0 && r[17] <= 1e6f && r[18] >= 0 && r[18] <= 1e6f)) return fail(SRR_EINVAL, "bounce KAT: a record's depth is out of range");
-    by_list[(int)r[0]].push_back(q);
-  }
-  std::map<int, Flat> flats;
-  for (auto& kv : by_list)
-    if ((rc = bounce_kat_flatten(sc, kv.first, flats[kv.first], err)) < 0) return fail(rc, err);
-  for (auto& kv : by_list) {
-    const std::vector<int>& idx = kv.second;
-    std::vector<float> rec(idx.size() * (size_t)width);
-    for (size_t i = 0; i < idx.size(); ++i)
-      std::memcpy(&rec[i * width], &records[(size_t)idx[i] * width], width * sizeof(float));
-    srr_renderer* r = nullptr;  // uploads the tables exactly as a render does
-    if ((rc = renderer_create_flat(flats[kv.first], 0, &r, err)) < 0) return fail(rc, err);
-    std::unique_ptr<srr_renderer> keep(r);
-    float* d_rec = nullptr;
-    const size_t rb = rec.size() * sizeof(float);
-    rc = 0;
-    if (hipMalloc((void**)&d_rec, rb) != hipSuccess) rc = fail(SRR_ENOMEM, "device allocation failed");
-    if (!rc && hipMemcpy(d_rec, rec.data(), rb, hipMemcpyHostToDevice) != hipSuccess) rc = fail(SRR_EIO, "copy to device failed");
-    BounceKatArgs A{};
-    A.n = (int)idx.size();
-    A.width = width;
-    A.rec = d_rec;
-    A.variant = variant;
-    A.deep_tries = deep_tries;
-    if (!rc && launch_bounce_kat(r->view, A) < 0) rc = fail(SRR_EIO, "bounce KAT kernel launch failed");
-    if (!rc && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(rec.data(), d_rec, rb, hipMemcpyDeviceToHost) != hipSuccess))
-      rc = fail(SRR_EIO, "bounce KAT kernel failed");
-    (void)hipFree(d_rec);
-    if (rc) return rc;
-    for (size_t i = 0; i < idx.size(); ++i)
-      std::memcpy(&records[(size_t)idx[i] * width], &rec[i * width], width * sizeof(float));
-  }
-  return 0;
-}
-
-int srr_device_libm(const char* fn, int64_t n, const void* x, const void* y, void* out0, void* out1) {
-  // every argument is checked before the first HIP call, so a refusal needs no GPU
-  // (tests/test_device_libm.py test_unknown_names_are_refused runs without one)
-  if (!fn || !x || !out0 || n <= 0 || n > (int64_t)1 << 30) return fail(SRR_EINVAL, "bad libm sweep arguments");
-  int k = -1;
-  for (int i = 0; i < kLibmFnCount; ++i)
-    if (!strcmp(fn, kLibmFns[i].name)) k = i;
-  if (k < 0) return fail(SRR_EINVAL, std::string("no device libm routine named ") + fn);
-  const LibmFn& f = kLibmFns[k];
-  if ((f.n_in == 2 && !y) || (f.n_out == 2 && !out1))
-    return fail(SRR_EINVAL, std::string("libm routine ") + fn + ": missing second operand or output");
-  const size_t b = (size_t)n * (f.f64 ? sizeof(double) : sizeof(float));
-  void* d[4] = {nullptr, nullptr, nullptr, nullptr};  // x, y, out0, out1
-  const bool use[4] = {true, f.n_in == 2, true, f.n_out == 2};
-  int rc = 0;
-  for (int i = 0; i < 4 && !rc; ++i)
-    if (use[i] && hipMalloc(&d[i], b) != hipSuccess) rc = fail(SRR_ENOMEM, "device allocation failed");
-  if (!rc && (hipMemcpy(d[0], x, b, hipMemcpyHostToDevice) != hipSuccess ||
-              (use[1] && hipMemcpy(d[1], y, b, hipMemcpyHostToDevice) != hipSuccess)))
-    rc = fail(SRR_EIO, "copy to device failed");
-  if (!rc && launch_libm(k, n, d[0], d[1], d[2], d[3]) < 0) rc = fail(SRR_EIO, "libm kernel launch failed");
-  if (!rc && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out0, d[2], b, hipMemcpyDeviceToHost) != hipSuccess ||
-              (use[3] && hipMemcpy(out1, d[3], b, hipMemcpyDeviceToHost) != hipSuccess)))
-    rc = fail(SRR_EIO, "libm kernel failed");
-  for (void* p : d) (void)hipFree(p);
-  return rc;
-}
-
 // ---- MERL tables (brdf.h)
 struct srr_merl {
   int device = 0;
@@ -1615,24 +930,14 @@ int srr_merl_lookup(srr_merl* m, int64_t n, const double* angles, double* rgb, i
   if (!m || n < 0 || (n > 0 && (!angles || !rgb))) return fail(SRR_EINVAL, "bad MERL lookup arguments");
   if (n == 0) return 0;
   HIPCHK(hipSetDevice(m->device));
-  double *d_ang = nullptr, *d_rgb = nullptr;
-  int32_t* d_cell = nullptr;
   int rc = 0;
-  if (hipMalloc((void**)&d_ang, 4 * (size_t)n * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&d_rgb, 3 * (size_t)n * sizeof(double)) != hipSuccess ||
-      (cell && hipMalloc((void**)&d_cell, (size_t)n * sizeof(int32_t)) != hipSuccess))
-    rc = fail(SRR_ENOMEM, "device allocation failed");
-  if (!rc && hipMemcpy(d_ang, angles, 4 * (size_t)n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-    rc = fail(SRR_EIO, "copy to device failed");
-  if (!rc && launch_merl_lookup(m->table, n, d_ang, d_rgb, d_cell) < 0) rc = fail(SRR_EIO, "MERL kernel launch failed");
-  if (!rc && (hipDeviceSynchronize() != hipSuccess ||
-              hipMemcpy(rgb, d_rgb, 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-              (cell && hipMemcpy(cell, d_cell, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)))
-    rc = fail(SRR_EIO, "MERL kernel failed");
-  (void)hipFree(d_ang);
-  (void)hipFree(d_rgb);
-  (void)hipFree(d_cell);
-  return rc;
+  DevBuf<double> d_ang(angles, 4 * (size_t)n, rc), d_rgb(3 * (size_t)n, rc);
+  DevBuf<int32_t> d_cell(cell ? (size_t)n : 0, rc);
+  if (rc) return rc;
+  if (launch_merl_lookup(m->table, n, d_ang.get(), d_rgb.get(), d_cell.get()) < 0) return fail(SRR_EIO, "MERL kernel launch failed");
+  if (hipDeviceSynchronize() != hipSuccess || !d_rgb.download(rgb, 3 * (size_t)n) || (cell && !d_cell.download(cell, (size_t)n)))
+    return fail(SRR_EIO, "MERL kernel failed");
+  return 0;
 }
 
 int srr_teapot_vertices(float scale, int divs, float* out) {

@@ -271,7 +271,34 @@ int paths_lanes_per_device(const SceneView& S, int device);  // persistent grid 
 int paths_block_lanes(const SceneView& S);  // k_paths lanes per block for this scene (256 or 1,024)
 // 0, or -1 (nothing launched) when W.stack_cap exceeds the kernels' LDS stack (kStack)
 int launch_paths(const SceneView& S, const PathWork& W, int all_families, hipStream_t st);
-// device known-answer tests (srr_device_kat); kind = dev::KatKind
+// device known-answer tests (srr_device_kat, kernels.hip k_kat).  kKats, the one table of the kinds: the name a
+// test asks for and the floats per record (layouts in oracle/ref/kat.inc); row i is kind i (checked below)
+enum KatKind : int { KAT_ERF, KAT_BECK11, KAT_BECK_DIST, KAT_BECK_PDF, KAT_COSINE, KAT_ORENNAYAR, KAT_DIELECTRIC,
+                     KAT_METAL, KAT_TRIANGLE, KAT_AABB, KAT_SQRT, KAT_CAMERA, KAT_LIGHTS, KAT_LIGHT_LIST,
+                     // scene KATs (one flattened host scene per record, kat_scene)
+                     KAT_SPHERE, KAT_MSPHERE, KAT_RECT, KAT_BOX, KAT_XFORM, KAT_MEDIUM, KAT_ISOTROPIC, KAT_TEX_CHECKER,
+                     KAT_TEX_NOISE, KAT_TEX_IMAGE };
+struct KatDesc {
+  KatKind kind;
+  const char* name;
+  int width;
+};
+constexpr KatDesc kKats[] = {
+    {KAT_ERF, "erf", 3},                {KAT_BECK11, "beckmann11", 5},           {KAT_BECK_DIST, "beckmann_dist", 16},
+    {KAT_BECK_PDF, "beckmann_pdf", 21}, {KAT_COSINE, "cosine_pdf", 21},          {KAT_ORENNAYAR, "orennayar_pdf", 21},
+    {KAT_DIELECTRIC, "dielectric", 14}, {KAT_METAL, "metal", 14},                {KAT_TRIANGLE, "triangle", 26},
+    {KAT_AABB, "aabb", 15},             {KAT_SQRT, "sqrt", 2},                   {KAT_CAMERA, "camera", 23},
+    {KAT_LIGHTS, "lights", 15},         {KAT_LIGHT_LIST, "light_list", 15},      {KAT_SPHERE, "sphere", 22},
+    {KAT_MSPHERE, "moving_sphere", 26}, {KAT_RECT, "rect", 25},                  {KAT_BOX, "box", 24},
+    {KAT_XFORM, "xform", 35},           {KAT_MEDIUM, "medium", 22},              {KAT_ISOTROPIC, "isotropic", 13},
+    {KAT_TEX_CHECKER, "texture_checker", 7}, {KAT_TEX_NOISE, "texture_noise", 7}, {KAT_TEX_IMAGE, "texture_image", 5}};
+constexpr int kKatCount = (int)(sizeof(kKats) / sizeof(kKats[0]));
+constexpr bool kat_table_in_kind_order() {
+  for (int i = 0; i < kKatCount; ++i)
+    if ((int)kKats[i].kind != i) return false;
+  return true;
+}
+static_assert(kKatCount == KAT_TEX_IMAGE + 1 && kat_table_in_kind_order(), "kKats[i] must be KatKind i");
 // device tables of the camera / light KATs (srr_device_kat builds them with the
 // host scene code: one camera per record, one light list for all records), and of
 // the scene KATs (sphere ... texture_image): the flattened tables of one host scene

@@ -4214,12 +4214,7 @@ __global__ void __launch_bounds__(256) k_merl_lookup(const double* table, int64_
 // reference's KAT records (tests/golden/kat_*.bin, layouts in oracle/ref/kat.inc):
 // inputs are read from each record and the outputs written back in place, so a
 // test can compare them bit for bit with the reference's outputs.
-// aux: 4 host-computed floats per record (Beckmann alphas, Oren-Nayar A / B).
-enum KatKind : int { KAT_ERF, KAT_BECK11, KAT_BECK_DIST, KAT_BECK_PDF, KAT_COSINE, KAT_ORENNAYAR, KAT_DIELECTRIC,
-                     KAT_METAL, KAT_TRIANGLE, KAT_AABB, KAT_SQRT, KAT_CAMERA, KAT_LIGHTS, KAT_LIGHT_LIST,
-                     // scene KATs (one flattened host scene per record, kat_scene)
-                     KAT_SPHERE, KAT_MSPHERE, KAT_RECT, KAT_BOX, KAT_XFORM, KAT_MEDIUM, KAT_ISOTROPIC, KAT_TEX_CHECKER,
-                     KAT_TEX_NOISE, KAT_TEX_IMAGE };
+// aux: 4 host-computed floats per record (Beckmann alphas, Oren-Nayar A / B).  kind: kernels.h KatKind.
 
 SRR_D V3 kat3(const float* p) { return v3(p[0], p[1], p[2]); }
 SRR_D void kat_put3(float* p, V3 v) { p[0] = v.x, p[1] = v.y, p[2] = v.z; }
@@ -5107,7 +5102,7 @@ int launch_merl_lookup(const double* table, int64_t n, const double* angles, dou
 int launch_kat(int kind, int n, int w, float* d_rec, const float* d_aux, const DStandaloneTri* d_tris,
                const KatTables& kt) {
   // a thread per record; the scene KATs a wave per record
-  const int blocks = kind >= dev::KAT_SPHERE ? n : (n + 63) / 64;
+  const int blocks = kind >= KAT_SPHERE ? n : (n + 63) / 64;
   hipLaunchKernelGGL(dev::k_kat, dim3(blocks), dim3(64), 0, 0, kind, n, w, d_rec, d_aux, d_tris, kt);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
