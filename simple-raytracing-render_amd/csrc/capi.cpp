@@ -29,6 +29,13 @@ namespace {
 thread_local std::string g_err;
 }  // namespace
 
+// a failed allocation, worded by the buffer it was for ("staging image: out of memory")
+#define MEMCHK(x, code, what)                                                                  \
+  do {                                                                                         \
+    hipError_t e_ = (x);                                                                       \
+    if (e_ != hipSuccess) return fail(code, std::string(what) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
 int srr::fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
@@ -514,23 +521,18 @@ int srr_render_adaptive_host(srr_renderer* r, const srr_params* p, const srr_ada
   if (r->multi) return fail(SRR_EINVAL, "srr_render_adaptive: one-device renderers only");
   const int64_t npix = srr_shard_pixels(p, nullptr);
   if (npix < 0) return (int)npix;
-  float* d = nullptr;
-  int32_t* dc = nullptr;
+  DeviceMem<float> d;  // (neither is null for a shard without pixels)
+  DeviceMem<int32_t> dc;
   HIPCHK(hipSetDevice(r->device));
-  HIPCHK(hipMalloc((void**)&d, std::max<size_t>(16, 3 * npix * sizeof(float))));
-  if (hipMalloc((void**)&dc, std::max<size_t>(16, npix * sizeof(int32_t))) != hipSuccess) {
-    hipFree(d);
-    return fail(SRR_ENOMEM, "hipMalloc of the count buffer failed");
-  }
-  int rc = srr_render_adaptive(r, p, a, d, dc, stats);
+  MEMCHK(d.grow(at_least_16_bytes<float>(3 * npix)), SRR_EIO, "adaptive staging image");
+  MEMCHK(dc.grow(at_least_16_bytes<int32_t>(npix)), SRR_ENOMEM, "adaptive count buffer");
+  int rc = srr_render_adaptive(r, p, a, d.get(), dc.get(), stats);
   std::vector<float> h(3 * npix);
   if (rc == 0) {
-    hipError_t e = hipMemcpy(h.data(), d, h.size() * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && count) e = hipMemcpy(count, dc, npix * sizeof(int32_t), hipMemcpyDeviceToHost);
+    hipError_t e = hipMemcpy(h.data(), d.get(), h.size() * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && count) e = hipMemcpy(count, dc.get(), npix * sizeof(int32_t), hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = fail(SRR_EIO, hipGetErrorString(e));
   }
-  hipFree(d);
-  hipFree(dc);
   if (rc < 0) return rc;
   if (mean) std::memcpy(mean, h.data(), h.size() * sizeof(float));
   if (rgb8) srr_tonemap(h.data(), npix, rgb8);
@@ -580,9 +582,10 @@ int srr_render_aov_host(srr_renderer* r, const srr_params* p, int which, float* 
   const int64_t npix = srr_shard_pixels(p, nullptr);
   if (npix < 0) return (int)npix;
   if (npix == 0) return 0;
-  float* d = nullptr;  // albedo [3 npix], normal [3 npix], depth [npix]
+  DeviceMem<float> buf;  // albedo [3 npix], normal [3 npix], depth [npix]
   HIPCHK(hipSetDevice(r->device));
-  HIPCHK(hipMalloc((void**)&d, 7 * npix * sizeof(float)));
+  MEMCHK(buf.grow(7 * npix), SRR_EIO, "AOV staging images");
+  float* const d = buf.get();
   int rc = srr_render_aov(r, p, which, d, d + 3 * npix, d + 6 * npix);
   if (rc == 0) {
     hipError_t e = hipSuccess;
@@ -593,7 +596,6 @@ int srr_render_aov_host(srr_renderer* r, const srr_params* p, int which, float* 
       e = hipMemcpy(depth, d + 6 * npix, npix * sizeof(float), hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = fail(SRR_EIO, hipGetErrorString(e));
   }
-  hipFree(d);
   return rc;
 }
 
@@ -634,11 +636,11 @@ namespace {
 // scratch of srr_denoise, kept per device between calls: two colour images and
 // the guides, float4 per pixel each
 struct DenoiseScratch {
-  float4* buf = nullptr;
-  size_t cap = 0;  // pixels
+  DeviceMem<float4> buf;  // [3][pixels]
 };
 std::mutex g_dn_mu;
-std::map<int, DenoiseScratch> g_dn_scratch;
+// (never destroyed: at process exit the HIP runtime may be gone before this library's statics)
+std::map<int, DenoiseScratch>& g_dn_scratch = *new std::map<int, DenoiseScratch>;
 }  // namespace
 
 int srr_denoise(int device, int nx, int ny, const srr_denoise_params* dp, const float* d_color,
@@ -655,16 +657,9 @@ int srr_denoise(int device, int nx, int ny, const srr_denoise_params* dp, const 
   std::lock_guard<std::mutex> lock(g_dn_mu);
   HIPCHK(hipSetDevice(device));
   DenoiseScratch& W = g_dn_scratch[device];
-  if (n > W.cap) {
-    (void)hipFree(W.buf);
-    W.buf = nullptr;
-    W.cap = 0;
-    if (hipMalloc((void**)&W.buf, 3 * n * sizeof(float4)) != hipSuccess)
-      return fail(SRR_ENOMEM, "srr_denoise: hipMalloc of the scratch images failed");
-    W.cap = n;
-  }
-  float4* x[2] = {W.buf, W.buf + n};
-  float4* guide = W.buf + 2 * n;
+  MEMCHK(W.buf.grow(3 * n), SRR_ENOMEM, "srr_denoise: scratch images");
+  float4* x[2] = {W.buf.get(), W.buf.get() + n};
+  float4* guide = W.buf.get() + 2 * n;
   const bool demod = (dp->flags & SRR_DENOISE_DEMODULATE) != 0;
   hipStream_t st = nullptr;  // the caller's inputs were written on the legacy stream or are complete
   launch_denoise_pack((int64_t)n, d_color, demod ? d_albedo : nullptr, d_normal, d_depth, x[0], guide, st);
@@ -693,9 +688,10 @@ int srr_denoise_host(int device, int nx, int ny, const srr_denoise_params* dp, c
                      const float* albedo, const float* normal, const float* depth, float* out) {
   if (const int rc = denoise_check(device, nx, ny, dp, color, albedo, normal, depth, out)) return rc;
   const size_t n = (size_t)nx * ny;
-  float* d = nullptr;  // colour, albedo, normal [3n each], depth [n], output [3n]
+  DeviceMem<float> buf;  // colour, albedo, normal [3n each], depth [n], output [3n]
   HIPCHK(hipSetDevice(device));
-  HIPCHK(hipMalloc((void**)&d, 13 * n * sizeof(float)));
+  MEMCHK(buf.grow(13 * n), SRR_EIO, "srr_denoise_host: staging images");
+  float* const d = buf.get();
   float *dc = d, *da = d + 3 * n, *dn = d + 6 * n, *dz = d + 9 * n, *dout = d + 10 * n;
   hipError_t e = hipMemcpy(dc, color, 3 * n * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(da, albedo, 3 * n * sizeof(float), hipMemcpyHostToDevice);
@@ -706,7 +702,6 @@ int srr_denoise_host(int device, int nx, int ny, const srr_denoise_params* dp, c
     e = hipMemcpy(out, dout, 3 * n * sizeof(float), hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = fail(SRR_EIO, hipGetErrorString(e));
   }
-  hipFree(d);
   return rc;
 }
 
@@ -725,16 +720,15 @@ int srr_render(srr_renderer* r, const srr_params* p, float* mean, unsigned char*
   int64_t npix = r->multi ? (p->nx > 0 && p->ny > 0 ? (int64_t)p->nx * p->ny : -1) : srr_shard_pixels(p, nullptr);
   if (npix < 0 && r->multi) return fail(SRR_EINVAL, "bad params");
   if (npix < 0) return (int)npix;
-  float* d = nullptr;
+  DeviceMem<float> d;
   HIPCHK(hipSetDevice(r->device));
-  HIPCHK(hipMalloc((void**)&d, 3 * npix * sizeof(float)));
-  int rc = srr_render_device(r, p, d, stats);
+  MEMCHK(d.grow(3 * npix), SRR_EIO, "staging image");
+  int rc = srr_render_device(r, p, d.get(), stats);
   std::vector<float> h(3 * npix);
   if (rc == 0) {
-    hipError_t e = hipMemcpy(h.data(), d, h.size() * sizeof(float), hipMemcpyDeviceToHost);
+    hipError_t e = hipMemcpy(h.data(), d.get(), h.size() * sizeof(float), hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = fail(SRR_EIO, hipGetErrorString(e));
   }
-  hipFree(d);
   if (rc < 0) return rc;
   if (mean) std::memcpy(mean, h.data(), h.size() * sizeof(float));
   if (rgb8) srr_tonemap(h.data(), npix, rgb8);
@@ -748,7 +742,7 @@ int srr_accum_get(srr_renderer* r, float* sums, int64_t* npix, int64_t* samples)
   if (samples) *samples = r->acc_samples;
   if (sums && r->acc_npix) {
     HIPCHK(hipSetDevice(r->device));
-    HIPCHK(hipMemcpy(sums, r->acc, 3 * r->acc_npix * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sums, r->acc.get(), 3 * r->acc_npix * sizeof(float), hipMemcpyDeviceToHost));
   }
   return 0;
 }
@@ -758,18 +752,8 @@ int srr_accum_set(srr_renderer* r, const float* sums, int64_t npix, int64_t samp
   if (r && r->multi) return fail(SRR_EINVAL, "progressive sums and kept paths are per device: use a one-device renderer");
   HIPCHK(hipSetDevice(r->device));
   drain_async(r);  // frames in flight read the pixel list this may reallocate
-  if ((size_t)npix > r->pix_cap) {
-    r->pix_key[0] = -1;  // the held pixel list goes with the buffer
-    (void)hipFree(r->pixels);
-    (void)hipFree(r->acc);
-    r->pixels = nullptr;
-    r->acc = nullptr;
-    r->pix_cap = 0;
-    HIPCHK(hipMalloc((void**)&r->pixels, npix * sizeof(int32_t)));
-    HIPCHK(hipMalloc((void**)&r->acc, 3 * npix * sizeof(float)));
-    r->pix_cap = npix;
-  }
-  HIPCHK(hipMemcpy(r->acc, sums, 3 * npix * sizeof(float), hipMemcpyHostToDevice));
+  MEMCHK(ensure_pixels(r, npix), SRR_EIO, "pixel list and running sums");
+  HIPCHK(hipMemcpy(r->acc.get(), sums, 3 * npix * sizeof(float), hipMemcpyHostToDevice));
   r->acc_npix = npix;
   r->acc_samples = samples;
   std::fill(r->acc_key, r->acc_key + 5, -1);  // any frame / shard of npix pixels may continue them
@@ -778,10 +762,10 @@ int srr_accum_set(srr_renderer* r, const float* sums, int64_t npix, int64_t samp
 
 int srr_copy_paths(srr_renderer* r, float* radiance, unsigned char* rays) {
   if (r && r->multi) return fail(SRR_EINVAL, "progressive sums and kept paths are per device: use a one-device renderer");
-  if (!r || !r->raw_all) return fail(SRR_EINVAL, "render with SRR_FLAG_KEEP_PATHS first");
+  if (!r || !r->raw_all.get()) return fail(SRR_EINVAL, "render with SRR_FLAG_KEEP_PATHS first");
   HIPCHK(hipSetDevice(r->device));
-  if (radiance) HIPCHK(hipMemcpy(radiance, r->raw_all, r->kept_paths * 3 * sizeof(float), hipMemcpyDeviceToHost));
-  if (rays) HIPCHK(hipMemcpy(rays, r->rays_all, r->kept_paths, hipMemcpyDeviceToHost));
+  if (radiance) HIPCHK(hipMemcpy(radiance, r->raw_all.get(), r->kept_paths * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (rays) HIPCHK(hipMemcpy(rays, r->rays_all.get(), r->kept_paths, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -883,7 +867,7 @@ void srr_image_free(unsigned char* pixels) { free(pixels); }
 // ---- MERL tables (brdf.h)
 struct srr_merl {
   int device = 0;
-  double* table = nullptr;  // device: 3 * merl::kCells doubles
+  DeviceMem<double> table;  // 3 * merl::kCells doubles
 };
 
 int srr_merl_create(const double* table, int64_t n_doubles, int device, srr_merl** out) {
@@ -892,11 +876,9 @@ int srr_merl_create(const double* table, int64_t n_doubles, int device, srr_merl
   HIPCHK(hipSetDevice(device));
   auto m = std::make_unique<srr_merl>();
   m->device = device;
-  HIPCHK(hipMalloc((void**)&m->table, (size_t)n_doubles * sizeof(double)));
-  if (hipMemcpy(m->table, table, (size_t)n_doubles * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(m->table);
+  MEMCHK(m->table.grow((size_t)n_doubles), SRR_EIO, "MERL table");
+  if (hipMemcpy(m->table.get(), table, (size_t)n_doubles * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
     return fail(SRR_EIO, "MERL table upload failed");
-  }
   *out = m.release();
   return 0;
 }
@@ -922,7 +904,6 @@ int srr_merl_load(const char* path, int device, srr_merl** out) {  // brdf::read
 void srr_merl_destroy(srr_merl* m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
-  (void)hipFree(m->table);
   delete m;
 }
 
@@ -934,7 +915,7 @@ int srr_merl_lookup(srr_merl* m, int64_t n, const double* angles, double* rgb, i
   DevBuf<double> d_ang(angles, 4 * (size_t)n, rc), d_rgb(3 * (size_t)n, rc);
   DevBuf<int32_t> d_cell(cell ? (size_t)n : 0, rc);
   if (rc) return rc;
-  if (launch_merl_lookup(m->table, n, d_ang.get(), d_rgb.get(), d_cell.get()) < 0) return fail(SRR_EIO, "MERL kernel launch failed");
+  if (launch_merl_lookup(m->table.get(), n, d_ang.get(), d_rgb.get(), d_cell.get()) < 0) return fail(SRR_EIO, "MERL kernel launch failed");
   if (hipDeviceSynchronize() != hipSuccess || !d_rgb.download(rgb, 3 * (size_t)n) || (cell && !d_cell.download(cell, (size_t)n)))
     return fail(SRR_EIO, "MERL kernel failed");
   return 0;

@@ -15,22 +15,22 @@ namespace srr {
 
 constexpr int kVisitWords = 3 + 2 * 64;  // SRR_FLAG_COUNT_VISITS: sums + two histograms
 
-#define RCHK(x)                                                        \
+// RCHK words a failure by the source expression; RMEM, for allocations and uploads, by the
+// buffer's name ("bounce records: out of memory")
+#define RMEM(x, what)                                                  \
   do {                                                                 \
     hipError_t e_ = (x);                                               \
     if (e_ != hipSuccess) {                                            \
-      err = std::string(#x) + ": " + hipGetErrorString(e_);            \
+      err = std::string(what) + ": " + hipGetErrorString(e_);          \
       return SRR_EIO;                                                  \
     }                                                                  \
   } while (0)
+#define RCHK(x) RMEM(x, #x)
 
 template <class T>
-static hipError_t upload(T** dst, const std::vector<T>& v, std::vector<void*>& keep) {
-  size_t bytes = std::max<size_t>(v.size() * sizeof(T), 16);
-  hipError_t e = hipMalloc((void**)dst, bytes);
-  if (e != hipSuccess) return e;
-  keep.push_back(*dst);
-  if (!v.empty()) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+static hipError_t upload(T** dst, const std::vector<T>& v, DeviceBag& keep) {
+  hipError_t e = keep.add(dst, v.size());
+  if (e == hipSuccess && !v.empty()) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
   return e;
 }
 
@@ -46,7 +46,8 @@ int renderer_create_flat(const Flat& F, int device, srr_renderer** out, std::str
   r->device = device;
   if (const char* e = getenv("SRR_LANES")) r->n_lanes = std::max(1, std::min(kMaxLanes, atoi(e)));
   RCHK(hipSetDevice(device));
-  std::vector<void*>& K = r->scene_bufs;
+  DeviceBag& K = r->scene_bufs;
+#define UPLOAD(dst, v) RMEM(upload(&dst, v, K), "scene table " #v)
   DObj* objs; DXform* xf; DSphere* sph; DRect* rct; DStandaloneTri* st; DMesh* me; float* nodes; float* n4;
   float* tp; TriShade* ts; DMedium* md; DMat* mt; DTex* tx; uint8_t* im; float* pr; int32_t* pp; DLight* li;
   DCamera* cm;
@@ -55,17 +56,17 @@ int renderer_create_flat(const Flat& F, int device, srr_renderer** out, std::str
   DSGroup* sg;
   DSGItem* sgi;
   std::vector<DCamera> cam{F.cam};
-  RCHK(upload(&objs, F.objs, K));
-  RCHK(upload(&xf, F.xforms, K));
-  RCHK(upload(&sph, F.spheres, K));
-  RCHK(upload(&rct, F.rects, K));
-  RCHK(upload(&st, F.stris, K));
-  RCHK(upload(&me, F.meshes, K));
-  RCHK(upload(&nodes, F.nodes, K));
-  RCHK(upload(&n4, F.node4, K));
+  UPLOAD(objs, F.objs);
+  UPLOAD(xf, F.xforms);
+  UPLOAD(sph, F.spheres);
+  UPLOAD(rct, F.rects);
+  UPLOAD(st, F.stris);
+  UPLOAD(me, F.meshes);
+  UPLOAD(nodes, F.nodes);
+  UPLOAD(n4, F.node4);
   float* n4q;
-  RCHK(upload(&n4q, F.node4q, K));
-  RCHK(upload(&tp, F.tri_pos, K));
+  UPLOAD(n4q, F.node4q);
+  UPLOAD(tp, F.tri_pos);
   // the walk's leaf-pair records (kernels.h SceneView::tri_edge): record i (128 B) holds
   // p0, e1 = p1 - p0, e2 = p2 - p0 of triangles i and i+1 (the last repeats itself), the
   // float differences tri_hit's front test forms -- computed here, they round the same
@@ -83,21 +84,21 @@ int renderer_create_flat(const Flat& F, int device, srr_renderer** out, std::str
           o[6 + c] = q[8 + c] - q[c];
         }
       }
-    RCHK(upload(&tedge, pr, K));
+    RMEM(upload(&tedge, pr, K), "scene table tri_edge");
   }
-  RCHK(upload(&ts, F.tri_shade, K));
-  RCHK(upload(&md, F.media, K));
-  RCHK(upload(&ob, F.obvhs, K));
-  RCHK(upload(&oc, F.obvh_children, K));
-  RCHK(upload(&sg, F.sgroups, K));
-  RCHK(upload(&sgi, F.sg_items, K));
-  RCHK(upload(&mt, F.mats, K));
-  RCHK(upload(&tx, F.texs, K));
-  RCHK(upload(&im, F.images, K));
-  RCHK(upload(&pr, F.perlin_ranvec, K));
-  RCHK(upload(&pp, F.perlin_perm, K));
-  RCHK(upload(&li, F.lights, K));
-  RCHK(upload(&cm, cam, K));
+  UPLOAD(ts, F.tri_shade);
+  UPLOAD(md, F.media);
+  UPLOAD(ob, F.obvhs);
+  UPLOAD(oc, F.obvh_children);
+  UPLOAD(sg, F.sgroups);
+  UPLOAD(sgi, F.sg_items);
+  UPLOAD(mt, F.mats);
+  UPLOAD(tx, F.texs);
+  UPLOAD(im, F.images);
+  UPLOAD(pr, F.perlin_ranvec);
+  UPLOAD(pp, F.perlin_perm);
+  UPLOAD(li, F.lights);
+  UPLOAD(cm, cam);
   // world-traversal tables packed for LDS staging (kernels.h SceneView::world_blob)
   std::vector<uint8_t> blob;
   int off[10];
@@ -117,7 +118,8 @@ int renderer_create_flat(const Flat& F, int device, srr_renderer** out, std::str
   put(8, F.texs.data(), F.texs.size() * sizeof(DTex));
   put(9, F.lights.data(), F.lights.size() * sizeof(DLight));
   uint8_t* wb;
-  RCHK(upload(&wb, blob, K));
+  UPLOAD(wb, blob);
+#undef UPLOAD
   SceneView& V = r->view;
   V.world_blob = (const uint4*)wb;
   V.world_words = (int)(blob.size() / 16);
@@ -207,52 +209,46 @@ int renderer_create_flat(const Flat& F, int device, srr_renderer** out, std::str
       RCHK(hipEventCreateWithFlags(&L.done_ev[k], hipEventDisableTiming));
       RCHK(hipEventCreateWithFlags(&L.acc_ev[k], hipEventDisableTiming));
     }
-    RCHK(hipMalloc((void**)&L.cnt, 16 * sizeof(int32_t)));
-    RCHK(hipHostMalloc((void**)&L.rb, 16 * sizeof(int32_t)));
+    RMEM(L.cnt.grow(16), "lane counters");
+    RMEM(L.rb.grow(16), "lane counters' host mirror");
   }
   *out = r.release();
   return 0;
 }
 
-static void free_lane_paths(Lane& L) {
-  for (void* p : L.bufs) (void)hipFree(p);
-  L.bufs.clear();
-  L.cap = 0;
-  L.P = PathState{};
-  L.act[0] = L.act[1] = nullptr;
-  L.lists = nullptr;
-}
-
-template <class T>
-static hipError_t lane_alloc(Lane& L, T** p, size_t n) {
-  hipError_t e = hipMalloc((void**)p, std::max<size_t>(n * sizeof(T), 16));
-  if (e == hipSuccess) L.bufs.push_back(*p);
+// PathState's depth-0 members for n paths (rays, RNG, depth, spec, hit record), the state a
+// first hit needs: all the AOVs allocate, the start of a lane's pool.  P starts afresh.
+static hipError_t alloc_depth0(DeviceBag& bag, PathState& P, size_t n) {
+  P = PathState{};
+  hipError_t e = bag.add(&P.ray_o, n);
+  if (e == hipSuccess) e = bag.add(&P.ray_d, n);
+  if (e == hipSuccess) e = bag.add(&P.lcg, n);
+  if (e == hipSuccess) e = bag.add(&P.pcg, n);
+  if (e == hipSuccess) e = bag.add(&P.depth, n);
+  if (e == hipSuccess) e = bag.add(&P.spec, n);
+  if (e == hipSuccess) e = bag.add(&P.hit_w, n);
+  if (e == hipSuccess) e = bag.add(&P.hit_p, n);
+  if (e == hipSuccess) e = bag.add(&P.hit_n, n);
   return e;
 }
 
 static int ensure_lane(Lane& L, size_t n, int depth, bool keep, std::string& err) {
   int d = std::max(depth, 1);
   if (n <= L.cap && d <= L.cap_depth && (!keep || L.has_raw)) return 0;
-  free_lane_paths(L);
+  L.bufs.clear();
+  L.cap = 0;  // (until every buffer is there: a failure below leaves a pool that the next call replaces)
+  L.act[0] = L.act[1] = L.lists = nullptr;
   PathState& P = L.P;
-  RCHK(lane_alloc(L, &P.ray_o, n));
-  RCHK(lane_alloc(L, &P.ray_d, n));
-  RCHK(lane_alloc(L, &P.lcg, n));
-  RCHK(lane_alloc(L, &P.pcg, n));
-  RCHK(lane_alloc(L, &P.depth, n));
-  RCHK(lane_alloc(L, &P.spec, n));
-  RCHK(lane_alloc(L, &P.hit_w, n));
-  RCHK(lane_alloc(L, &P.hit_p, n));
-  RCHK(lane_alloc(L, &P.hit_n, n));
-  RCHK(lane_alloc(L, &P.rec_a, n * d));
-  RCHK(lane_alloc(L, &P.sample, 3 * n));
-  RCHK(lane_alloc(L, &L.lists, 4 * n));
-  RCHK(lane_alloc(L, &L.act[0], n));
-  RCHK(lane_alloc(L, &L.act[1], n));
+  RMEM(alloc_depth0(L.bufs, P, n), "lane path state");
+  RMEM(L.bufs.add(&P.rec_a, n * d), "lane bounce records");
+  RMEM(L.bufs.add(&P.sample, 3 * n), "lane samples");
+  RMEM(L.bufs.add(&L.lists, 4 * n), "lane family lists");
+  RMEM(L.bufs.add(&L.act[0], n), "lane active list");
+  RMEM(L.bufs.add(&L.act[1], n), "lane active list");
   L.has_raw = keep;
   if (keep) {
-    RCHK(lane_alloc(L, &P.raw, 3 * n));
-    RCHK(lane_alloc(L, &P.rays, n));
+    RMEM(L.bufs.add(&P.raw, 3 * n), "lane kept radiance");
+    RMEM(L.bufs.add(&P.rays, n), "lane kept ray counts");
   }
   L.cap = n;
   L.cap_depth = d;
@@ -296,7 +292,7 @@ static int begin_accum(srr_renderer* r, const srr_params* p, int64_t npix, hipSt
     return 0;
   }
   if (zero_pending) *zero_pending = true;
-  else RCHK(hipMemsetAsync(r->acc, 0, 3 * npix * sizeof(float), st));
+  else RCHK(hipMemsetAsync(r->acc.get(), 0, 3 * npix * sizeof(float), st));
   r->acc_npix = npix;
   r->acc_samples = 0;
   std::copy(key, key + 5, r->acc_key);
@@ -307,40 +303,42 @@ static int begin_accum(srr_renderer* r, const srr_params* p, int64_t npix, hipSt
 // to it); an identity list is not uploaded (the path engine does not read it).
 static hipError_t stage_pixels(srr_renderer* r, const int32_t* pix, int64_t npix, bool identity) {
   r->pix_key[0] = -1;  // srr_render_device sets the key once the render succeeds
-  if ((size_t)npix > r->pix_cap) {
-    (void)hipFree(r->pixels);
-    (void)hipFree(r->acc);
-    r->pixels = nullptr;
-    r->acc = nullptr;
-    r->pix_cap = 0;
-    // the running sums went with the old buffer: nothing may continue them
-    r->acc_npix = 0;
-    r->acc_samples = 0;
-    std::fill(r->acc_key, r->acc_key + 5, -1);
-    hipError_t e = hipMalloc((void**)&r->pixels, npix * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&r->acc, 3 * npix * sizeof(float));
-    if (e != hipSuccess) return e;
-    r->pix_cap = npix;
-  }
+  const hipError_t e = ensure_pixels(r, npix);
+  if (e != hipSuccess) return e;
   r->pix_identity = identity;
-  return identity ? hipSuccess : hipMemcpy(r->pixels, pix, npix * sizeof(int32_t), hipMemcpyHostToDevice);
+  return identity ? hipSuccess : hipMemcpy(r->pixels.get(), pix, npix * sizeof(int32_t), hipMemcpyHostToDevice);
 }
 
-// The device Sobol set holds the first sobol_n points; the set is a
+hipError_t ensure_pixels(srr_renderer* r, int64_t npix) {
+  if ((size_t)npix <= r->pixels.capacity()) return hipSuccess;
+  // the held list and the running sums go with the old buffers: nothing may continue them
+  r->pix_key[0] = -1;
+  r->acc_npix = 0;
+  r->acc_samples = 0;
+  std::fill(r->acc_key, r->acc_key + 5, -1);
+  return grow_pair(r->pixels, (size_t)npix, r->acc, 3 * (size_t)npix);
+}
+
+// A device Sobol set holds the first `have` points; the set is a
 // prefix-stable sequence (tests/test_dist_gloo.py), so it is generated and
 // uploaded only when a render needs more points than it holds.
-static hipError_t ensure_sobol(srr_renderer* r, int n_sobol) {
-  if (n_sobol <= r->sobol_n) return hipSuccess;
-  (void)hipFree(r->sobol);
-  r->sobol = nullptr;
-  r->sobol_n = 0;
-  hipError_t e = hipMalloc((void**)&r->sobol, 2 * (size_t)n_sobol * sizeof(double));
+static hipError_t ensure_sobol(DeviceMem<double>& set, int& have, int n_sobol) {
+  if (n_sobol <= have) return hipSuccess;
+  have = 0;
+  hipError_t e = set.grow(2 * (size_t)n_sobol);
   if (e != hipSuccess) return e;
   std::vector<double> sp(2 * (size_t)n_sobol);
   sobol2((unsigned)n_sobol, sp.data());
-  e = hipMemcpy(r->sobol, sp.data(), sp.size() * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) r->sobol_n = n_sobol;
+  e = hipMemcpy(set.get(), sp.data(), sp.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) have = n_sobol;
   return e;
+}
+
+// SRR_FLAG_KEEP_PATHS: room for this frame's `need` paths, in both buffers or in neither
+static int ensure_kept(srr_renderer* r, size_t need, std::string& err) {
+  RMEM(grow_pair(r->raw_all, 3 * need, r->rays_all, need), "kept paths");
+  r->kept_paths = (int64_t)need;
+  return 0;
 }
 
 // Invalidates the running sums unless the render that began them committed:
@@ -365,32 +363,18 @@ static int slot_init(FrameSlot& F, hipStream_t shared_st, std::string& err) {
   }
   RCHK(hipEventCreate(&F.ev_beg));
   RCHK(hipEventCreate(&F.ev_end));
-  RCHK(hipMalloc((void**)&F.ctr, kPathsCtrWords * sizeof(unsigned long long)));
-  RCHK(hipHostMalloc((void**)&F.ctr_host, kPathsCtrWords * sizeof(unsigned long long)));
+  RMEM(F.ctr.grow(kPathsCtrWords), "frame counters");
+  RMEM(F.ctr_host.grow(kPathsCtrWords), "frame counters' host mirror");
   return 0;
 }
 
-void slot_free(FrameSlot& F) {
-  (void)hipFree(F.rec);
-  (void)hipFree(F.gstack);
-  (void)hipFree(F.sample);
-  (void)hipFree(F.ctr);
-  (void)hipFree(F.acc);
-  if (F.ctr_host) (void)hipHostFree(F.ctr_host);
+// the slot's events and its own stream; the buffers go with the slot itself
+static void slot_destroy(FrameSlot& F) {
   for (hipEvent_t e : F.win_ev) (void)hipEventDestroy(e);
   if (F.ev_beg) (void)hipEventDestroy(F.ev_beg);
   if (F.ev_end) (void)hipEventDestroy(F.ev_end);
   if (F.own_stream && F.st) (void)hipStreamDestroy(F.st);
   F = FrameSlot{};
-}
-
-// frees a slot's sample window (the largest per-frame buffer); the next frame
-// on the slot allocates it again
-static void release_window(FrameSlot& F) {
-  if (!F.sample) return;
-  (void)hipFree(F.sample);
-  F.sample = nullptr;
-  F.sample_cap = 0;
 }
 
 // Path-resident engine (kernels.hip k_paths): one persistent kernel per window
@@ -418,20 +402,14 @@ static int paths_prepare(srr_renderer* r, FrameSlot& F, int max_depth, PathsSetu
   // launched: diffuse only, no media; 16 B x lanes x max_depth more, 210 MB per slot at depth 50)
   const bool head_cols = r->diffuse_only && !r->view.has_media;
   const size_t rec_need = (head_cols ? 2 : 1) * (size_t)r->pw_lanes * std::max(1, max_depth);
-  if (rec_need > F.rec_cap) {
-    (void)hipFree(F.rec);
-    F.rec = nullptr;
-    F.rec_cap = 0;
-    RCHK(hipMalloc((void**)&F.rec, rec_need * sizeof(float4)));
-    F.rec_cap = rec_need;
-  }
+  RMEM(F.rec.grow(rec_need), "bounce records");
   // global extension of the BVH4 traversal stack, for meshes deep enough to need it
   // (SRR_GSTACK=0 disables it: every deeper traversal then re-walks the BVH2)
   const char* gs_env = getenv("SRR_GSTACK");
   ps.gst_cap = (r->has_meshes && !(gs_env && !atoi(gs_env))) ? kPathsGlobalStack : 0;
-  // ... followed by the save area of suspended mesh walks (3 float4 per lane)
-  if (ps.gst_cap && !F.gstack)
-    RCHK(hipMalloc((void**)&F.gstack, (size_t)ps.gst_cap * r->pw_lanes * sizeof(int2) + 3 * (size_t)r->pw_lanes * sizeof(float4)));
+  // ... followed by the save area of suspended mesh walks (3 float4, 6 int2's bytes, per lane)
+  static_assert(sizeof(float4) == 2 * sizeof(int2), "the save area is counted in stack entries");
+  if (ps.gst_cap) RMEM(F.gstack.grow(((size_t)ps.gst_cap + 6) * r->pw_lanes), "traversal-stack extension");
   // suspendable mesh walks: a walk still running when at most SRR_WALK_Q / 64
   // of its wave's lanes walk continues in the next wave-iteration (default: the scene's
   // walk_q_default, 8 or 0); SRR_WALK_Q=0 never suspends and launches the kernel variant
@@ -470,27 +448,21 @@ static int window_samples(const PathsSetup& ps, int64_t npix, int spp) {
 
 // The slot's sample window holds at least win_paths paths.
 static int ensure_window(srr_renderer* r, FrameSlot& F, size_t win_paths, std::string& err) {
-  if (win_paths > F.sample_cap) {
-    (void)hipFree(F.sample);
-    F.sample = nullptr;
-    F.sample_cap = 0;
-    hipError_t e = hipMalloc((void**)&F.sample, win_paths * 3 * sizeof(float));
-    if (e == hipErrorOutOfMemory) {
-      // the synchronous slot and the two async slots each keep their window across
-      // mode switches (at most 3 x SRR_WINDOW_MB of the 288 GB); only when the device
-      // runs out are the other mode's windows given back
-      (void)hipGetLastError();
-      if (&F == &r->sync_slot) {
-        drain_async(r);
-        for (FrameSlot& A : r->async_slots) release_window(A);
-      } else {
-        release_window(r->sync_slot);
-      }
-      e = hipMalloc((void**)&F.sample, win_paths * 3 * sizeof(float));
+  hipError_t e = F.sample.grow(3 * win_paths);
+  if (e == hipErrorOutOfMemory) {
+    // the synchronous slot and the two async slots each keep their window across
+    // mode switches (at most 3 x SRR_WINDOW_MB of the 288 GB); only when the device
+    // runs out are the other mode's windows given back (the next frame there allocates again)
+    (void)hipGetLastError();
+    if (&F == &r->sync_slot) {
+      drain_async(r);
+      for (FrameSlot& A : r->async_slots) A.sample.reset();
+    } else {
+      r->sync_slot.sample.reset();
     }
-    RCHK(e);
-    F.sample_cap = win_paths;
+    e = F.sample.grow(3 * win_paths);
   }
+  RMEM(e, "sample window");
   return 0;
 }
 
@@ -500,7 +472,7 @@ static PathWork paths_work(srr_renderer* r, FrameSlot& F, const srr_params* p, c
                            const int32_t* pixels, int64_t npix, int s_first, int Wn) {
   PathWork w{};
   w.pixels = pixels;
-  w.sobol = r->sobol + 2 * (size_t)s_first;
+  w.sobol = r->sobol.get() + 2 * (size_t)s_first;
   w.npix = (int)npix;
   w.spp_w = Wn;
   w.s_base = s_first;
@@ -511,15 +483,15 @@ static PathWork paths_work(srr_renderer* r, FrameSlot& F, const srr_params* p, c
   w.base_seed = p->base_seed;
   w.n_paths = (int64_t)npix * Wn;
   w.max_depth = p->max_depth;
-  w.cursor = F.ctr + kCtrCursor;
-  w.counters = F.ctr;
-  w.sample = F.sample;
-  w.rec = F.rec;
-  w.err = (int*)(F.ctr + kCtrError);
+  w.cursor = F.ctr.get() + kCtrCursor;
+  w.counters = F.ctr.get();
+  w.sample = F.sample.get();
+  w.rec = F.rec.get();
+  w.err = (int*)(F.ctr.get() + kCtrError);
   const int64_t bl = paths_block_lanes(r->view);  // whole blocks of the launch's size
   w.lanes = (int)std::min<int64_t>(r->pw_lanes, ((w.n_paths + bl - 1) / bl) * bl);
   w.stack_cap = ps.stack_cap;
-  w.gstack = ps.gst_cap ? F.gstack : nullptr;
+  w.gstack = ps.gst_cap ? F.gstack.get() : nullptr;
   w.gstack_cap = ps.gst_cap;
   w.deep_tries = ps.deep_tries;
   w.walk_q = ps.gst_cap ? ps.walk_q : 0;  // (the save area follows the global stack extension)
@@ -547,7 +519,7 @@ static int paths_enqueue(srr_renderer* r, FrameSlot& F, const srr_params* p, boo
     const int rc = ensure_window(r, F, (size_t)npix * W, err);
     if (rc < 0) return rc;
   }
-  RCHK(hipMemsetAsync(F.ctr, 0, kPathsCtrWords * sizeof(unsigned long long), st));
+  RCHK(hipMemsetAsync(F.ctr.get(), 0, kPathsCtrWords * sizeof(unsigned long long), st));
   const bool want_sums = (p->flags & SRR_FLAG_SUMS) != 0;
   // per-window HIP events around k_paths, read once the frame is done (no host
   // round trip between windows)
@@ -563,26 +535,26 @@ static int paths_enqueue(srr_renderer* r, FrameSlot& F, const srr_params* p, boo
   static const bool want_wave_times = getenv("SRR_WAVE_TIMES") != nullptr;
   unsigned long long* wave_times = nullptr;
   const int n_waves = (r->pw_lanes + 63) / 64;
-  if (want_wave_times && diagnostics) {  // owned by the renderer (freed in ~srr_renderer), so no early return leaks it
-    if (!r->pw_wave_times) RCHK(hipMalloc((void**)&r->pw_wave_times, 4 * (size_t)n_waves * sizeof(unsigned long long)));
-    wave_times = r->pw_wave_times;
+  if (want_wave_times && diagnostics) {
+    RMEM(r->pw_wave_times.grow(4 * (size_t)n_waves), "wave times");
+    wave_times = r->pw_wave_times.get();
     RCHK(hipMemsetAsync(wave_times, 0, 4 * (size_t)n_waves * sizeof(unsigned long long), st));
   }
 #ifdef SRR_SLOW_RAYS
-  if (!r->pw_slow) RCHK(hipMalloc((void**)&r->pw_slow, (16 * 65536 + 16) * sizeof(float)));
-  RCHK(hipMemsetAsync(r->pw_slow + 16 * 65536, 0, 16 * sizeof(float), st));
+  RMEM(r->pw_slow.grow(16 * 65536 + 16), "slow-ray records");
+  RCHK(hipMemsetAsync(r->pw_slow.get() + 16 * 65536, 0, 16 * sizeof(float), st));
 #endif
   RCHK(hipEventRecord(F.ev_beg, st));
   for (int s0 = 0; s0 < p->spp; s0 += W) {
     const int Wn = std::min(W, p->spp - s0);
-    PathWork w = paths_work(r, F, p, ps, identity ? nullptr : r->pixels, npix, p->sample_begin + s0, Wn);
-    w.raw = keep ? r->raw_all : nullptr;
-    w.rays = keep ? r->rays_all : nullptr;
+    PathWork w = paths_work(r, F, p, ps, identity ? nullptr : r->pixels.get(), npix, p->sample_begin + s0, Wn);
+    w.raw = keep ? r->raw_all.get() : nullptr;
+    w.rays = keep ? r->rays_all.get() : nullptr;
     w.keep_spp = p->spp;
     w.keep_s0 = s0;
     w.wave_times = wave_times;
-    w.slow_rays = diagnostics ? r->pw_slow : nullptr;
-    w.slow_count = w.slow_rays ? (unsigned*)(r->pw_slow + 16 * 65536) : nullptr;
+    w.slow_rays = diagnostics ? r->pw_slow.get() : nullptr;
+    w.slow_count = w.slow_rays ? (unsigned*)(r->pw_slow.get() + 16 * 65536) : nullptr;
     const int wi = s0 / W;
     if (wi > 0) RCHK(hipMemsetAsync(w.cursor, 0, sizeof(unsigned long long), st));  // window 0: zeroed with ctr
     RCHK(hipEventRecord(F.win_ev[2 * wi], st));
@@ -594,7 +566,7 @@ static int paths_enqueue(srr_renderer* r, FrameSlot& F, const srr_params* p, boo
     RCHK(hipEventRecord(F.win_ev[2 * wi + 1], st));
     // the last window also writes the output (k_finish fused): means, or raw sums (SRR_FLAG_SUMS)
     const bool last = s0 + Wn >= p->spp;
-    launch_accumulate_window(F.sample, (int)npix, Wn, acc, st, wi == 0 && zero_pending, last ? d_mean : nullptr,
+    launch_accumulate_window(F.sample.get(), (int)npix, Wn, acc, st, wi == 0 && zero_pending, last ? d_mean : nullptr,
                              want_sums ? 0 : (int)acc_total);
     if (wave_times) {  // realtime clock: 100 MHz (10 ns ticks)
       RCHK(hipEventSynchronize(F.win_ev[2 * wi + 1]));
@@ -632,7 +604,7 @@ static int paths_enqueue(srr_renderer* r, FrameSlot& F, const srr_params* p, boo
     else
       launch_finish(acc, d_mean, npix, (int)acc_total, st);
   }
-  RCHK(hipMemcpyAsync(F.ctr_host, F.ctr, kPathsCtrWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  RCHK(hipMemcpyAsync(F.ctr_host.get(), F.ctr.get(), kPathsCtrWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   RCHK(hipEventRecord(F.ev_end, st));
   F.npix = npix;
   F.paths = npix * p->spp;
@@ -650,7 +622,7 @@ static int paths_finish(srr_renderer* r, FrameSlot& F, const srr_params* p, srr_
     kernel_ms += ms;
   }
   unsigned long long ctr[kPathsCtrWords];
-  std::memcpy(ctr, F.ctr_host, sizeof(ctr));
+  std::memcpy(ctr, F.ctr_host.get(), sizeof(ctr));
   if (getenv("SRR_PATHS_TIMING") && ctr[kCtrWaveIters]) {
     const double it = (double)ctr[kCtrWaveIters];
     fprintf(stderr, "k_paths per wave-iteration (ticks): refill %.0f  world %.0f  mesh %.0f  record %.0f  scatter %.0f  fold %.0f  (%llu wave-iterations)\n",
@@ -692,12 +664,12 @@ static int paths_finish(srr_renderer* r, FrameSlot& F, const srr_params* p, srr_
             ctr[kCtrTailPasses], per(ctr[kCtrTicksTail], ctr[kCtrTailPasses]), per(ctr[kCtrTailLanes], ctr[kCtrTailPasses]));
   }
 #ifdef SRR_SLOW_RAYS
-  if (r->pw_slow) {  // diagnostics build: dump the slow world hits' records (one line per lane, JSON)
+  if (r->pw_slow.get()) {  // diagnostics build: dump the slow world hits' records (one line per lane, JSON)
     unsigned n = 0;
-    RCHK(hipMemcpy(&n, r->pw_slow + 16 * 65536, sizeof(unsigned), hipMemcpyDeviceToHost));
+    RCHK(hipMemcpy(&n, r->pw_slow.get() + 16 * 65536, sizeof(unsigned), hipMemcpyDeviceToHost));
     n = std::min(n, 65536u);
     std::vector<float> v(16 * (size_t)n);
-    if (n) RCHK(hipMemcpy(v.data(), r->pw_slow, v.size() * sizeof(float), hipMemcpyDeviceToHost));
+    if (n) RCHK(hipMemcpy(v.data(), r->pw_slow.get(), v.size() * sizeof(float), hipMemcpyDeviceToHost));
     auto I = [&](size_t k) { int x; memcpy(&x, &v[k], 4); return x; };
     for (unsigned i = 0; i < n; ++i) {
       const size_t b = 16 * (size_t)i;
@@ -751,9 +723,9 @@ static int paths_stage(srr_renderer* r, const srr_params* p, const int32_t* pix,
   if (pix) {  // a new pixel list (else the renderer holds this shard's already)
     identity = p->shard_count <= 1;
     for (int64_t i = 0; identity && i < npix; i += std::max<int64_t>(1, npix / 64)) identity = pix[i] == i;
-    RCHK(stage_pixels(r, pix, npix, identity));
+    RMEM(stage_pixels(r, pix, npix, identity), "pixel list and running sums");
   }
-  RCHK(ensure_sobol(r, p->sample_begin + p->spp));
+  RMEM(ensure_sobol(r->sobol, r->sobol_n, p->sample_begin + p->spp), "Sobol points");
   return 0;
 }
 
@@ -766,15 +738,8 @@ static int render_paths(srr_renderer* r, const srr_params* p, const int32_t* pix
     if (rc < 0) return rc;
   }
   if (keep) {
-    size_t need = (size_t)npix * p->spp;
-    if (need > r->keep_cap) {
-      (void)hipFree(r->raw_all);
-      (void)hipFree(r->rays_all);
-      RCHK(hipMalloc((void**)&r->raw_all, need * 3 * sizeof(float)));
-      RCHK(hipMalloc((void**)&r->rays_all, need));
-      r->keep_cap = need;
-    }
-    r->kept_paths = (int64_t)need;
+    const int rc = ensure_kept(r, (size_t)npix * p->spp, err);
+    if (rc < 0) return rc;
   }
   FrameSlot& F = r->sync_slot;
   {
@@ -790,7 +755,7 @@ static int render_paths(srr_renderer* r, const srr_params* p, const int32_t* pix
   AccCommit commit{r};
   const int64_t acc_total = r->acc_samples + p->spp;
   {
-    const int rc = paths_enqueue(r, F, p, identity, npix, r->acc, zero_pending, acc_total, d_mean, true, err);
+    const int rc = paths_enqueue(r, F, p, identity, npix, r->acc.get(), zero_pending, acc_total, d_mean, true, err);
     if (rc < 0) {
       (void)hipStreamSynchronize(F.st);  // windows already enqueued must not outlive the error
       return rc;
@@ -806,30 +771,18 @@ static int render_paths(srr_renderer* r, const srr_params* p, const int32_t* pix
 }
 
 // ---- adaptive sampling (include/srr_capi.h srr_render_adaptive)
-void free_adaptive(AdaptiveState& A) {
-  (void)hipFree(A.mom);
-  for (int k = 0; k < 2; ++k) {
-    (void)hipFree(A.slot[k]);
-    (void)hipFree(A.pixel[k]);
-  }
-  (void)hipFree(A.keep);
-  (void)hipFree(A.blk);
-  if (A.n_host) (void)hipHostFree(A.n_host);
-  A = AdaptiveState{};
-}
-
 static int ensure_adaptive(AdaptiveState& A, size_t npix, std::string& err) {
   if (npix <= A.cap) return 0;
-  free_adaptive(A);
-  RCHK(hipMalloc((void**)&A.mom, npix * sizeof(float2)));
+  A = AdaptiveState{};  // every old buffer goes before the first new one comes
+  RMEM(A.mom.grow(npix), "adaptive moments");
   for (int k = 0; k < 2; ++k) {
-    RCHK(hipMalloc((void**)&A.slot[k], npix * sizeof(int32_t)));
-    RCHK(hipMalloc((void**)&A.pixel[k], npix * sizeof(int32_t)));
+    RMEM(A.slot[k].grow(npix), "adaptive slot list");
+    RMEM(A.pixel[k].grow(npix), "adaptive pixel list");
   }
-  RCHK(hipMalloc((void**)&A.keep, npix));
-  RCHK(hipMalloc((void**)&A.blk, ((npix + 255) / 256 + 1) * sizeof(int32_t)));
-  RCHK(hipHostMalloc((void**)&A.n_host, sizeof(int32_t)));
-  A.cap = npix;
+  RMEM(A.keep.grow(npix), "adaptive keep flags");
+  RMEM(A.blk.grow((npix + 255) / 256 + 1), "adaptive compaction scratch");
+  RMEM(A.n_host.grow(1), "adaptive count's host mirror");
+  A.cap = npix;  // (set last: after a failure above the next call starts afresh)
   return 0;
 }
 
@@ -842,10 +795,10 @@ static int adaptive_passes(srr_renderer* r, FrameSlot& F, const srr_params* p, c
   AdaptiveState& A = r->adaptive;
   hipStream_t st = F.st;
   const int budget = p->spp;
-  const int32_t* shard_pixels = identity ? nullptr : r->pixels;
-  int32_t* n_dev = A.blk + (A.cap + 255) / 256;
+  const int32_t* shard_pixels = identity ? nullptr : r->pixels.get();
+  int32_t* n_dev = A.blk.get() + (A.cap + 255) / 256;
   srr_adaptive_stats s{};
-  RCHK(hipMemsetAsync(F.ctr, 0, kPathsCtrWords * sizeof(unsigned long long), st));
+  RCHK(hipMemsetAsync(F.ctr.get(), 0, kPathsCtrWords * sizeof(unsigned long long), st));
   RCHK(hipEventRecord(F.ev_beg, st));
   int n = 0;     // samples every active pixel holds
   int cur = -1;  // the active lists are A.slot / A.pixel[cur]; -1: every slot, in order
@@ -855,8 +808,8 @@ static int adaptive_passes(srr_renderer* r, FrameSlot& F, const srr_params* p, c
     const int w = std::min(a->batch_spp, budget - n), n_new = n + w;
     // can a pixel retire after this pass?  (if none can, no flags, no compaction, no read-back)
     const bool decide = n_new >= budget || (n_new >= a->min_spp && a->rel_tol > 0.f);
-    const int32_t* slots = cur < 0 ? nullptr : A.slot[cur];
-    const int32_t* pixels = cur < 0 ? shard_pixels : A.pixel[cur];
+    const int32_t* slots = cur < 0 ? nullptr : A.slot[cur].get();
+    const int32_t* pixels = cur < 0 ? shard_pixels : A.pixel[cur].get();
     // the pass in sample windows that fit the slot's buffer (one, unless the frame is huge)
     int W = (int)std::min<int64_t>(window_samples(ps, n_act, w), (int64_t)(win_cap / (size_t)n_act));
     if (W < w && W >= 16) W &= ~3;
@@ -870,19 +823,19 @@ static int adaptive_passes(srr_renderer* r, FrameSlot& F, const srr_params* p, c
         return SRR_EINVAL;
       }
       AdaptiveFold f{};
-      f.sample = F.sample;
+      f.sample = F.sample.get();
       f.active_slot = slots;
       f.n_active = (int)n_act;
       f.spp_w = Wn;
-      f.sums = r->acc;
-      f.mom = A.mom;
+      f.sums = r->acc.get();
+      f.mom = A.mom.get();
       f.init = n + s0 == 0;
       f.decide = decide && s0 + Wn >= w;
       f.n_new = n_new;
       f.budget = budget;
       f.rel_tol = a->rel_tol;
       f.abs_eps = a->abs_eps;
-      f.keep = A.keep;
+      f.keep = A.keep.get();
       f.mean = d_mean;
       f.count = d_count;
       launch_adaptive_fold(f, st);
@@ -893,11 +846,12 @@ static int adaptive_passes(srr_renderer* r, FrameSlot& F, const srr_params* p, c
     if (n >= budget) break;  // the fold retired every active pixel at the budget
     if (!decide) continue;
     const int nxt = cur < 0 ? 0 : cur ^ 1;
-    launch_adaptive_compact(A.keep, slots, (int)n_act, shard_pixels, A.blk, A.slot[nxt], A.pixel[nxt], n_dev, st);
+    launch_adaptive_compact(A.keep.get(), slots, (int)n_act, shard_pixels, A.blk.get(), A.slot[nxt].get(), A.pixel[nxt].get(),
+                            n_dev, st);
     // the one host round trip of a pass: the next launch is sized by the survivors
-    RCHK(hipMemcpyAsync(A.n_host, n_dev, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    RCHK(hipMemcpyAsync(A.n_host.get(), n_dev, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     RCHK(hipStreamSynchronize(st));
-    const int64_t n_next = *A.n_host;
+    const int64_t n_next = *A.n_host.get();
     if (n_next < 0 || n_next > n_act) {
       err = "adaptive compaction returned " + std::to_string(n_next) + " of " + std::to_string(n_act) + " pixels";
       return SRR_EIO;
@@ -906,17 +860,17 @@ static int adaptive_passes(srr_renderer* r, FrameSlot& F, const srr_params* p, c
     n_act = n_next;
     cur = nxt;
   }
-  RCHK(hipMemcpyAsync(F.ctr_host, F.ctr, kPathsCtrWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  RCHK(hipMemcpyAsync(F.ctr_host.get(), F.ctr.get(), kPathsCtrWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   RCHK(hipEventRecord(F.ev_end, st));
   RCHK(hipStreamSynchronize(st));
   RCHK(hipGetLastError());
-  if (F.ctr_host[kCtrError]) {
-    err = "k_paths index guard tripped (bits " + std::to_string(F.ctr_host[kCtrError]) + ")";
+  if (F.ctr_host.get()[kCtrError]) {
+    err = "k_paths index guard tripped (bits " + std::to_string(F.ctr_host.get()[kCtrError]) + ")";
     return SRR_EIO;
   }
   float total = 0;
   RCHK(hipEventElapsedTime(&total, F.ev_beg, F.ev_end));
-  s.world_rays = (int64_t)F.ctr_host[kCtrWorldRays];
+  s.world_rays = (int64_t)F.ctr_host.get()[kCtrWorldRays];
   s.total_ms = total;
   if (stats) {
     s.struct_size = stats->struct_size;
@@ -1001,18 +955,12 @@ int render_device_async(srr_renderer* r, const srr_params* p, const int32_t* pix
     const int rc = slot_init(F, nullptr, err);
     if (rc < 0) return rc;
   }
-  if ((size_t)npix > F.acc_cap) {
-    (void)hipFree(F.acc);
-    F.acc = nullptr;
-    F.acc_cap = 0;
-    RCHK(hipMalloc((void**)&F.acc, 3 * (size_t)npix * sizeof(float)));
-    F.acc_cap = npix;
-  }
+  RMEM(F.acc.grow(3 * (size_t)npix), "async frame sums");
   // the caller's stream order: the frame starts after what the legacy stream holds
   RCHK(hipEventRecord(r->ev_async_in, nullptr));
   RCHK(hipStreamWaitEvent(F.st, r->ev_async_in, 0));
   {
-    const int rc = paths_enqueue(r, F, p, identity, npix, F.acc, true, p->spp, d_mean, false, err);
+    const int rc = paths_enqueue(r, F, p, identity, npix, F.acc.get(), true, p->spp, d_mean, false, err);
     if (rc < 0) {
       // windows already on F.st read the slot's buffers: drain them before the slot is reused
       (void)hipStreamSynchronize(F.st);
@@ -1071,30 +1019,23 @@ int render_device(srr_renderer* r, const srr_params* p, const int32_t* pix, int6
   hipStream_t ast = r->acc_st;
   unsigned long long* visits = nullptr;
   if (p->flags & SRR_FLAG_COUNT_VISITS) {
-    if (!r->visits) RCHK(hipMalloc((void**)&r->visits, kVisitWords * sizeof(unsigned long long)));
-    RCHK(hipMemset(r->visits, 0, kVisitWords * sizeof(unsigned long long)));
-    visits = r->visits;
+    RMEM(r->visits.grow(kVisitWords), "visit counters");
+    visits = r->visits.get();
+    RCHK(hipMemset(visits, 0, kVisitWords * sizeof(unsigned long long)));
   }
   // frame buffers
-  if (pix) RCHK(stage_pixels(r, pix, npix, false));
+  if (pix) RMEM(stage_pixels(r, pix, npix, false), "pixel list and running sums");
   else if (r->pix_identity) {  // the path engine skipped the upload of an identity list
     std::vector<int32_t> id((size_t)npix);
     for (int64_t i = 0; i < npix; ++i) id[i] = (int32_t)i;
-    RCHK(stage_pixels(r, id.data(), npix, false));
+    RMEM(stage_pixels(r, id.data(), npix, false), "pixel list and running sums");
   }
   // Sobol points of the global sample range [sample_begin, sample_begin + spp):
   // the set is a prefix-stable sequence, so a sample shard reads its own slice.
-  RCHK(ensure_sobol(r, p->sample_begin + p->spp));
+  RMEM(ensure_sobol(r->sobol, r->sobol_n, p->sample_begin + p->spp), "Sobol points");
   if (keep) {
-    size_t need = (size_t)npix * p->spp;
-    if (need > r->keep_cap) {
-      (void)hipFree(r->raw_all);
-      (void)hipFree(r->rays_all);
-      RCHK(hipMalloc((void**)&r->raw_all, need * 3 * sizeof(float)));
-      RCHK(hipMalloc((void**)&r->rays_all, need));
-      r->keep_cap = need;
-    }
-    r->kept_paths = (int64_t)need;
+    const int rc = ensure_kept(r, (size_t)npix * p->spp, err);
+    if (rc < 0) return rc;
   }
   // Batches: (pixel chunk, sample chunk) in the order every pixel must see its
   // samples accumulated.
@@ -1107,8 +1048,8 @@ int render_device(srr_renderer* r, const srr_params* p, const int32_t* pix, int6
     int np = (int)std::min<int64_t>(pix_chunk, npix - p0);
     for (int s0 = 0; s0 < p->spp; s0 += S) {
       BatchInfo B{};
-      B.pixels = r->pixels;
-      B.sobol = r->sobol + 2 * (size_t)p->sample_begin;
+      B.pixels = r->pixels.get();
+      B.sobol = r->sobol.get() + 2 * (size_t)p->sample_begin;
       B.s_base = p->sample_begin;
       B.p0 = (int)p0;
       B.spp_batch = std::min(S, p->spp - s0);
@@ -1177,9 +1118,9 @@ int render_device(srr_renderer* r, const srr_params* p, const int32_t* pix, int6
         L.trace_ms += ms;
         RCHK(hipEventElapsedTime(&ms, L.ev_t1, L.ev_s1));
         L.shade_ms += ms;
-        L.n = L.rb[R];
+        L.n = L.rb.get()[R];
         for (int k = 0; k < R; ++k)
-          if (L.reg_batch[k] >= 0 && !b_done[L.reg_batch[k]] && L.rb[k] == 0) {
+          if (L.reg_batch[k] >= 0 && !b_done[L.reg_batch[k]] && L.rb.get()[k] == 0) {
             b_done[L.reg_batch[k]] = 1;
             RCHK(hipEventRecord(L.done_ev[k], L.st));
           }
@@ -1201,7 +1142,7 @@ int render_device(srr_renderer* r, const srr_params* p, const int32_t* pix, int6
         B.active = L.act[L.cur];
         B.act0 = L.n;
         B.slot0 = (int)(fr * region);
-        B.count = L.cnt + L.cur;
+        B.count = L.cnt.get() + L.cur;
         launch_raygen(r->view, L.P, B, L.st);
         L.n += B.n_paths;
         L.reg_batch[fr] = (int)next_batch;
@@ -1213,20 +1154,20 @@ int render_device(srr_renderer* r, const srr_params* p, const int32_t* pix, int6
       }
       if (L.n > 0) {
         int n = L.n, cur = L.cur;
-        int* alive = L.cnt + 2;
+        int* alive = L.cnt.get() + 2;
         int* fam = alive + R;
-        RCHK(hipMemsetAsync(L.cnt + (cur ^ 1), 0, sizeof(int), L.st));
+        RCHK(hipMemsetAsync(L.cnt.get() + (cur ^ 1), 0, sizeof(int), L.st));
         int* fetch = alive + R + 4;  // persistent trace's ray cursor
         RCHK(hipMemsetAsync(alive, 0, (R + 5) * sizeof(int), L.st));
         RCHK(hipEventRecord(L.ev_t0, L.st));
-        launch_trace(r->view, L.P, L.act[cur], L.cnt + cur, n, L.lists, (int)L.cap, fam, fetch, p->max_depth, visits,
+        launch_trace(r->view, L.P, L.act[cur], L.cnt.get() + cur, n, L.lists, (int)L.cap, fam, fetch, p->max_depth, visits,
                      L.st);
         RCHK(hipEventRecord(L.ev_t1, L.st));
-        launch_shade(r->view, L.P, L.lists, (int)L.cap, fam, L.act[cur ^ 1], L.cnt + (cur ^ 1), alive, (int)region,
+        launch_shade(r->view, L.P, L.lists, (int)L.cap, fam, L.act[cur ^ 1], L.cnt.get() + (cur ^ 1), alive, (int)region,
                      n, p->max_depth, L.st);
         RCHK(hipEventRecord(L.ev_s1, L.st));
-        RCHK(hipMemcpyAsync(L.rb, alive, R * sizeof(int), hipMemcpyDeviceToHost, L.st));
-        RCHK(hipMemcpyAsync(L.rb + R, L.cnt + (cur ^ 1), sizeof(int), hipMemcpyDeviceToHost, L.st));
+        RCHK(hipMemcpyAsync(L.rb.get(), alive, R * sizeof(int), hipMemcpyDeviceToHost, L.st));
+        RCHK(hipMemcpyAsync(L.rb.get() + R, L.cnt.get() + (cur ^ 1), sizeof(int), hipMemcpyDeviceToHost, L.st));
         RCHK(hipEventRecord(L.ev_rb, L.st));
         L.pending = true;
         L.cur ^= 1;
@@ -1242,13 +1183,13 @@ int render_device(srr_renderer* r, const srr_params* p, const int32_t* pix, int6
       int rg = b_reg[acc_head];
       BatchInfo& B = batches[acc_head];
       RCHK(hipStreamWaitEvent(ast, L.done_ev[rg], 0));
-      launch_accumulate(L.P, B, r->acc, ast);
+      launch_accumulate(L.P, B, r->acc.get(), ast);
       if (keep) {  // region paths are [pixel][sample-in-batch]; the frame keeps [pixel][spp]
         int np = B.n_paths / B.spp_batch, Sb = B.spp_batch;
-        RCHK(hipMemcpy2DAsync(r->raw_all + 3 * ((size_t)B.p0 * p->spp + B.s0), 3 * sizeof(float) * p->spp,
+        RCHK(hipMemcpy2DAsync(r->raw_all.get() + 3 * ((size_t)B.p0 * p->spp + B.s0), 3 * sizeof(float) * p->spp,
                               L.P.raw + 3 * (size_t)B.slot0, 3 * sizeof(float) * Sb, 3 * sizeof(float) * Sb, np,
                               hipMemcpyDeviceToDevice, ast));
-        RCHK(hipMemcpy2DAsync(r->rays_all + ((size_t)B.p0 * p->spp + B.s0), p->spp, L.P.rays + B.slot0, Sb, Sb, np,
+        RCHK(hipMemcpy2DAsync(r->rays_all.get() + ((size_t)B.p0 * p->spp + B.s0), p->spp, L.P.rays + B.slot0, Sb, Sb, np,
                               hipMemcpyDeviceToDevice, ast));
       }
       RCHK(hipEventRecord(L.acc_ev[rg], ast));
@@ -1261,9 +1202,9 @@ int render_device(srr_renderer* r, const srr_params* p, const int32_t* pix, int6
   }
   const int64_t acc_total = r->acc_samples + p->spp;
   if (p->flags & SRR_FLAG_SUMS)
-    RCHK(hipMemcpyAsync(d_mean, r->acc, 3 * (size_t)npix * sizeof(float), hipMemcpyDeviceToDevice, ast));
+    RCHK(hipMemcpyAsync(d_mean, r->acc.get(), 3 * (size_t)npix * sizeof(float), hipMemcpyDeviceToDevice, ast));
   else
-    launch_finish(r->acc, d_mean, npix, (int)acc_total, ast);
+    launch_finish(r->acc.get(), d_mean, npix, (int)acc_total, ast);
   RCHK(hipEventRecord(r->ev_end, ast));
   RCHK(hipStreamSynchronize(ast));
   RCHK(hipGetLastError());
@@ -1298,70 +1239,23 @@ int render_device(srr_renderer* r, const srr_params* p, const int32_t* pix, int6
 }
 
 // ---- first-hit AOVs
-void free_aov(AovState& A) {
-  for (void* b : A.bufs) (void)hipFree(b);
-  A.bufs.clear();
-  (void)hipFree(A.acc);
-  (void)hipFree(A.pixels);
-  (void)hipFree(A.sobol);
-  if (A.st) (void)hipStreamDestroy(A.st);
-  A = AovState{};
-}
-
-template <class T>
-static hipError_t aov_alloc(AovState& A, T** p, size_t n) {
-  const hipError_t e = hipMalloc((void**)p, std::max<size_t>(n * sizeof(T), 16));
-  if (e == hipSuccess) A.bufs.push_back(*p);
-  return e;
-}
-
 // Per path in flight: PathState's depth-0 members (rays 32 B, RNG 16 B, depth 4 B, spec
 // 8 B, hit record 48 B), the active list (4 B), the family lists (16 B) and the values
 // (32 B): 160 B, 160 MiB at the default batch of 2^20 paths.
-static int ensure_aov(AovState& A, size_t n, size_t pix_chunk, size_t npix, int n_sobol, std::string& err) {
+static int ensure_aov(AovState& A, size_t n, size_t npix, int n_sobol, std::string& err) {
   if (!A.st) RCHK(hipStreamCreateWithFlags(&A.st, hipStreamNonBlocking));
   if (n > A.cap) {
-    for (void* b : A.bufs) (void)hipFree(b);
     A.bufs.clear();
     A.cap = 0;
-    PathState& P = A.P;
-    P = PathState{};
-    RCHK(aov_alloc(A, &P.ray_o, n));
-    RCHK(aov_alloc(A, &P.ray_d, n));
-    RCHK(aov_alloc(A, &P.lcg, n));
-    RCHK(aov_alloc(A, &P.pcg, n));
-    RCHK(aov_alloc(A, &P.depth, n));
-    RCHK(aov_alloc(A, &P.spec, n));
-    RCHK(aov_alloc(A, &P.hit_w, n));
-    RCHK(aov_alloc(A, &P.hit_p, n));
-    RCHK(aov_alloc(A, &P.hit_n, n));
-    RCHK(aov_alloc(A, &A.active, n));
-    RCHK(aov_alloc(A, &A.lists, 4 * n));
-    RCHK(aov_alloc(A, &A.cnt, 8));
-    RCHK(aov_alloc(A, &A.val, 2 * n));
+    RMEM(alloc_depth0(A.bufs, A.P, n), "AOV path state");
+    RMEM(A.bufs.add(&A.active, n), "AOV active list");
+    RMEM(A.bufs.add(&A.lists, 4 * n), "AOV family lists");
+    RMEM(A.bufs.add(&A.cnt, 8), "AOV counters");
+    RMEM(A.bufs.add(&A.val, 2 * n), "AOV values");
     A.cap = n;
   }
-  if (npix > A.pix_cap) {
-    (void)hipFree(A.pixels);
-    (void)hipFree(A.acc);
-    A.pixels = nullptr;
-    A.acc = nullptr;
-    A.pix_cap = 0;
-    RCHK(hipMalloc((void**)&A.pixels, npix * sizeof(int32_t)));
-    RCHK(hipMalloc((void**)&A.acc, 8 * npix * sizeof(float)));
-    A.pix_cap = npix;
-  }
-  (void)pix_chunk;
-  if (n_sobol > A.sobol_n) {
-    (void)hipFree(A.sobol);
-    A.sobol = nullptr;
-    A.sobol_n = 0;
-    RCHK(hipMalloc((void**)&A.sobol, 2 * (size_t)n_sobol * sizeof(double)));
-    std::vector<double> sp(2 * (size_t)n_sobol);
-    sobol2((unsigned)n_sobol, sp.data());
-    RCHK(hipMemcpy(A.sobol, sp.data(), sp.size() * sizeof(double), hipMemcpyHostToDevice));
-    A.sobol_n = n_sobol;
-  }
+  RMEM(grow_pair(A.pixels, npix, A.acc, 8 * npix), "AOV pixel list and sums");
+  RMEM(ensure_sobol(A.sobol, A.sobol_n, n_sobol), "AOV Sobol points");
   return 0;
 }
 
@@ -1380,10 +1274,10 @@ int render_aov(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t
   }
   AovState& A = r->aov;
   {  // every allocation comes before the first launch
-    const int rc = ensure_aov(A, (size_t)region, (size_t)pix_chunk, (size_t)npix, p->sample_begin + p->spp, err);
+    const int rc = ensure_aov(A, (size_t)region, (size_t)npix, p->sample_begin + p->spp, err);
     if (rc < 0) return rc;
   }
-  RCHK(hipMemcpyAsync(A.pixels, pix, npix * sizeof(int32_t), hipMemcpyHostToDevice, A.st));
+  RCHK(hipMemcpyAsync(A.pixels.get(), pix, npix * sizeof(int32_t), hipMemcpyHostToDevice, A.st));
   for (int64_t p0 = 0; p0 < npix; p0 += pix_chunk) {
     const int np = (int)std::min<int64_t>(pix_chunk, npix - p0);
     for (int s0 = 0; s0 < p->spp; s0 += S) {
@@ -1392,8 +1286,8 @@ int render_aov(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t
       B.count = A.cnt;
       B.act0 = 0;
       B.slot0 = 0;
-      B.pixels = A.pixels;
-      B.sobol = A.sobol + 2 * (size_t)p->sample_begin;
+      B.pixels = A.pixels.get();
+      B.sobol = A.sobol.get() + 2 * (size_t)p->sample_begin;
       B.s_base = p->sample_begin;
       B.p0 = (int)p0;
       B.spp_batch = std::min(S, p->spp - s0);
@@ -1411,7 +1305,7 @@ int render_aov(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t
       F.val = (const float*)A.val;
       F.np = np;
       F.spp_b = B.spp_batch;
-      F.acc = A.acc;
+      F.acc = A.acc.get();
       F.init = s0 == 0;
       F.finish = s0 + B.spp_batch == p->spp;
       F.ns = p->spp;
@@ -1436,19 +1330,13 @@ srr_renderer::~srr_renderer() {
   }
   (void)hipSetDevice(device);
   (void)hipDeviceSynchronize();
-  for (void* p : scene_bufs) (void)hipFree(p);
-  if (visits) (void)hipFree(visits);
-  srr::slot_free(sync_slot);
-  for (auto& F : async_slots) srr::slot_free(F);
+  // events and streams; every buffer belongs to a member, and members go after this body,
+  // with the device still synchronised
+  srr::slot_destroy(sync_slot);
+  for (auto& F : async_slots) srr::slot_destroy(F);
   if (ev_async_in) (void)hipEventDestroy(ev_async_in);
-  (void)hipFree(pw_wave_times);
-  (void)hipFree(pw_slow);
-  srr::free_adaptive(adaptive);
-  srr::free_aov(aov);
+  if (aov.st) (void)hipStreamDestroy(aov.st);
   for (auto& L : lanes) {
-    srr::free_lane_paths(L);
-    (void)hipFree(L.cnt);
-    if (L.rb) (void)hipHostFree(L.rb);
     for (hipEvent_t e : {L.ev_t0, L.ev_t1, L.ev_s1, L.ev_rb})
       if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < srr::kRegionsPerLane; ++k) {
@@ -1457,11 +1345,6 @@ srr_renderer::~srr_renderer() {
     }
     if (L.st) (void)hipStreamDestroy(L.st);
   }
-  (void)hipFree(acc);
-  (void)hipFree(pixels);
-  (void)hipFree(sobol);
-  (void)hipFree(raw_all);
-  (void)hipFree(rays_all);
   if (ev_beg) (void)hipEventDestroy(ev_beg);
   if (ev_end) (void)hipEventDestroy(ev_end);
   if (acc_st) (void)hipStreamDestroy(acc_st);

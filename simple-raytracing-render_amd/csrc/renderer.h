@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/srr_capi.h"
+#include "devmem.h"
 #include "kernels.h"
 #include "scene.h"
 
@@ -30,15 +31,16 @@ struct Lane {
   hipEvent_t done_ev[kRegionsPerLane] = {};  // batch in region finished (lane stream)
   hipEvent_t acc_ev[kRegionsPerLane] = {};   // batch in region accumulated (acc stream)
   bool acc_pending[kRegionsPerLane] = {};    // region reuse must wait for acc_ev
+  // the path pool (renderer.cpp ensure_lane): P, act and lists point into `bufs`
   PathState P{};
   int32_t* act[2] = {nullptr, nullptr};
   int32_t* lists = nullptr;  // 4 material-family lists
-  int32_t* cnt = nullptr;    // [0..1] active counts, [2..2+R) region survivors, [2+R..6+R) families
-  int32_t* rb = nullptr;     // pinned host mirror of region survivors + next count
-  size_t cap = 0;
+  DeviceBag bufs;
+  size_t cap = 0;            // paths the pool holds (0: none)
   int cap_depth = 0;
   bool has_raw = false;
-  std::vector<void*> bufs;
+  DeviceMem<int32_t> cnt;  // [0..1] active counts, [2..2+R) region survivors, [2+R..6+R) families
+  PinnedMem<int32_t> rb;   // host mirror of region survivors + next count
   // per-frame state
   int n = 0, cur = 0;
   bool pending = false;
@@ -54,17 +56,14 @@ struct FrameSlot {
   bool own_stream = false;
   hipEvent_t ev_beg = nullptr, ev_end = nullptr;
   std::vector<hipEvent_t> win_ev;  // per sample window: k_paths start / end
-  float4* rec = nullptr;
-  size_t rec_cap = 0;
+  DeviceMem<float4> rec;
   // [kPathsGlobalStack][pw_lanes] int2 (kernels.h), then [3][pw_lanes] float4 of suspended
   // mesh walks (kernels.h PathWork::walk_q)
-  int2* gstack = nullptr;
-  float* sample = nullptr;
-  size_t sample_cap = 0;
-  unsigned long long* ctr = nullptr;       // [0] world rays, [1] path cursor, ...
-  unsigned long long* ctr_host = nullptr;  // pinned mirror, read after the frame's stream sync
-  float* acc = nullptr;                    // async slots: the frame's own per-pixel sums
-  size_t acc_cap = 0;
+  DeviceMem<int2> gstack;                   // allocated once and kept
+  DeviceMem<float> sample;                  // the sample window: [paths][3]
+  DeviceMem<unsigned long long> ctr;        // [0] world rays, [1] path cursor, ...
+  PinnedMem<unsigned long long> ctr_host;   // mirror, read after the frame's stream sync
+  DeviceMem<float> acc;                     // async slots: the frame's own per-pixel sums [pixels][3]
   // a frame in flight (async slots)
   bool busy = false;
   int64_t ticket = -1, npix = 0, paths = 0;
@@ -73,7 +72,6 @@ struct FrameSlot {
   srr_stats stats{};
   std::string err;
 };
-void slot_free(FrameSlot& F);
 
 struct DoneTicket {  // an async frame finished before its srr_render_wait
   int64_t ticket;
@@ -85,33 +83,31 @@ struct DoneTicket {  // an async frame finished before its srr_render_wait
 // Per-slot state and active lists of srr_render_adaptive (renderer.cpp render_adaptive);
 // a slot is a position in the shard's pixel list.  The rgb sums are srr_renderer::acc.
 struct AdaptiveState {
-  size_t cap = 0;               // slots the buffers hold
-  float2* mom = nullptr;        // [slot] luminance moments (s1, s2)
-  int32_t* slot[2] = {};        // active slots, ping-pong over the compactions
-  int32_t* pixel[2] = {};       // their image pixels (PathWork::pixels)
-  uint8_t* keep = nullptr;      // [active row] survives the pass
-  int32_t* blk = nullptr;       // compaction scratch: per-block counts / offsets, then [nb] the new active count
-  int32_t* n_host = nullptr;    // pinned mirror of the new active count
+  size_t cap = 0;               // slots the buffers hold (0: none)
+  DeviceMem<float2> mom;        // [slot] luminance moments (s1, s2)
+  DeviceMem<int32_t> slot[2];   // active slots, ping-pong over the compactions
+  DeviceMem<int32_t> pixel[2];  // their image pixels (PathWork::pixels)
+  DeviceMem<uint8_t> keep;      // [active row] survives the pass
+  DeviceMem<int32_t> blk;       // compaction scratch: per-block counts / offsets, then [nb] the new active count
+  PinnedMem<int32_t> n_host;    // mirror of the new active count
 };
 
 // Buffers of srr_render_aov (renderer.cpp render_aov): a stream, a pixel list, Sobol
 // points and depth-0 path state of its own, so the call leaves the frame state alone.
 struct AovState {
   hipStream_t st = nullptr;
-  size_t cap = 0;       // paths the batch buffers hold
-  size_t pix_cap = 0;   // pixels the list and the sums hold
+  size_t cap = 0;       // paths the batch buffers hold (0: none)
   PathState P{};        // depth-0 state only: rays, RNG, depth, spec, hit record
   int32_t* active = nullptr;
   int32_t* lists = nullptr;  // launch_trace's 4 material-family lists [4][cap]
   int32_t* cnt = nullptr;    // [0] active count, [1..4] family counts, [5] fetch
   float4* val = nullptr;     // [cap][2] per-path values
-  float* acc = nullptr;      // [pixels of a chunk][8]
-  int32_t* pixels = nullptr;
-  double* sobol = nullptr;
+  DeviceBag bufs;            // the batch buffers: what P, active, lists, cnt and val point to
+  DeviceMem<int32_t> pixels;
+  DeviceMem<float> acc;      // [pixels][8], sized with the list
+  DeviceMem<double> sobol;
   int sobol_n = 0;
-  std::vector<void*> bufs;   // the batch buffers
 };
-void free_aov(AovState& A);
 
 struct Multi;  // multi.h
 }  // namespace srr
@@ -122,19 +118,19 @@ struct srr_renderer {
   // their own renderers (multi.cpp); its single-device state below stays unused
   srr::Multi* multi = nullptr;
   srr::SceneView view{};
-  std::vector<void*> scene_bufs;
+  srr::DeviceBag scene_bufs;  // what `view` points to
   int n_lanes = 2;
   srr::Lane lanes[srr::kMaxLanes];
   hipStream_t acc_st = nullptr;
   hipEvent_t ev_beg = nullptr, ev_end = nullptr;
   // frame buffers
-  float* acc = nullptr;
+  srr::DeviceMem<float> acc;  // [pixels][3], sized with the pixel list
   int64_t acc_npix = 0;     // pixels the running sums cover (SRR_FLAG_CONTINUE)
   int64_t acc_samples = 0;  // samples per pixel accumulated in them
   // the frame and shard the running sums belong to: {nx, ny, shard_index,
   // shard_count, tile}; all -1 after srr_accum_set (only npix is known then)
   int acc_key[5] = {-1, -1, -1, -1, -1};
-  unsigned long long* visits = nullptr;  // SRR_FLAG_COUNT_VISITS counters (3)
+  srr::DeviceMem<unsigned long long> visits;  // SRR_FLAG_COUNT_VISITS counters
   // path-resident engine (render_paths)
   int pw_lanes = 0;
   bool diffuse_only = false;  // no beckmann / specular materials: lean kernel variant
@@ -148,10 +144,9 @@ struct srr_renderer {
   // renderers sharing this device under one multi-device handle (multi.cpp): each takes
   // 1/window_share of the sample-window budget (SRR_WINDOW_MB)
   int window_share = 1;
-  unsigned long long* pw_wave_times = nullptr;  // SRR_WAVE_TIMES diagnostics, 4 words per wave
-  float* pw_slow = nullptr;  // diagnostics build (-DSRR_SLOW_RAYS): slow world-hit records + count
-  int32_t* pixels = nullptr;
-  size_t pix_cap = 0;
+  srr::DeviceMem<unsigned long long> pw_wave_times;  // SRR_WAVE_TIMES diagnostics, 4 words per wave
+  srr::DeviceMem<float> pw_slow;  // diagnostics build (-DSRR_SLOW_RAYS): slow world-hit records + count
+  srr::DeviceMem<int32_t> pixels;
   // the shard whose pixel list (srr_shard_pixels) the renderer holds: {nx, ny,
   // shard_index, shard_count, tile}, its pixel count, and whether it is the
   // identity (then `pixels` is not read); key[0] = -1: none.  srr_render_device
@@ -159,11 +154,11 @@ struct srr_renderer {
   int pix_key[5] = {-1, -1, -1, -1, -1};
   int64_t pix_n = 0;
   bool pix_identity = false;
-  double* sobol = nullptr;
+  srr::DeviceMem<double> sobol;
   int sobol_n = 0;
-  float* raw_all = nullptr;
-  uint8_t* rays_all = nullptr;
-  size_t keep_cap = 0;
+  // SRR_FLAG_KEEP_PATHS: [path][3] radiance and [path] ray counts, both or neither (renderer.cpp ensure_kept)
+  srr::DeviceMem<float> raw_all;
+  srr::DeviceMem<uint8_t> rays_all;
   int64_t kept_paths = 0;
   srr::AdaptiveState adaptive;
   srr::AovState aov;
@@ -187,6 +182,10 @@ int render_adaptive(srr_renderer* r, const srr_params* p, const srr_adaptive_par
 // a nullptr buffer is not asked for
 int render_aov(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t npix, float* d_albedo,
                float* d_normal, float* d_depth, std::string& err);
+// The pixel list and the running sums hold npix pixels (contents not preserved).  Growing
+// replaces both buffers, and the held list (pix_key) and the running sums' bookkeeping
+// (acc_npix, acc_samples, acc_key) are forgotten with them; on failure both are empty.
+hipError_t ensure_pixels(srr_renderer* r, int64_t npix);
 int render_wait(srr_renderer* r, int64_t ticket, srr_stats* stats, std::string& err);
 void drain_async(srr_renderer* r);  // finish every async frame in flight (results kept for render_wait)
 // the event recorded after async frame `ticket`'s last operation (its slot's frame end),
