@@ -36,6 +36,13 @@
  *                                frame with srr_denoise (its defaults) over the
  *                                first-hit AOVs of srr_render_aov; --out is then
  *                                the tone-mapped denoised frame
+ *   --denoise-var                the same with srr_denoise_var (its defaults), guided
+ *                                by the variance of every pixel's mean luminance
+ *                                (srr_adaptive_variance); not with --denoise.  With
+ *                                --adaptive the variance is that frame's; without,
+ *                                the frame is rendered by srr_render_adaptive with
+ *                                rel_tol 0 and batch_spp = min_spp = ns: one pass,
+ *                                bitwise the fixed-spp frame
  *   --aov-spp N                  samples of the AOVs (default min(ns, 16))
  *   --aov-out PREFIX             write PREFIX_albedo.png (255.99 * albedo, clamped),
  *                                PREFIX_normal.png (255.99 * (n / 2 + 1/2)) and
@@ -77,14 +84,14 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
   double adaptive = -1;  // --adaptive REL_TOL (< 0: fixed spp)
   int batch_spp = 16, min_spp = 16;
   std::string count_map;
-  bool denoise = false;
+  bool denoise = false, denoise_var = false;
   int aov_spp = 0;  // 0: min(ns, 16)
   std::string aov_out;
   auto usage = [&]() {
     std::fprintf(stderr, "usage: %s [--sceneid N | --scene NAME] [--nx N] [--ny N] [--ns N] [--max-depth N] "
                          "[--device N] [--gpus N | --devices a,b,..] [--tile N] [--out FILE] [--dry-run] "
                          "[--adaptive REL_TOL [--batch-spp N] [--min-spp N] [--count-map FILE]] "
-                         "[--denoise] [--aov-spp N] [--aov-out PREFIX]\nscenes:",
+                         "[--denoise | --denoise-var] [--aov-spp N] [--aov-out PREFIX]\nscenes:",
                  argv[0]);
     for (int k = 0; k < n_scenes; ++k) std::fprintf(stderr, " %d:%s", scenes[k].sceneid, scenes[k].name);
     std::fprintf(stderr, "\n");
@@ -120,6 +127,7 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
     else if (a == "--min-spp") ok = num(min_spp) && min_spp >= 1;
     else if (a == "--count-map" && i + 1 < argc) count_map = argv[++i];
     else if (a == "--denoise") denoise = true;
+    else if (a == "--denoise-var") denoise_var = true;
     else if (a == "--aov-spp") ok = num(aov_spp) && aov_spp >= 1;
     else if (a == "--aov-out" && i + 1 < argc) aov_out = argv[++i];
     else ok = false;
@@ -130,7 +138,8 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
     if (name.empty() ? scenes[k].sceneid == sceneid : name == scenes[k].name) e = &scenes[k];
   if ((!e && text_path.empty()) || nx < 1 || ny < 1 || ns < 1) return usage();
   if (adaptive < 0 && !count_map.empty()) return usage();
-  if ((denoise || !aov_out.empty()) && (gpus > 1 || !devices.empty())) return usage();  // one GPU
+  if (denoise && denoise_var) return usage();
+  if ((denoise || denoise_var || !aov_out.empty()) && (gpus > 1 || !devices.empty())) return usage();  // one GPU
   if (aov_spp == 0) aov_spp = ns < 16 ? ns : 16;
   const char* scene_name = text_path.empty() ? e->name : text_path.c_str();
 
@@ -190,19 +199,20 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
   p.shard_count = 1;
   const size_t npix = (size_t)nx * ny;
   std::vector<unsigned char> rgb8(3 * npix);
-  const bool want_aov = denoise || !aov_out.empty();
+  const bool want_aov = denoise || denoise_var || !aov_out.empty();
   std::vector<float> mean(want_aov ? 3 * npix : 0);
   srr_stats st{};
   const auto t0 = std::chrono::steady_clock::now();
   int rc;
   srr_adaptive_stats ast{};
   std::vector<int32_t> count;
-  if (adaptive >= 0) {
+  if (adaptive >= 0 || denoise_var) {
+    // (--denoise-var without --adaptive: the fixed-spp frame as one adaptive pass, which keeps its moments)
     srr_adaptive_params ap{};
     ap.struct_size = sizeof ap;
-    ap.batch_spp = batch_spp;
-    ap.min_spp = min_spp;
-    ap.rel_tol = (float)adaptive;
+    ap.batch_spp = adaptive >= 0 ? batch_spp : ns;
+    ap.min_spp = adaptive >= 0 ? min_spp : ns;
+    ap.rel_tol = adaptive >= 0 ? (float)adaptive : 0.f;
     ap.abs_eps = 1e-3f;
     ast.struct_size = sizeof ast;
     count.resize((size_t)nx * ny);
@@ -220,6 +230,16 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
     pa.spp = aov_spp;
     rc = srr_render_aov_host(r, &pa, SRR_AOV_ALBEDO | SRR_AOV_NORMAL | SRR_AOV_DEPTH, albedo.data(), normal.data(),
                              depth.data());
+  }
+  if (rc == 0 && denoise_var) {
+    srr_denoise_var_params dp{};
+    std::vector<float> var(npix), den(3 * npix);
+    rc = srr_adaptive_variance_host(r, count.data(), var.data());
+    if (rc == 0) rc = srr_denoise_var_defaults(&dp);
+    if (rc == 0)
+      rc = srr_denoise_var_host(devices[0], nx, ny, &dp, mean.data(), var.data(), albedo.data(), normal.data(),
+                                depth.data(), den.data(), nullptr);
+    if (rc == 0) rc = srr_tonemap(den.data(), (int64_t)npix, rgb8.data());
   }
   if (rc == 0 && denoise) {
     srr_denoise_params dp{};

@@ -314,6 +314,37 @@ int srr_render_adaptive_host(srr_renderer* r, const srr_params* p, const srr_ada
 /* The convergence rule above on the host (no GPU): 1 converged, 0 not. */
 int srr_adaptive_converged(int32_t n, float s1, float s2, float rel_tol, float abs_eps);
 
+/* ---- Variance of a pixel's mean luminance, from the moments (s1, s2) that the
+ * adaptive frame keeps for the rule above, for a pixel that holds n samples.  Every
+ * operation in float32, in exactly this order, without fused multiply-add; rdiv is
+ * IEEE division.  With nf = (float)n:
+ *   n < 2:     v = s1*s1
+ *   otherwise: d = s2*nf - s1*s1;  if !(d > 0) then d = 0  (this also catches NaN);
+ *              v = rdiv(d, (nf*nf) * (nf - 1.0f))
+ * Origin, as for the convergence rule: var(mean) = (s2 - s1*s1/n) / (n (n - 1)), the
+ * unbiased sample variance over n, multiplied through by n so that one division is
+ * left.  n < 2 has no sample variance: a one-sample pixel gets the prior of 100 %
+ * relative error, v = mean^2 = s1*s1.
+ * srr_variance_of_mean evaluates it on the host (no GPU) by the code the kernel runs.
+ *
+ * srr_adaptive_variance reads the moments left by the most recent SUCCESSFUL
+ * srr_render_adaptive on this renderer (npix = that frame's shard pixel count) and
+ * d_count[i], that frame's counts (DEVICE pointer, npix int32: what the frame wrote
+ * to its d_count), and writes d_var[i] (DEVICE pointer, npix floats), both in
+ * srr_shard_pixels() order.  One small kernel on the renderer's synchronous stream;
+ * the call returns after it.  SRR_EINVAL, before anything is enqueued, for a NULL
+ * argument, a multi-device renderer, and a renderer that holds no valid adaptive
+ * frame (none rendered yet, or the most recent one failed after it had started).  No
+ * other render entry touches the moments: srr_render_device, srr_render_aov and the
+ * async frames may run in between.
+ * A fixed-spp frame with variance is srr_render_adaptive with rel_tol = 0 and
+ * batch_spp = min_spp = spp: one pass, whose image and world rays are bitwise those
+ * of srr_render_device at that spp. */
+float srr_variance_of_mean(int32_t n, float s1, float s2);
+int srr_adaptive_variance(srr_renderer* r, const int32_t* d_count, float* d_var);
+/* The same with host buffers. */
+int srr_adaptive_variance_host(srr_renderer* r, const int32_t* count, float* var);
+
 /* ---- First-hit feature buffers (AOVs) for a denoiser (no reference counterpart).
  * For every shard pixel and every sample of [p->sample_begin, p->sample_begin +
  * p->spp) the PRIMARY ray of the beauty frame is traced (the same per-path seed,
@@ -389,6 +420,61 @@ int srr_denoise(int device, int nx, int ny, const srr_denoise_params* dp, const 
 /* The same with host buffers. */
 int srr_denoise_host(int device, int nx, int ny, const srr_denoise_params* dp, const float* color,
                      const float* albedo, const float* normal, const float* depth, float* out);
+
+/* ---- Variance-guided denoiser: the a-trous filter above with the colour term of
+ * Schied, Kaplanyan, Wyman et al. 2017 (SVGF), section 4.4: the luminance tolerance of
+ * a pixel is the standard deviation of its own estimate, and the variance is carried
+ * through the iterations.  Nothing of it is the reference's.  Images as for
+ * srr_denoise; d_var and d_var_out hold nx*ny floats, the variance of each pixel's
+ * mean luminance (srr_adaptive_variance, scattered into PPM order) and that of the
+ * filtered pixel; d_var_out may be NULL.  d_out and d_var_out must overlap neither
+ * an input nor each other.
+ *
+ * Definition: every operation in float32, in exactly this order, without fused
+ * multiply-add; rdiv and rexp as in srr_denoise, rsqrt the correctly rounded square
+ * root; lum(x) = (0.2126f*x.r + 0.7152f*x.g) + 0.0722f*x.b.
+ *   Set-up.  Without SRR_DENOISE_DEMODULATE x = c and v = var.  With it, per channel
+ *     m.ch = a.ch + 1e-3f, x.ch = rdiv(c.ch, m.ch);  la = lum(m);  v = rdiv(var, la*la).
+ *   Iteration k = 0 .. iterations-1, s = 1 << k.  For pixel p:
+ *     Variance prefilter, always over the ADJACENT pixels (not the dilated ones): taps
+ *       (dy, dx), dy = -1..1 outer, dx = -1..1 inner, a tap outside the image skipped;
+ *       G = {0.25f centre, 0.125f edge, 0.0625f corner};  gs += G*vq;  gw += G
+ *       (both start at 0);  vbar = rdiv(gs, gw).
+ *     den = k_l * rsqrt(vbar) + 1e-6f;  lp = lum(xp).
+ *     Wavelet taps exactly as in srr_denoise: dy = -2..2 outer, dx inner,
+ *       q = p + s*(dx, dy), a tap outside the image skipped, h = B[|dx|]*B[|dy|].
+ *       dl = fabsf(lum(xq) - lp);  wl = rdiv(dl, den)
+ *       dn, dz as in srr_denoise
+ *       w  = h * rexp(-((wl + dn*k_n) + dz*k_z))
+ *       sum.ch += w*xq.ch;  wsum += w;  vsum += (w*w)*vq      (all start at 0)
+ *     x'p.ch = rdiv(sum.ch, wsum);  v'p = rdiv(vsum, wsum*wsum)
+ *       (the centre tap makes wsum >= 9/64)
+ *   Output.  out = x, or x.ch * m.ch with SRR_DENOISE_DEMODULATE;
+ *            var_out = v, or v * (la*la) with it.
+ * (k_l = 0 leaves den = 1e-6f: pixels then average only with neighbours of their own
+ * luminance.  A large k_l, not 0, switches the luminance term off.)
+ * tests/denoise_var_ref.py restates this in numpy, bit for bit.
+ * SRR_EINVAL, before the GPU is touched, for the sizes srr_denoise refuses, iterations
+ * outside 1..6, a negative or non-finite k_l / k_n / k_z, unknown flags, a struct_size
+ * smaller than the struct below, a NULL buffer other than d_var_out, and an output
+ * that overlaps an input or the other output. */
+typedef struct srr_denoise_var_params {
+  uint32_t struct_size; /* sizeof(srr_denoise_var_params) of the caller */
+  int iterations;       /* 1..6 */
+  float k_l, k_n, k_z;  /* luminance tolerance in standard deviations; normal, depth strengths: >= 0, finite */
+  int flags;            /* SRR_DENOISE_DEMODULATE */
+} srr_denoise_var_params;
+/* The defaults (the sweep of DESIGN.md §4.3): struct_size, 3 iterations, k_l 2, k_n 128,
+ * k_z 64, SRR_DENOISE_DEMODULATE (the plain filter scores better on the 16-spp frame of
+ * the sweep's scene and smears a light that is in view: see there). */
+int srr_denoise_var_defaults(srr_denoise_var_params* dp);
+int srr_denoise_var(int device, int nx, int ny, const srr_denoise_var_params* dp, const float* d_color,
+                    const float* d_var, const float* d_albedo, const float* d_normal, const float* d_depth,
+                    float* d_out, float* d_var_out);
+/* The same with host buffers. */
+int srr_denoise_var_host(int device, int nx, int ny, const srr_denoise_var_params* dp, const float* color,
+                         const float* var, const float* albedo, const float* normal, const float* depth, float* out,
+                         float* var_out);
 
 /* Progressive rendering with resume: the renderer's per-pixel running sums
  * (3 floats per shard pixel, in srr_shard_pixels order) and the samples per pixel

@@ -17,6 +17,7 @@
 
 #include "capi_internal.h"
 #include "denoise.h"
+#include "denoise_var.h"
 #include "imageio.h"
 #include "meshio.h"
 #include "../../include/srr/merl.h"
@@ -543,6 +544,42 @@ int srr_adaptive_converged(int32_t n, float s1, float s2, float rel_tol, float a
   return adaptive_converged_host(n, s1, s2, rel_tol, abs_eps);
 }
 
+float srr_variance_of_mean(int32_t n, float s1, float s2) { return variance_of_mean_host(n, s1, s2); }
+
+static int adaptive_variance_check(const srr_renderer* r, const void* count, const void* var) {
+  if (!r || !count || !var) return fail(SRR_EINVAL, "null argument");
+  if (r->multi) return fail(SRR_EINVAL, "srr_adaptive_variance: one-device renderers only");
+  if (r->adaptive.valid_npix <= 0)
+    return fail(SRR_EINVAL, "srr_adaptive_variance: the renderer holds no adaptive frame's moments (the most recent "
+                            "srr_render_adaptive must have succeeded)");
+  return 0;
+}
+
+int srr_adaptive_variance(srr_renderer* r, const int32_t* d_count, float* d_var) {
+  // every refusal comes before anything is enqueued
+  if (const int rc = adaptive_variance_check(r, d_count, d_var)) return rc;
+  std::string err;
+  const int rc = adaptive_variance(r, d_count, d_var, err);
+  return rc < 0 ? fail(rc, err) : 0;
+}
+
+int srr_adaptive_variance_host(srr_renderer* r, const int32_t* count, float* var) {
+  if (const int rc = adaptive_variance_check(r, count, var)) return rc;
+  const size_t npix = (size_t)r->adaptive.valid_npix;
+  DeviceMem<int32_t> dc;
+  DeviceMem<float> dv;
+  HIPCHK(hipSetDevice(r->device));
+  MEMCHK(dc.grow(at_least_16_bytes<int32_t>(npix)), SRR_ENOMEM, "adaptive count buffer");
+  MEMCHK(dv.grow(at_least_16_bytes<float>(npix)), SRR_ENOMEM, "adaptive variance buffer");
+  hipError_t e = hipMemcpy(dc.get(), count, npix * sizeof(int32_t), hipMemcpyHostToDevice);
+  int rc = e == hipSuccess ? srr_adaptive_variance(r, dc.get(), dv.get()) : fail(SRR_EIO, hipGetErrorString(e));
+  if (rc == 0) {
+    e = hipMemcpy(var, dv.get(), npix * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(SRR_EIO, hipGetErrorString(e));
+  }
+  return rc;
+}
+
 // ---- first-hit AOVs
 static int aov_check(const srr_renderer* r, const srr_params* p, int which, const void* a, const void* n,
                      const void* z) {
@@ -700,6 +737,119 @@ int srr_denoise_host(int device, int nx, int ny, const srr_denoise_params* dp, c
   int rc = e == hipSuccess ? srr_denoise(device, nx, ny, dp, dc, da, dn, dz, dout) : fail(SRR_EIO, hipGetErrorString(e));
   if (rc == 0) {
     e = hipMemcpy(out, dout, 3 * n * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(SRR_EIO, hipGetErrorString(e));
+  }
+  return rc;
+}
+
+// ---- the variance-guided a-trous filter (denoise_var.hip)
+static int denoise_var_check(int device, int nx, int ny, const srr_denoise_var_params* dp, const float* color,
+                             const float* var, const float* albedo, const float* normal, const float* depth,
+                             const float* out, const float* var_out) {
+  if (!dp) return fail(SRR_EINVAL, "srr_denoise_var: null params");
+  if (dp->struct_size < sizeof(srr_denoise_var_params))
+    return fail(SRR_EINVAL, "srr_denoise_var_params.struct_size " + std::to_string(dp->struct_size) +
+                                " is smaller than the " + std::to_string(sizeof(srr_denoise_var_params)) +
+                                " bytes this library reads");
+  if (device < 0) return fail(SRR_EINVAL, "srr_denoise_var: bad device");
+  if (nx < 1 || ny < 1 || nx > 65536 || ny > 65536 || (int64_t)nx * ny > ((int64_t)1 << 28))
+    return fail(SRR_EINVAL, "srr_denoise_var: 1 <= nx, ny <= 65536 and nx*ny <= 2^28");
+  if (dp->iterations < 1 || dp->iterations > 6) return fail(SRR_EINVAL, "srr_denoise_var: iterations must be 1..6");
+  for (const float k : {dp->k_l, dp->k_n, dp->k_z})
+    if (!(k >= 0.f) || !(k <= 3.402823466e38f))  // (NaN fails both comparisons)
+      return fail(SRR_EINVAL, "srr_denoise_var: k_l, k_n, k_z must be finite and >= 0");
+  if (dp->flags & ~SRR_DENOISE_DEMODULATE) return fail(SRR_EINVAL, "srr_denoise_var: unknown flags");
+  if (!color || !var || !albedo || !normal || !depth || !out) return fail(SRR_EINVAL, "srr_denoise_var: null buffer");
+  const size_t n = (size_t)nx * ny * sizeof(float);
+  const std::pair<const float*, size_t> in[] = {{color, 3 * n}, {var, n}, {albedo, 3 * n}, {normal, 3 * n}, {depth, n}};
+  const std::pair<const float*, size_t> outs[] = {{out, 3 * n}, {var_out, n}};
+  auto overlap = [](const std::pair<const float*, size_t>& a, const std::pair<const float*, size_t>& b) {
+    return (uintptr_t)a.first < (uintptr_t)b.first + b.second && (uintptr_t)b.first < (uintptr_t)a.first + a.second;
+  };
+  for (const auto& o : outs) {
+    if (!o.first) continue;  // (var_out may be NULL)
+    for (const auto& b : in)
+      if (overlap(o, b)) return fail(SRR_EINVAL, "srr_denoise_var: an output overlaps an input");
+  }
+  if (var_out && overlap(outs[0], outs[1])) return fail(SRR_EINVAL, "srr_denoise_var: the outputs overlap each other");
+  return 0;
+}
+
+int srr_denoise_var_defaults(srr_denoise_var_params* dp) {
+  if (!dp) return fail(SRR_EINVAL, "null argument");
+  // chosen by the sweep of DESIGN.md §4.3 (profiles/r12/denoise_var.txt)
+  *dp = srr_denoise_var_params{(uint32_t)sizeof(srr_denoise_var_params), 3, 2.0f, 128.0f, 64.0f,
+                               SRR_DENOISE_DEMODULATE};
+  return 0;
+}
+
+int srr_denoise_var(int device, int nx, int ny, const srr_denoise_var_params* dp, const float* d_color,
+                    const float* d_var, const float* d_albedo, const float* d_normal, const float* d_depth,
+                    float* d_out, float* d_var_out) {
+  // every refusal comes before the GPU is touched
+  if (const int rc = denoise_var_check(device, nx, ny, dp, d_color, d_var, d_albedo, d_normal, d_depth, d_out, d_var_out))
+    return rc;
+  static const int variant = [] {  // SRR_DENOISE_VARIANT, as srr_denoise reads it: measurements only
+    const char* e = getenv("SRR_DENOISE_VARIANT");
+    if (e && !strcmp(e, "tile")) return (int)kDnTile;
+    if (e && !strcmp(e, "gather")) return (int)kDnGather;
+    return (int)kDnAuto;
+  }();
+  const size_t n = (size_t)nx * ny;
+  std::lock_guard<std::mutex> lock(g_dn_mu);
+  HIPCHK(hipSetDevice(device));
+  // two (colour, variance) images and the guides: the size and the role of srr_denoise's
+  // scratch, so the two filters share the device's
+  DenoiseScratch& W = g_dn_scratch[device];
+  MEMCHK(W.buf.grow(3 * n), SRR_ENOMEM, "srr_denoise_var: scratch images");
+  float4* x[2] = {W.buf.get(), W.buf.get() + n};
+  float4* guide = W.buf.get() + 2 * n;
+  const bool demod = (dp->flags & SRR_DENOISE_DEMODULATE) != 0;
+  hipStream_t st = nullptr;  // the caller's inputs were written on the legacy stream or are complete
+  launch_denoise_var_pack((int64_t)n, d_color, d_var, demod ? d_albedo : nullptr, d_normal, d_depth, x[0], guide, st);
+  for (int k = 0; k < dp->iterations; ++k) {
+    const bool last = k + 1 == dp->iterations;
+    DnvIter I{};
+    I.nx = nx;
+    I.ny = ny;
+    I.step = 1 << k;
+    I.kl = dp->k_l;
+    I.kn = dp->k_n;
+    I.kz = dp->k_z;
+    I.x_in = x[k & 1];
+    I.guide = guide;
+    I.x_out = last ? nullptr : x[(k & 1) ^ 1];
+    I.out = last ? d_out : nullptr;
+    I.var_out = last ? d_var_out : nullptr;
+    I.albedo = last && demod ? d_albedo : nullptr;
+    launch_denoise_var_iter(I, variant, st);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+int srr_denoise_var_host(int device, int nx, int ny, const srr_denoise_var_params* dp, const float* color,
+                         const float* var, const float* albedo, const float* normal, const float* depth, float* out,
+                         float* var_out) {
+  if (const int rc = denoise_var_check(device, nx, ny, dp, color, var, albedo, normal, depth, out, var_out)) return rc;
+  const size_t n = (size_t)nx * ny;
+  DeviceMem<float> buf;  // colour, albedo, normal [3n each], depth, variance [n each], outputs [3n, n]
+  HIPCHK(hipSetDevice(device));
+  MEMCHK(buf.grow(15 * n), SRR_EIO, "srr_denoise_var_host: staging images");
+  float* const d = buf.get();
+  float *dc = d, *da = d + 3 * n, *dn = d + 6 * n, *dz = d + 9 * n, *dv = d + 10 * n, *dout = d + 11 * n,
+        *dvout = d + 14 * n;
+  hipError_t e = hipMemcpy(dc, color, 3 * n * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(da, albedo, 3 * n * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dn, normal, 3 * n * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dz, depth, n * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dv, var, n * sizeof(float), hipMemcpyHostToDevice);
+  int rc = e == hipSuccess ? srr_denoise_var(device, nx, ny, dp, dc, dv, da, dn, dz, dout, var_out ? dvout : nullptr)
+                           : fail(SRR_EIO, hipGetErrorString(e));
+  if (rc == 0) {
+    e = hipMemcpy(out, dout, 3 * n * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && var_out) e = hipMemcpy(var_out, dvout, n * sizeof(float), hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = fail(SRR_EIO, hipGetErrorString(e));
   }
   return rc;

@@ -410,6 +410,10 @@ void launch_accumulate_window(const float* sample, int npix, int spp_w, float* a
 int paths_kernel_stack();  // the kernels' LDS traversal stack entries (kStack): launch_paths refuses a larger stack_cap
 // the convergence rule of include/srr_capi.h, evaluated by the code the kernel runs
 int adaptive_converged_host(int32_t n, float s1, float s2, float rel_tol, float abs_eps);
+// the variance of the mean luminance of include/srr_capi.h, by the code the kernel runs
+float variance_of_mean_host(int32_t n, float s1, float s2);
+// var[slot] = that of (count[slot], mom[slot]) for the n slots of an adaptive frame
+void launch_adaptive_variance(int n, const float2* mom, const int32_t* count, float* var, hipStream_t st);
 // One sample window of a pass: row j of `sample` ([n_active][spp_w][3]) holds the
 // window's samples of slot active_slot[j] (nullptr: slot j), a slot being a position
 // in the shard's pixel list.  The fold adds them, in sample order, to the slot's rgb

@@ -3985,6 +3985,27 @@ __host__ __device__ inline bool adaptive_converged(int n, float s1, float s2, fl
   return (s2 * nf - s1 * s1) <= ((rel_tol * rel_tol) * (nf - 1.0f)) * (m * m);
 }
 
+// The variance of the pixel's mean luminance of include/srr_capi.h, from the moments
+// the fold keeps: (s2 - s1*s1/n) / (n (n - 1)) with one division, every operation in
+// float32 in the order written.  One definition for k_adaptive_variance and
+// srr_variance_of_mean.
+__host__ __device__ inline float variance_of_mean(int n, float s1, float s2) {
+  const float nf = (float)n;
+  if (n < 2) return s1 * s1;  // one sample: a prior of 100 % relative error
+  float d = s2 * nf - s1 * s1;
+  if (!(d > 0.f)) d = 0.f;  // (also a NaN)
+  return d / ((nf * nf) * (nf - 1.0f));  // (f32 division is correctly rounded on both sides)
+}
+
+__global__ void __launch_bounds__(256) k_adaptive_variance(int n, const float2* __restrict__ mom,
+                                                           const int32_t* __restrict__ count,
+                                                           float* __restrict__ var) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float2 m = mom[i];
+  var[i] = variance_of_mean(count[i], m.x, m.y);
+}
+
 // The moments fold of one sample window of an adaptive pass (kernels.h AdaptiveFold):
 // a block stages 256 rows x 16 samples through LDS as k_accumulate_window16 does --
 // 16-byte loads when spp_w % 4 == 0 (V4; every row and chunk is then 16-byte
@@ -5169,6 +5190,13 @@ int paths_kernel_stack() { return dev::kStack; }
 
 int adaptive_converged_host(int32_t n, float s1, float s2, float rel_tol, float abs_eps) {
   return dev::adaptive_converged(n, s1, s2, rel_tol, abs_eps) ? 1 : 0;
+}
+
+float variance_of_mean_host(int32_t n, float s1, float s2) { return dev::variance_of_mean(n, s1, s2); }
+
+void launch_adaptive_variance(int n, const float2* mom, const int32_t* count, float* var, hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(dev::k_adaptive_variance, dim3((n + 255) / 256), dim3(256), 0, st, n, mom, count, var);
 }
 
 void launch_adaptive_fold(const AdaptiveFold& A, hipStream_t st) {

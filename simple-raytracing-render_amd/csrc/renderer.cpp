@@ -885,6 +885,7 @@ int render_adaptive(srr_renderer* r, const srr_params* p, const srr_adaptive_par
     err = "srr_render_adaptive: path engine only (SRR_ENGINE=wave is set)";
     return SRR_EINVAL;
   }
+  r->adaptive.valid_npix = 0;  // the moments are this frame's from here on, and valid once it succeeds
   RCHK(hipSetDevice(r->device));
   // the rgb sums of the pass loop live in the progressive accumulator: whatever it
   // held is gone, and what this frame leaves (pixels of different sample counts) is
@@ -926,7 +927,18 @@ int render_adaptive(srr_renderer* r, const srr_params* p, const srr_adaptive_par
   }
   const int rc = adaptive_passes(r, F, p, a, ps, identity, npix, win_cap, d_mean, d_count, stats, err);
   if (rc < 0) (void)hipStreamSynchronize(F.st);  // passes already enqueued must not outlive the error
+  if (rc == 0) r->adaptive.valid_npix = npix;
   return rc;
+}
+
+int adaptive_variance(srr_renderer* r, const int32_t* d_count, float* d_var, std::string& err) {
+  const AdaptiveState& A = r->adaptive;
+  RCHK(hipSetDevice(r->device));
+  hipStream_t st = r->sync_slot.st;  // the stream the frame's folds ran on
+  launch_adaptive_variance((int)A.valid_npix, A.mom.get(), d_count, d_var, st);
+  RCHK(hipGetLastError());
+  RCHK(hipStreamSynchronize(st));
+  return 0;
 }
 
 // srr_render_device_async: a fresh frame (no CONTINUE, KEEP_PATHS, COUNT_VISITS or

@@ -84,7 +84,10 @@ struct DoneTicket {  // an async frame finished before its srr_render_wait
 // a slot is a position in the shard's pixel list.  The rgb sums are srr_renderer::acc.
 struct AdaptiveState {
   size_t cap = 0;               // slots the buffers hold (0: none)
-  DeviceMem<float2> mom;        // [slot] luminance moments (s1, s2)
+  // slots whose moments the most recent successful frame left in `mom` (0: none);
+  // srr_adaptive_variance reads them
+  int64_t valid_npix = 0;
+  DeviceMem<float2> mom;       // [slot] luminance moments (s1, s2)
   DeviceMem<int32_t> slot[2];   // active slots, ping-pong over the compactions
   DeviceMem<int32_t> pixel[2];  // their image pixels (PathWork::pixels)
   DeviceMem<uint8_t> keep;      // [active row] survives the pass
@@ -178,6 +181,8 @@ int render_device_async(srr_renderer* r, const srr_params* p, const int32_t* pix
 // srr_render_adaptive on a one-device renderer, its arguments already validated (capi.cpp)
 int render_adaptive(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, const int32_t* pix,
                     int64_t npix, float* d_mean, int32_t* d_count, srr_adaptive_stats* stats, std::string& err);
+// srr_adaptive_variance on a one-device renderer that holds a valid adaptive frame (capi.cpp)
+int adaptive_variance(srr_renderer* r, const int32_t* d_count, float* d_var, std::string& err);
 // srr_render_aov on a one-device renderer, its arguments already validated (capi.cpp);
 // a nullptr buffer is not asked for
 int render_aov(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t npix, float* d_albedo,

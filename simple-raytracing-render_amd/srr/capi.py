@@ -74,6 +74,20 @@ class DenoiseParams(ctypes.Structure):
         return dp
 
 
+class DenoiseVarParams(ctypes.Structure):
+    """srr_denoise_var_params; ``DenoiseVarParams.defaults()`` is srr_denoise_var_defaults."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("iterations", ctypes.c_int), ("k_l", ctypes.c_float),
+                ("k_n", ctypes.c_float), ("k_z", ctypes.c_float), ("flags", ctypes.c_int)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "DenoiseVarParams":
+        dp = cls()
+        _check(lib().srr_denoise_var_defaults(ctypes.byref(dp)))
+        for k, v in kw.items():
+            setattr(dp, k, v)
+        return dp
+
+
 def lib():
     global _LIB
     if _LIB is None:
@@ -140,6 +154,15 @@ def lib():
             L.srr_denoise_defaults.argtypes = [dpp]
             L.srr_denoise.argtypes = [ip, ip, ip, dpp, vp, vp, vp, vp, vp]
             L.srr_denoise_host.argtypes = [ip, ip, ip, dpp, vp, vp, vp, vp, vp]
+        if hasattr(L, "srr_denoise_var"):  # (as above)
+            dvp = ctypes.POINTER(DenoiseVarParams)
+            L.srr_variance_of_mean.argtypes = [ctypes.c_int32, ctypes.c_float, ctypes.c_float]
+            L.srr_variance_of_mean.restype = ctypes.c_float
+            L.srr_adaptive_variance.argtypes = [vp, vp, vp]
+            L.srr_adaptive_variance_host.argtypes = [vp, vp, vp]
+            L.srr_denoise_var_defaults.argtypes = [dvp]
+            L.srr_denoise_var.argtypes = [ip, ip, ip, dvp, vp, vp, vp, vp, vp, vp, vp]
+            L.srr_denoise_var_host.argtypes = [ip, ip, ip, dvp, vp, vp, vp, vp, vp, vp, vp]
         _LIB = L
     return _LIB
 
@@ -313,6 +336,20 @@ class Renderer:
                                          ctypes.byref(st)))
         return st.as_dict()
 
+    def adaptive_variance(self, count) -> np.ndarray:
+        """The variance of every pixel's mean luminance (srr_adaptive_variance_host) from
+        the moments of the most recent successful render_adaptive on this renderer;
+        count: that frame's counts.  Returns var[n] in shard-pixel order."""
+        count = np.ascontiguousarray(count, np.int32).ravel()
+        var = np.zeros(count.size, np.float32)
+        _check(lib().srr_adaptive_variance_host(self.h, _ptr(count), _ptr(var)))
+        return var
+
+    def adaptive_variance_device(self, d_count_ptr: int, d_var_ptr: int) -> None:
+        """srr_adaptive_variance over device buffers (e.g. torch tensors' data_ptr())."""
+        _check(lib().srr_adaptive_variance(self.h, ctypes.c_void_p(d_count_ptr or None),
+                                           ctypes.c_void_p(d_var_ptr or None)))
+
     def render_aov(self, nx, ny, spp, which=AOV_ALBEDO | AOV_NORMAL | AOV_DEPTH, max_depth=50, **kw):
         """First-hit feature buffers (srr_render_aov_host) of the samples
         [sample_begin, sample_begin + spp): dict(albedo[n,3], normal[n,3], depth[n])
@@ -379,6 +416,35 @@ def denoise(color, albedo, normal, depth, params: DenoiseParams = None, device: 
     _check(lib().srr_denoise_host(device, nx, ny, ctypes.byref(dp), _ptr(color), _ptr(albedo), _ptr(normal),
                                   _ptr(depth), _ptr(out)))
     return out
+
+
+def variance_of_mean(n, s1, s2) -> np.float32:
+    """The variance of a pixel's mean luminance from its moments (srr_variance_of_mean; host, no GPU)."""
+    return np.float32(lib().srr_variance_of_mean(int(n), float(s1), float(s2)))
+
+
+def denoise_var(color, var, albedo, normal, depth, params: DenoiseVarParams = None, device: int = 0,
+                want_var: bool = True):
+    """The variance-guided a-trous filter (srr_denoise_var_host) over whole images in PPM
+    order: color, albedo, normal [ny, nx, 3], var, depth [ny, nx] -> (out [ny, nx, 3],
+    var_out [ny, nx]); var_out is None when want_var is false (d_var_out = NULL)."""
+    color = np.ascontiguousarray(color, np.float32)
+    if color.ndim != 3 or color.shape[2] != 3:
+        raise SrrError("denoise_var needs color[ny, nx, 3]")
+    ny, nx = color.shape[:2]
+    var = np.ascontiguousarray(var, np.float32)
+    albedo = np.ascontiguousarray(albedo, np.float32)
+    normal = np.ascontiguousarray(normal, np.float32)
+    depth = np.ascontiguousarray(depth, np.float32)
+    if albedo.size != color.size or normal.size != color.size or depth.size * 3 != color.size or \
+            var.size * 3 != color.size:
+        raise SrrError("denoise_var: albedo and normal need ny*nx*3 floats, var and depth ny*nx")
+    dp = params if params is not None else DenoiseVarParams.defaults()
+    out = np.zeros_like(color)
+    var_out = np.zeros((ny, nx), np.float32) if want_var else None
+    _check(lib().srr_denoise_var_host(device, nx, ny, ctypes.byref(dp), _ptr(color), _ptr(var), _ptr(albedo),
+                                      _ptr(normal), _ptr(depth), _ptr(out), _ptr(var_out)))
+    return out, var_out
 
 
 def tonemap(mean: np.ndarray) -> np.ndarray:

@@ -13,6 +13,11 @@ format of Raytracing_n.cpp:850-886).
                                            (srr_denoise over the first-hit AOVs of srr_render_aov; one GPU;
                                             --out is the tone-mapped denoised frame; PREFIX_albedo.png,
                                             PREFIX_normal.png, PREFIX_depth.png)
+                              [--denoise-var [--aov-spp N] [--aov-out PREFIX]]
+                                           (the same with srr_denoise_var, guided by the variance of every
+                                            pixel's mean luminance; not with --denoise; without --adaptive the
+                                            frame is one srr_render_adaptive pass at rel_tol 0, bitwise the
+                                            fixed-spp frame)
 
 Defaults are the reference's globals (Raytracing_n.cpp:39-43).  Differences, all
 forced by the reference: its 8 render threads race on shared state
@@ -53,6 +58,8 @@ def parse(argv=None):
                     help="adaptive: PNG of the samples each pixel took, as grey level count / ns")
     ap.add_argument("--denoise", action="store_true",
                     help="filter the frame with the a-trous denoiser over its first-hit AOVs (one GPU)")
+    ap.add_argument("--denoise-var", action="store_true",
+                    help="filter the frame with the variance-guided a-trous denoiser (one GPU; not with --denoise)")
     ap.add_argument("--aov-spp", type=int, default=None, help="samples of the AOVs (default min(ns, 16))")
     ap.add_argument("--aov-out", default=None, metavar="PREFIX",
                     help="write PREFIX_albedo.png, PREFIX_normal.png, PREFIX_depth.png")
@@ -81,6 +88,12 @@ def count_map(count, max_spp):
 
 def main(argv=None) -> int:
     a = parse(argv)
+    if a.denoise and a.denoise_var:
+        print("--denoise and --denoise-var exclude each other", file=sys.stderr)
+        return 2
+    if a.denoise_var and a.gpus != 1:
+        print("--denoise-var needs one GPU", file=sys.stderr)
+        return 2
     sc = ref_scenes.BY_SCENEID[a.sceneid](float(a.nx) / float(a.ny), contents=a.contents)  # :894-919
     r = (capi.Renderer(sc.text(), device=a.device) if a.gpus == 1 else
          capi.Renderer(sc.text(), devices=list(range(a.device, a.device + a.gpus))))
@@ -94,14 +107,23 @@ def main(argv=None) -> int:
     if a.adaptive is not None:
         out = r.render_adaptive(a.nx, a.ny, a.ns, a.max_depth, batch_spp=a.batch_spp, min_spp=a.min_spp,
                                 rel_tol=a.adaptive, tile=1)
+    elif a.denoise_var:  # the fixed-spp frame as one adaptive pass, which keeps its moments
+        out = r.render_adaptive(a.nx, a.ny, a.ns, a.max_depth, batch_spp=a.ns, min_spp=a.ns, rel_tol=0.0, tile=1)
     else:
         out = r.render(a.nx, a.ny, a.ns, a.max_depth, tile=1)
-    if a.denoise or a.aov_out:
+    if a.denoise or a.denoise_var or a.aov_out:
         aov = r.render_aov(a.nx, a.ny, a.aov_spp or min(a.ns, 16), max_depth=a.max_depth)
         if a.denoise:
             shape = (a.ny, a.nx, 3)
             den = capi.denoise(out["mean"].reshape(shape), aov["albedo"].reshape(shape), aov["normal"].reshape(shape),
                                aov["depth"].reshape(a.ny, a.nx), device=a.device)
+            out["img8"] = capi.tonemap(den.reshape(-1, 3))
+        if a.denoise_var:
+            shape = (a.ny, a.nx, 3)
+            var = r.adaptive_variance(out["count"])
+            den, _ = capi.denoise_var(out["mean"].reshape(shape), var.reshape(a.ny, a.nx), aov["albedo"].reshape(shape),
+                                      aov["normal"].reshape(shape), aov["depth"].reshape(a.ny, a.nx), device=a.device,
+                                      want_var=False)
             out["img8"] = capi.tonemap(den.reshape(-1, 3))
         if a.aov_out:
             for k, img in aov_images(aov).items():
