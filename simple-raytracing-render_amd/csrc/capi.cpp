@@ -17,7 +17,6 @@
 
 #include "capi_internal.h"
 #include "denoise.h"
-#include "denoise_var.h"
 #include "imageio.h"
 #include "meshio.h"
 #include "../../include/srr/merl.h"
@@ -636,142 +635,165 @@ int srr_render_aov_host(srr_renderer* r, const srr_params* p, int which, float* 
   return rc;
 }
 
-// ---- the a-trous denoiser (denoise.hip)
-static int denoise_check(int device, int nx, int ny, const srr_denoise_params* dp, const float* color,
-                         const float* albedo, const float* normal, const float* depth, const float* out) {
-  if (!dp) return fail(SRR_EINVAL, "srr_denoise: null params");
-  if (dp->struct_size < sizeof(srr_denoise_params))
-    return fail(SRR_EINVAL, "srr_denoise_params.struct_size " + std::to_string(dp->struct_size) +
-                                " is smaller than the " + std::to_string(sizeof(srr_denoise_params)) +
-                                " bytes this library reads");
-  if (device < 0) return fail(SRR_EINVAL, "srr_denoise: bad device");
-  if (nx < 1 || ny < 1 || nx > 65536 || ny > 65536 || (int64_t)nx * ny > ((int64_t)1 << 28))
-    return fail(SRR_EINVAL, "srr_denoise: 1 <= nx, ny <= 65536 and nx*ny <= 2^28");
-  if (dp->iterations < 1 || dp->iterations > 6) return fail(SRR_EINVAL, "srr_denoise: iterations must be 1..6");
-  for (const float k : {dp->k_c, dp->k_n, dp->k_z})
-    if (!(k >= 0.f) || !(k <= 3.402823466e38f))  // (NaN fails both comparisons)
-      return fail(SRR_EINVAL, "srr_denoise: k_c, k_n, k_z must be finite and >= 0");
-  if (dp->flags & ~SRR_DENOISE_DEMODULATE) return fail(SRR_EINVAL, "srr_denoise: unknown flags");
-  if (!color || !albedo || !normal || !depth || !out) return fail(SRR_EINVAL, "srr_denoise: null buffer");
-  const size_t n = (size_t)nx * ny * sizeof(float);
-  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + 3 * n;
-  const std::pair<const float*, size_t> in[] = {{color, 3 * n}, {albedo, 3 * n}, {normal, 3 * n}, {depth, n}};
-  for (const auto& b : in)
-    if ((uintptr_t)b.first < o1 && o0 < (uintptr_t)b.first + b.second)
-      return fail(SRR_EINVAL, "srr_denoise: the output overlaps an input");
-  return 0;
-}
-
-int srr_denoise_defaults(srr_denoise_params* dp) {
-  if (!dp) return fail(SRR_EINVAL, "null argument");
-  // chosen by the sweep of DESIGN.md §4.2 (profiles/r08/denoise.txt)
-  *dp = srr_denoise_params{(uint32_t)sizeof(srr_denoise_params), 3, 256.0f, 32.0f, 64.0f, 0};
-  return 0;
-}
-
+// ---- the a-trous denoisers (denoise.hip): srr_denoise and srr_denoise_var
+extern "C++" {
 namespace {
-// scratch of srr_denoise, kept per device between calls: two colour images and
-// the guides, float4 per pixel each
-struct DenoiseScratch {
-  DeviceMem<float4> buf;  // [3][pixels]
+// what tells the two filters' entries apart: the name in their messages, the label of
+// their first strength, the kernels' policy
+struct DnEntry {
+  const char* fn;
+  const char* k0;
+  AtrousStop stop;
 };
-std::mutex g_dn_mu;
-// (never destroyed: at process exit the HIP runtime may be gone before this library's statics)
-std::map<int, DenoiseScratch>& g_dn_scratch = *new std::map<int, DenoiseScratch>;
-}  // namespace
+const DnEntry kDnColour{"srr_denoise", "k_c", kColourStop}, kDnVar{"srr_denoise_var", "k_l", kVarianceStop};
+float dn_k0(const srr_denoise_params& p) { return p.k_c; }
+float dn_k0(const srr_denoise_var_params& p) { return p.k_l; }
 
-int srr_denoise(int device, int nx, int ny, const srr_denoise_params* dp, const float* d_color,
-                const float* d_albedo, const float* d_normal, const float* d_depth, float* d_out) {
-  // every refusal comes before the GPU is touched
-  if (const int rc = denoise_check(device, nx, ny, dp, d_color, d_albedo, d_normal, d_depth, d_out)) return rc;
-  static const int variant = [] {  // SRR_DENOISE_VARIANT: measurements only
+struct DnBuffers {  // var and var_out: srr_denoise_var only (var_out may be NULL there too)
+  const float *color, *var, *albedo, *normal, *depth;
+  float *out, *var_out;
+};
+
+struct Image {  // a caller's buffer and, in the _host entries, its part of the staging allocation
+  const float* p;
+  size_t floats;
+  float* dev = nullptr;
+};
+bool overlap(const Image& a, const Image& b) {
+  return (uintptr_t)a.p < (uintptr_t)b.p + b.floats * sizeof(float) &&
+         (uintptr_t)b.p < (uintptr_t)a.p + a.floats * sizeof(float);
+}
+
+template <class Params>
+int denoise_check(const DnEntry& E, int device, int nx, int ny, const Params* dp, const DnBuffers& b) {
+  const std::string fn = E.fn;
+  if (!dp) return fail(SRR_EINVAL, fn + ": null params");
+  if (dp->struct_size < sizeof(Params))
+    return fail(SRR_EINVAL, fn + "_params.struct_size " + std::to_string(dp->struct_size) + " is smaller than the " +
+                                std::to_string(sizeof(Params)) + " bytes this library reads");
+  if (device < 0) return fail(SRR_EINVAL, fn + ": bad device");
+  if (nx < 1 || ny < 1 || nx > 65536 || ny > 65536 || (int64_t)nx * ny > ((int64_t)1 << 28))
+    return fail(SRR_EINVAL, fn + ": 1 <= nx, ny <= 65536 and nx*ny <= 2^28");
+  if (dp->iterations < 1 || dp->iterations > 6) return fail(SRR_EINVAL, fn + ": iterations must be 1..6");
+  for (const float k : {dn_k0(*dp), dp->k_n, dp->k_z})
+    if (!(k >= 0.f) || !(k <= 3.402823466e38f))  // (NaN fails both comparisons)
+      return fail(SRR_EINVAL, fn + ": " + E.k0 + ", k_n, k_z must be finite and >= 0");
+  if (dp->flags & ~SRR_DENOISE_DEMODULATE) return fail(SRR_EINVAL, fn + ": unknown flags");
+  const bool has_var = E.stop == kVarianceStop;
+  if (!b.color || (has_var && !b.var) || !b.albedo || !b.normal || !b.depth || !b.out)
+    return fail(SRR_EINVAL, fn + ": null buffer");
+  const size_t n = (size_t)nx * ny;
+  const Image in[] = {{b.color, 3 * n}, {b.var, n}, {b.albedo, 3 * n}, {b.normal, 3 * n}, {b.depth, n}};
+  const Image outs[] = {{b.out, 3 * n}, {b.var_out, n}};
+  for (const Image& o : outs)
+    for (const Image& i : in)
+      if (o.p && i.p && overlap(o, i))
+        return fail(SRR_EINVAL, fn + (has_var ? ": an output" : ": the output") + " overlaps an input");
+  if (b.var_out && overlap(outs[0], outs[1])) return fail(SRR_EINVAL, fn + ": the outputs overlap each other");
+  return 0;
+}
+
+int denoise_variant() {  // SRR_DENOISE_VARIANT: measurements only
+  static const int variant = [] {
     const char* e = getenv("SRR_DENOISE_VARIANT");
     if (e && !strcmp(e, "tile")) return (int)kDnTile;
     if (e && !strcmp(e, "gather")) return (int)kDnGather;
     return (int)kDnAuto;
   }();
+  return variant;
+}
+
+// the filters' scratch, kept per device between calls: the two x images that the
+// iterations ping-pong and the guides, float4 per pixel each
+std::mutex g_dn_mu;
+// (never destroyed: at process exit the HIP runtime may be gone before this library's statics)
+std::map<int, DeviceMem<float4>>& g_dn_scratch = *new std::map<int, DeviceMem<float4>>;
+
+template <class Params>
+int denoise_device(const DnEntry& E, int device, int nx, int ny, const Params* dp, const DnBuffers& b) {
+  // every refusal comes before the GPU is touched
+  if (const int rc = denoise_check(E, device, nx, ny, dp, b)) return rc;
   const size_t n = (size_t)nx * ny;
   std::lock_guard<std::mutex> lock(g_dn_mu);
   HIPCHK(hipSetDevice(device));
-  DenoiseScratch& W = g_dn_scratch[device];
-  MEMCHK(W.buf.grow(3 * n), SRR_ENOMEM, "srr_denoise: scratch images");
-  float4* x[2] = {W.buf.get(), W.buf.get() + n};
-  float4* guide = W.buf.get() + 2 * n;
+  DeviceMem<float4>& W = g_dn_scratch[device];
+  MEMCHK(W.grow(3 * n), SRR_ENOMEM, std::string(E.fn) + ": scratch images");
+  float4* x[2] = {W.get(), W.get() + n};
+  float4* guide = W.get() + 2 * n;
   const bool demod = (dp->flags & SRR_DENOISE_DEMODULATE) != 0;
   hipStream_t st = nullptr;  // the caller's inputs were written on the legacy stream or are complete
-  launch_denoise_pack((int64_t)n, d_color, demod ? d_albedo : nullptr, d_normal, d_depth, x[0], guide, st);
+  launch_atrous_pack(E.stop, (int64_t)n, b.color, b.var, demod ? b.albedo : nullptr, b.normal, b.depth, x[0], guide, st);
   for (int k = 0; k < dp->iterations; ++k) {
     const bool last = k + 1 == dp->iterations;
-    DnIter I{};
+    AtrousIter I{};
     I.nx = nx;
     I.ny = ny;
     I.step = 1 << k;
-    I.kc = dp->k_c * (float)(1 << (2 * k));
+    I.k = E.stop == kColourStop ? dn_k0(*dp) * (float)(1 << (2 * k)) : dn_k0(*dp);
     I.kn = dp->k_n;
     I.kz = dp->k_z;
     I.x_in = x[k & 1];
     I.guide = guide;
     I.x_out = last ? nullptr : x[(k & 1) ^ 1];
-    I.out = last ? d_out : nullptr;
-    I.albedo = last && demod ? d_albedo : nullptr;
-    launch_denoise_iter(I, variant, st);
+    I.out = last ? b.out : nullptr;
+    I.var_out = last ? b.var_out : nullptr;
+    I.albedo = last && demod ? b.albedo : nullptr;
+    launch_atrous_iter(E.stop, I, denoise_variant(), st);
   }
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(st));
   return 0;
 }
 
-int srr_denoise_host(int device, int nx, int ny, const srr_denoise_params* dp, const float* color,
-                     const float* albedo, const float* normal, const float* depth, float* out) {
-  if (const int rc = denoise_check(device, nx, ny, dp, color, albedo, normal, depth, out)) return rc;
-  const size_t n = (size_t)nx * ny;
-  DeviceMem<float> buf;  // colour, albedo, normal [3n each], depth [n], output [3n]
-  HIPCHK(hipSetDevice(device));
-  MEMCHK(buf.grow(13 * n), SRR_EIO, "srr_denoise_host: staging images");
-  float* const d = buf.get();
-  float *dc = d, *da = d + 3 * n, *dn = d + 6 * n, *dz = d + 9 * n, *dout = d + 10 * n;
-  hipError_t e = hipMemcpy(dc, color, 3 * n * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(da, albedo, 3 * n * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dn, normal, 3 * n * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dz, depth, n * sizeof(float), hipMemcpyHostToDevice);
-  int rc = e == hipSuccess ? srr_denoise(device, nx, ny, dp, dc, da, dn, dz, dout) : fail(SRR_EIO, hipGetErrorString(e));
-  if (rc == 0) {
-    e = hipMemcpy(out, dout, 3 * n * sizeof(float), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = fail(SRR_EIO, hipGetErrorString(e));
+// The _host entries: every image that has a host pointer gets its part of one device
+// allocation, the first n_in of them are copied there, and the rest are copied back.
+template <size_t N>
+int stage_in(DeviceMem<float>& buf, const std::string& what, Image (&img)[N], size_t n_in) {
+  size_t total = 0;
+  for (const Image& i : img) total += i.p ? i.floats : 0;
+  MEMCHK(buf.grow(total), SRR_EIO, what);
+  float* d = buf.get();
+  for (Image& i : img) {
+    if (!i.p) continue;
+    i.dev = d;
+    d += i.floats;
+    if (size_t(&i - img) >= n_in) continue;
+    const hipError_t e = hipMemcpy(i.dev, i.p, i.floats * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(SRR_EIO, hipGetErrorString(e));
   }
-  return rc;
+  return 0;
+}
+template <size_t N>
+int stage_out(Image (&img)[N], size_t n_in) {
+  for (size_t j = n_in; j < N; ++j) {
+    if (!img[j].p) continue;
+    const hipError_t e =
+        hipMemcpy(const_cast<float*>(img[j].p), img[j].dev, img[j].floats * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(SRR_EIO, hipGetErrorString(e));
+  }
+  return 0;
 }
 
-// ---- the variance-guided a-trous filter (denoise_var.hip)
-static int denoise_var_check(int device, int nx, int ny, const srr_denoise_var_params* dp, const float* color,
-                             const float* var, const float* albedo, const float* normal, const float* depth,
-                             const float* out, const float* var_out) {
-  if (!dp) return fail(SRR_EINVAL, "srr_denoise_var: null params");
-  if (dp->struct_size < sizeof(srr_denoise_var_params))
-    return fail(SRR_EINVAL, "srr_denoise_var_params.struct_size " + std::to_string(dp->struct_size) +
-                                " is smaller than the " + std::to_string(sizeof(srr_denoise_var_params)) +
-                                " bytes this library reads");
-  if (device < 0) return fail(SRR_EINVAL, "srr_denoise_var: bad device");
-  if (nx < 1 || ny < 1 || nx > 65536 || ny > 65536 || (int64_t)nx * ny > ((int64_t)1 << 28))
-    return fail(SRR_EINVAL, "srr_denoise_var: 1 <= nx, ny <= 65536 and nx*ny <= 2^28");
-  if (dp->iterations < 1 || dp->iterations > 6) return fail(SRR_EINVAL, "srr_denoise_var: iterations must be 1..6");
-  for (const float k : {dp->k_l, dp->k_n, dp->k_z})
-    if (!(k >= 0.f) || !(k <= 3.402823466e38f))  // (NaN fails both comparisons)
-      return fail(SRR_EINVAL, "srr_denoise_var: k_l, k_n, k_z must be finite and >= 0");
-  if (dp->flags & ~SRR_DENOISE_DEMODULATE) return fail(SRR_EINVAL, "srr_denoise_var: unknown flags");
-  if (!color || !var || !albedo || !normal || !depth || !out) return fail(SRR_EINVAL, "srr_denoise_var: null buffer");
-  const size_t n = (size_t)nx * ny * sizeof(float);
-  const std::pair<const float*, size_t> in[] = {{color, 3 * n}, {var, n}, {albedo, 3 * n}, {normal, 3 * n}, {depth, n}};
-  const std::pair<const float*, size_t> outs[] = {{out, 3 * n}, {var_out, n}};
-  auto overlap = [](const std::pair<const float*, size_t>& a, const std::pair<const float*, size_t>& b) {
-    return (uintptr_t)a.first < (uintptr_t)b.first + b.second && (uintptr_t)b.first < (uintptr_t)a.first + a.second;
-  };
-  for (const auto& o : outs) {
-    if (!o.first) continue;  // (var_out may be NULL)
-    for (const auto& b : in)
-      if (overlap(o, b)) return fail(SRR_EINVAL, "srr_denoise_var: an output overlaps an input");
-  }
-  if (var_out && overlap(outs[0], outs[1])) return fail(SRR_EINVAL, "srr_denoise_var: the outputs overlap each other");
+template <class Params>
+int denoise_host(const DnEntry& E, int device, int nx, int ny, const Params* dp, const DnBuffers& h) {
+  if (const int rc = denoise_check(E, device, nx, ny, dp, h)) return rc;
+  const size_t n = (size_t)nx * ny;
+  Image img[] = {{h.color, 3 * n}, {h.var, n}, {h.albedo, 3 * n}, {h.normal, 3 * n}, {h.depth, n},
+                 {h.out, 3 * n},   {h.var_out, n}};
+  DeviceMem<float> buf;
+  HIPCHK(hipSetDevice(device));
+  if (const int rc = stage_in(buf, std::string(E.fn) + "_host: staging images", img, 5)) return rc;
+  const int rc = denoise_device(E, device, nx, ny, dp,
+                                {img[0].dev, img[1].dev, img[2].dev, img[3].dev, img[4].dev, img[5].dev, img[6].dev});
+  return rc ? rc : stage_out(img, 5);
+}
+}  // namespace
+}  // extern "C++"
+
+int srr_denoise_defaults(srr_denoise_params* dp) {
+  if (!dp) return fail(SRR_EINVAL, "null argument");
+  // chosen by the sweep of DESIGN.md §4.2 (profiles/r08/denoise.txt)
+  *dp = srr_denoise_params{(uint32_t)sizeof(srr_denoise_params), 3, 256.0f, 32.0f, 64.0f, 0};
   return 0;
 }
 
@@ -783,76 +805,26 @@ int srr_denoise_var_defaults(srr_denoise_var_params* dp) {
   return 0;
 }
 
+int srr_denoise(int device, int nx, int ny, const srr_denoise_params* dp, const float* d_color,
+                const float* d_albedo, const float* d_normal, const float* d_depth, float* d_out) {
+  return denoise_device(kDnColour, device, nx, ny, dp, {d_color, nullptr, d_albedo, d_normal, d_depth, d_out, nullptr});
+}
+
+int srr_denoise_host(int device, int nx, int ny, const srr_denoise_params* dp, const float* color,
+                     const float* albedo, const float* normal, const float* depth, float* out) {
+  return denoise_host(kDnColour, device, nx, ny, dp, {color, nullptr, albedo, normal, depth, out, nullptr});
+}
+
 int srr_denoise_var(int device, int nx, int ny, const srr_denoise_var_params* dp, const float* d_color,
                     const float* d_var, const float* d_albedo, const float* d_normal, const float* d_depth,
                     float* d_out, float* d_var_out) {
-  // every refusal comes before the GPU is touched
-  if (const int rc = denoise_var_check(device, nx, ny, dp, d_color, d_var, d_albedo, d_normal, d_depth, d_out, d_var_out))
-    return rc;
-  static const int variant = [] {  // SRR_DENOISE_VARIANT, as srr_denoise reads it: measurements only
-    const char* e = getenv("SRR_DENOISE_VARIANT");
-    if (e && !strcmp(e, "tile")) return (int)kDnTile;
-    if (e && !strcmp(e, "gather")) return (int)kDnGather;
-    return (int)kDnAuto;
-  }();
-  const size_t n = (size_t)nx * ny;
-  std::lock_guard<std::mutex> lock(g_dn_mu);
-  HIPCHK(hipSetDevice(device));
-  // two (colour, variance) images and the guides: the size and the role of srr_denoise's
-  // scratch, so the two filters share the device's
-  DenoiseScratch& W = g_dn_scratch[device];
-  MEMCHK(W.buf.grow(3 * n), SRR_ENOMEM, "srr_denoise_var: scratch images");
-  float4* x[2] = {W.buf.get(), W.buf.get() + n};
-  float4* guide = W.buf.get() + 2 * n;
-  const bool demod = (dp->flags & SRR_DENOISE_DEMODULATE) != 0;
-  hipStream_t st = nullptr;  // the caller's inputs were written on the legacy stream or are complete
-  launch_denoise_var_pack((int64_t)n, d_color, d_var, demod ? d_albedo : nullptr, d_normal, d_depth, x[0], guide, st);
-  for (int k = 0; k < dp->iterations; ++k) {
-    const bool last = k + 1 == dp->iterations;
-    DnvIter I{};
-    I.nx = nx;
-    I.ny = ny;
-    I.step = 1 << k;
-    I.kl = dp->k_l;
-    I.kn = dp->k_n;
-    I.kz = dp->k_z;
-    I.x_in = x[k & 1];
-    I.guide = guide;
-    I.x_out = last ? nullptr : x[(k & 1) ^ 1];
-    I.out = last ? d_out : nullptr;
-    I.var_out = last ? d_var_out : nullptr;
-    I.albedo = last && demod ? d_albedo : nullptr;
-    launch_denoise_var_iter(I, variant, st);
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st));
-  return 0;
+  return denoise_device(kDnVar, device, nx, ny, dp, {d_color, d_var, d_albedo, d_normal, d_depth, d_out, d_var_out});
 }
 
 int srr_denoise_var_host(int device, int nx, int ny, const srr_denoise_var_params* dp, const float* color,
                          const float* var, const float* albedo, const float* normal, const float* depth, float* out,
                          float* var_out) {
-  if (const int rc = denoise_var_check(device, nx, ny, dp, color, var, albedo, normal, depth, out, var_out)) return rc;
-  const size_t n = (size_t)nx * ny;
-  DeviceMem<float> buf;  // colour, albedo, normal [3n each], depth, variance [n each], outputs [3n, n]
-  HIPCHK(hipSetDevice(device));
-  MEMCHK(buf.grow(15 * n), SRR_EIO, "srr_denoise_var_host: staging images");
-  float* const d = buf.get();
-  float *dc = d, *da = d + 3 * n, *dn = d + 6 * n, *dz = d + 9 * n, *dv = d + 10 * n, *dout = d + 11 * n,
-        *dvout = d + 14 * n;
-  hipError_t e = hipMemcpy(dc, color, 3 * n * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(da, albedo, 3 * n * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dn, normal, 3 * n * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dz, depth, n * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dv, var, n * sizeof(float), hipMemcpyHostToDevice);
-  int rc = e == hipSuccess ? srr_denoise_var(device, nx, ny, dp, dc, dv, da, dn, dz, dout, var_out ? dvout : nullptr)
-                           : fail(SRR_EIO, hipGetErrorString(e));
-  if (rc == 0) {
-    e = hipMemcpy(out, dout, 3 * n * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && var_out) e = hipMemcpy(var_out, dvout, n * sizeof(float), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = fail(SRR_EIO, hipGetErrorString(e));
-  }
-  return rc;
+  return denoise_host(kDnVar, device, nx, ny, dp, {color, var, albedo, normal, depth, out, var_out});
 }
 
 int srr_render_wait(srr_renderer* r, int64_t ticket, srr_stats* stats) {
