@@ -314,6 +314,63 @@ int srr_render_adaptive_host(srr_renderer* r, const srr_params* p, const srr_ada
 /* The convergence rule above on the host (no GPU): 1 converged, 0 not. */
 int srr_adaptive_converged(int32_t n, float s1, float s2, float rel_tol, float abs_eps);
 
+/* ---- Resuming an adaptive frame.  The ADAPTIVE STATE of a renderer is, per slot i
+ * of the shard's pixel list (srr_shard_pixels() order): n_i, the samples held
+ * (int32); sums_i, the rgb sums (3 floats); (s1_i, s2_i), the luminance moments.  A
+ * successful srr_render_adaptive leaves it, and so do a successful
+ * srr_render_adaptive_resume and srr_adaptive_state_set.
+ *
+ * For the parameters of a call (B = p->spp, batch_spp, min_spp, rel_tol, abs_eps) a
+ * slot is RETIRED iff n_i >= B, or n_i >= min_spp, rel_tol > 0 and
+ * srr_adaptive_converged(n_i, s1_i, s2_i, rel_tol, abs_eps).  The resume loop: while
+ * some slot is not retired,
+ *   1. n = the smallest n_i over the slots that are not retired;
+ *   2. the pass's active list is the not retired slots with n_i == n, in ascending
+ *      slot order;
+ *   3. w = min(batch_spp, B - n);
+ *   4. each active slot receives the samples with the global indices [n, n + w),
+ *      folded in sample order by the fold of the fresh frame;
+ *   5. n_i = n + w.
+ * Retirement is evaluated afresh from the state after every pass, so slots that
+ * retired at different counts can become active again under a tighter tolerance,
+ * and levels merge as the lower one catches up.  Samples are never removed: a slot
+ * with n_i > B (the budget was lowered) is simply retired.  A slot with n_i == 0
+ * starts from zero sums and moments, whatever the state holds for it.  From an
+ * all-zero state this loop is exactly the loop of srr_render_adaptive.  A path
+ * depends only on (pixel, global sample index), so a slot that ends with n_i samples
+ * holds bitwise the fixed-spp frame of spp = n_i, however many calls it took.
+ *
+ * srr_render_adaptive_resume: arguments as srr_render_adaptive.  On return d_mean
+ * and d_count (may be NULL) are written for EVERY slot, also for those that never
+ * became active in this call: sum * (float)(1.0 / (float)n_i), and n_i.  stats:
+ * passes, paths and world_rays cover this call only; pixels_retired is the number of
+ * slots that end with n_i < p->spp (for a fresh frame that is the same number).
+ * SRR_EINVAL, before anything is enqueued: in every case in which
+ * srr_render_adaptive refuses; for a renderer that holds no valid adaptive state;
+ * for a frame whose nx, ny, tile, shard_index or shard_count differs from the one
+ * the state belongs to; and for a state whose rgb sums have been overwritten since:
+ * they live in the progressive accumulator, which a synchronous srr_render /
+ * srr_render_device and srr_accum_set write (srr_adaptive_variance, which needs only
+ * the moments, keeps working after those).  max_depth, base_seed and the scene are
+ * not checked: continuing with others is the caller's responsibility, as with
+ * srr_accum_set.  A resume that fails after it has started leaves no valid state. */
+int srr_render_adaptive_resume(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, float* d_mean,
+                               int32_t* d_count, srr_adaptive_stats* stats);
+/* Host convenience, as srr_render_adaptive_host. */
+int srr_render_adaptive_resume_host(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, float* mean,
+                                    int32_t* count, unsigned char* rgb8, srr_adaptive_stats* stats);
+/* The adaptive state into host buffers: sums (npix*3), mom (npix*2: s1, s2) and
+ * count (npix), any of which may be NULL; *npix (may be NULL) = its slots.
+ * SRR_EINVAL for a multi-device renderer, a renderer without a valid state, and for
+ * sums != NULL when the rgb sums have been overwritten since. */
+int srr_adaptive_state_get(srr_renderer* r, float* sums, float* mom, int32_t* count, int64_t* npix);
+/* Install a state from host buffers (none may be NULL).  p names the frame it belongs
+ * to (nx, ny, tile, shard_index, shard_count; nothing else of p is read); SRR_EINVAL
+ * unless npix == srr_shard_pixels(p) and every count >= 0, and for a multi-device
+ * renderer.  Like srr_render_adaptive it invalidates the progressive running sums. */
+int srr_adaptive_state_set(srr_renderer* r, const srr_params* p, const float* sums, const float* mom,
+                           const int32_t* count, int64_t npix);
+
 /* ---- Variance of a pixel's mean luminance, from the moments (s1, s2) that the
  * adaptive frame keeps for the rule above, for a pixel that holds n samples.  Every
  * operation in float32, in exactly this order, without fused multiply-add; rdiv is
@@ -328,7 +385,8 @@ int srr_adaptive_converged(int32_t n, float s1, float s2, float rel_tol, float a
  * srr_variance_of_mean evaluates it on the host (no GPU) by the code the kernel runs.
  *
  * srr_adaptive_variance reads the moments left by the most recent SUCCESSFUL
- * srr_render_adaptive on this renderer (npix = that frame's shard pixel count) and
+ * srr_render_adaptive (or resume, or srr_adaptive_state_set: the adaptive state above)
+ * on this renderer (npix = that frame's shard pixel count) and
  * d_count[i], that frame's counts (DEVICE pointer, npix int32: what the frame wrote
  * to its d_count), and writes d_var[i] (DEVICE pointer, npix floats), both in
  * srr_shard_pixels() order.  One small kernel on the renderer's synchronous stream;

@@ -465,8 +465,9 @@ int srr_render_device_async(srr_renderer* r, const srr_params* p, float* d_mean,
   return 0;
 }
 
-int srr_render_adaptive(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, float* d_mean,
-                        int32_t* d_count, srr_adaptive_stats* stats) {
+// srr_render_adaptive (resume = false) and srr_render_adaptive_resume
+static int render_adaptive_entry(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, float* d_mean,
+                                 int32_t* d_count, srr_adaptive_stats* stats, bool resume) {
   if (!r || !p || !a || !d_mean) return fail(SRR_EINVAL, "null argument");
   // every refusal comes before anything is staged or enqueued
   if (a->struct_size < sizeof(srr_adaptive_params))
@@ -488,9 +489,22 @@ int srr_render_adaptive(srr_renderer* r, const srr_params* p, const srr_adaptive
     return fail(SRR_EINVAL, "srr_render_adaptive: rel_tol and abs_eps must be >= 0");
   // the shard's pixel list is built and uploaded once per shard, as in srr_render_device
   const int key[5] = {p->nx, p->ny, p->shard_index, p->shard_count, p->tile};
+  if (resume) {
+    const AdaptiveState& A = r->adaptive;
+    if (A.valid_npix <= 0)
+      return fail(SRR_EINVAL, "srr_render_adaptive_resume: the renderer holds no adaptive state (a successful "
+                              "srr_render_adaptive, resume or srr_adaptive_state_set must come first)");
+    if (!A.sums_valid)
+      return fail(SRR_EINVAL, "srr_render_adaptive_resume: the state's rgb sums have been overwritten since (by a "
+                              "synchronous render or srr_accum_set)");
+    if (!std::equal(key, key + 5, A.key))
+      return fail(SRR_EINVAL, "srr_render_adaptive_resume: the adaptive state belongs to another frame or shard");
+  }
   const bool held = std::equal(key, key + 5, r->pix_key);
   int64_t npix = held ? r->pix_n : srr_shard_pixels(p, nullptr);
   if (npix < 0) return (int)npix;
+  if (resume && npix != r->adaptive.valid_npix)
+    return fail(SRR_EINVAL, "srr_render_adaptive_resume: the adaptive state belongs to another frame or shard");
   if (npix == 0) {  // a shard without pixels: no pass
     if (stats) {
       const uint32_t size = stats->struct_size;
@@ -506,7 +520,7 @@ int srr_render_adaptive(srr_renderer* r, const srr_params* p, const srr_adaptive
     r->pix_key[0] = -1;  // forgotten until the render succeeds
   }
   std::string err;
-  int rc = render_adaptive(r, p, a, held ? nullptr : pix.data(), npix, d_mean, d_count, stats, err);
+  int rc = render_adaptive(r, p, a, held ? nullptr : pix.data(), npix, d_mean, d_count, stats, resume, err);
   if (rc < 0) return fail(rc, err);
   if (!held) {
     std::copy(key, key + 5, r->pix_key);
@@ -515,8 +529,18 @@ int srr_render_adaptive(srr_renderer* r, const srr_params* p, const srr_adaptive
   return 0;
 }
 
-int srr_render_adaptive_host(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, float* mean,
-                             int32_t* count, unsigned char* rgb8, srr_adaptive_stats* stats) {
+int srr_render_adaptive(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, float* d_mean,
+                        int32_t* d_count, srr_adaptive_stats* stats) {
+  return render_adaptive_entry(r, p, a, d_mean, d_count, stats, false);
+}
+
+int srr_render_adaptive_resume(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, float* d_mean,
+                               int32_t* d_count, srr_adaptive_stats* stats) {
+  return render_adaptive_entry(r, p, a, d_mean, d_count, stats, true);
+}
+
+static int render_adaptive_host_entry(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, float* mean,
+                                      int32_t* count, unsigned char* rgb8, srr_adaptive_stats* stats, bool resume) {
   if (!r || !p || !a) return fail(SRR_EINVAL, "null argument");
   if (r->multi) return fail(SRR_EINVAL, "srr_render_adaptive: one-device renderers only");
   const int64_t npix = srr_shard_pixels(p, nullptr);
@@ -526,7 +550,7 @@ int srr_render_adaptive_host(srr_renderer* r, const srr_params* p, const srr_ada
   HIPCHK(hipSetDevice(r->device));
   MEMCHK(d.grow(at_least_16_bytes<float>(3 * npix)), SRR_EIO, "adaptive staging image");
   MEMCHK(dc.grow(at_least_16_bytes<int32_t>(npix)), SRR_ENOMEM, "adaptive count buffer");
-  int rc = srr_render_adaptive(r, p, a, d.get(), dc.get(), stats);
+  int rc = render_adaptive_entry(r, p, a, d.get(), dc.get(), stats, resume);
   std::vector<float> h(3 * npix);
   if (rc == 0) {
     hipError_t e = hipMemcpy(h.data(), d.get(), h.size() * sizeof(float), hipMemcpyDeviceToHost);
@@ -537,6 +561,47 @@ int srr_render_adaptive_host(srr_renderer* r, const srr_params* p, const srr_ada
   if (mean) std::memcpy(mean, h.data(), h.size() * sizeof(float));
   if (rgb8) srr_tonemap(h.data(), npix, rgb8);
   return 0;
+}
+
+int srr_render_adaptive_host(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, float* mean,
+                             int32_t* count, unsigned char* rgb8, srr_adaptive_stats* stats) {
+  return render_adaptive_host_entry(r, p, a, mean, count, rgb8, stats, false);
+}
+
+int srr_render_adaptive_resume_host(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, float* mean,
+                                    int32_t* count, unsigned char* rgb8, srr_adaptive_stats* stats) {
+  return render_adaptive_host_entry(r, p, a, mean, count, rgb8, stats, true);
+}
+
+int srr_adaptive_state_get(srr_renderer* r, float* sums, float* mom, int32_t* count, int64_t* npix) {
+  if (!r) return fail(SRR_EINVAL, "null renderer");
+  if (r->multi) return fail(SRR_EINVAL, "srr_adaptive_state_get: one-device renderers only");
+  const AdaptiveState& A = r->adaptive;
+  if (A.valid_npix <= 0) return fail(SRR_EINVAL, "srr_adaptive_state_get: the renderer holds no adaptive state");
+  if (sums && !A.sums_valid)
+    return fail(SRR_EINVAL, "srr_adaptive_state_get: the state's rgb sums have been overwritten since (by a "
+                            "synchronous render or srr_accum_set)");
+  if (npix) *npix = A.valid_npix;
+  std::string err;
+  const int rc = adaptive_state_get(r, sums, mom, count, err);
+  return rc < 0 ? fail(rc, err) : 0;
+}
+
+int srr_adaptive_state_set(srr_renderer* r, const srr_params* p, const float* sums, const float* mom,
+                           const int32_t* count, int64_t npix) {
+  if (!r || !p || !sums || !mom || !count) return fail(SRR_EINVAL, "null argument");
+  if (r->multi) return fail(SRR_EINVAL, "srr_adaptive_state_set: one-device renderers only");
+  const int64_t want = srr_shard_pixels(p, nullptr);
+  if (want < 0) return (int)want;
+  if (npix <= 0 || npix != want)
+    return fail(SRR_EINVAL, "srr_adaptive_state_set: npix " + std::to_string(npix) + " is not the frame's " +
+                                std::to_string(want) + " shard pixels");
+  for (int64_t i = 0; i < npix; ++i)
+    if (count[i] < 0)
+      return fail(SRR_EINVAL, "srr_adaptive_state_set: count[" + std::to_string(i) + "] is negative");
+  std::string err;
+  const int rc = adaptive_state_set(r, p, sums, mom, count, npix, err);
+  return rc < 0 ? fail(rc, err) : 0;
 }
 
 int srr_adaptive_converged(int32_t n, float s1, float s2, float rel_tol, float abs_eps) {
@@ -550,7 +615,7 @@ static int adaptive_variance_check(const srr_renderer* r, const void* count, con
   if (r->multi) return fail(SRR_EINVAL, "srr_adaptive_variance: one-device renderers only");
   if (r->adaptive.valid_npix <= 0)
     return fail(SRR_EINVAL, "srr_adaptive_variance: the renderer holds no adaptive frame's moments (the most recent "
-                            "srr_render_adaptive must have succeeded)");
+                            "srr_render_adaptive, resume or srr_adaptive_state_set must have succeeded)");
   return 0;
 }
 
@@ -875,6 +940,7 @@ int srr_accum_set(srr_renderer* r, const float* sums, int64_t npix, int64_t samp
   HIPCHK(hipSetDevice(r->device));
   drain_async(r);  // frames in flight read the pixel list this may reallocate
   MEMCHK(ensure_pixels(r, npix), SRR_EIO, "pixel list and running sums");
+  r->adaptive.sums_valid = false;  // an adaptive state's rgb sums are overwritten
   HIPCHK(hipMemcpy(r->acc.get(), sums, 3 * npix * sizeof(float), hipMemcpyHostToDevice));
   r->acc_npix = npix;
   r->acc_samples = samples;

@@ -440,6 +440,26 @@ void launch_adaptive_fold(const AdaptiveFold& A, hipStream_t st);
 // many.  blk: scratch of (n_active + 255) / 256 ints.  The lists must not alias.
 void launch_adaptive_compact(const uint8_t* keep, const int32_t* active_slot, int n_active, const int32_t* pixels,
                              int32_t* blk, int32_t* slot_out, int32_t* pixel_out, int32_t* n_out, hipStream_t st);
+// ---- resuming an adaptive frame (srr_render_adaptive_resume, renderer.cpp adaptive_resume_passes)
+// A slot that holds n samples is retired iff n >= budget, or n >= min_spp, rel_tol > 0
+// and the convergence rule holds for its moments.
+struct AdaptiveRule {
+  int budget, min_spp;
+  float rel_tol, abs_eps;
+};
+// the words of a resume's device scratch `lvl`; a pass reads the first two back in one copy
+enum { kLvlActive = 0, kLvlLevel = 1, kLvlLive = 2, kLvlBelow = 3, kLvlWords = 4 };
+// The next pass's active set from the state of all n_slots slots: live[i] = slot i is
+// not retired, lvl[kLvlLevel] = the least count among the live slots (INT_MAX: none),
+// lvl[kLvlLive] = how many are live, keep[i] = live and count[i] == that level; then
+// launch_adaptive_compact over every slot leaves their lists in slot_out / pixel_out
+// and their number in lvl[kLvlActive].
+void launch_adaptive_level_select(int n_slots, const int32_t* count, const float2* mom, const AdaptiveRule& R,
+                                  uint8_t* live, uint8_t* keep, int32_t* lvl, hipStream_t st);
+// mean[slot] = sums[slot] * (float)(1.0 / (float)count[slot]) and count_out[slot] (may be
+// nullptr) = count[slot] for every slot; lvl[kLvlBelow] (zeroed here) = the slots with count < budget
+void launch_adaptive_finish(int n_slots, const float* sums, const int32_t* count, int budget, float* mean,
+                            int32_t* count_out, int32_t* lvl, hipStream_t st);
 void launch_raygen(const SceneView& S, const PathState& P, const BatchInfo& B, hipStream_t st);
 void launch_trace(const SceneView& S, const PathState& P, const int* active, const int* count, int max_n,
                   int* lists, int list_cap, int* fam_count, int* fetch, int max_depth, unsigned long long* ctr,

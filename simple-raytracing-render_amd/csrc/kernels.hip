@@ -4084,6 +4084,78 @@ __global__ void __launch_bounds__(256) k_adaptive_fold(AdaptiveFold A) {
   }
 }
 
+// ---- resuming an adaptive frame (include/srr_capi.h srr_render_adaptive_resume)
+// A slot is retired iff it holds the budget, or min_spp samples and the rule holds.
+SRR_D bool adaptive_retired(int n, float2 m, const AdaptiveRule& R) {
+  return n >= R.budget || (n >= R.min_spp && R.rel_tol > 0.f && adaptive_converged(n, m.x, m.y, R.rel_tol, R.abs_eps));
+}
+
+// One thread per slot: live[i] = the slot is not retired; lvl[kLvlLevel] = the least
+// count of the live slots (the host set it to INT_MAX), lvl[kLvlLive] += how many
+// there are.  A block reduces both in LDS and issues one atomic of each.
+__global__ void __launch_bounds__(256) k_adaptive_level(int n_slots, const int32_t* __restrict__ count,
+                                                        const float2* __restrict__ mom, AdaptiveRule R,
+                                                        uint8_t* __restrict__ live, int32_t* lvl) {
+  __shared__ int s_min, s_live;
+  if (threadIdx.x == 0) {
+    s_min = INT_MAX;
+    s_live = 0;
+  }
+  __syncthreads();
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n_slots) {
+    const int n = count[i];
+    // (a slot without samples has no moments yet: whatever the state holds for it is not read)
+    const bool is_live = !adaptive_retired(n, n > 0 ? mom[i] : make_float2(0.f, 0.f), R);
+    live[i] = is_live ? 1 : 0;
+    if (is_live) {
+      atomicMin(&s_min, n);
+      atomicAdd(&s_live, 1);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && s_live > 0) {
+    atomicMin(&lvl[kLvlLevel], s_min);
+    atomicAdd(&lvl[kLvlLive], s_live);
+  }
+}
+
+// keep[i] = the slot is live and holds exactly the level's count: the pass's active set
+__global__ void __launch_bounds__(256) k_adaptive_select(int n_slots, const int32_t* __restrict__ count,
+                                                         const uint8_t* __restrict__ live,
+                                                         const int32_t* __restrict__ lvl, uint8_t* __restrict__ keep) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_slots) return;
+  keep[i] = live[i] != 0 && count[i] == lvl[kLvlLevel] ? 1 : 0;
+}
+
+// The frame's outputs from the state, for every slot: mean = sums * (float)(1.0 / (float)n)
+// (k_finish's division; a slot without samples gives 0), count_out (may be nullptr) = n;
+// lvl[kLvlBelow] += the slots that hold fewer samples than the budget.
+__global__ void __launch_bounds__(256) k_adaptive_finish(int n_slots, const float* __restrict__ sums,
+                                                         const int32_t* __restrict__ count, int budget,
+                                                         float* __restrict__ mean, int32_t* __restrict__ count_out,
+                                                         int32_t* lvl) {
+  __shared__ int wc[4];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  int n = budget;
+  if (i < n_slots) {
+    n = count[i];
+    const float k = n > 0 ? (float)(1.0 / (float)n) : 0.f;
+    mean[3 * (size_t)i] = n > 0 ? sums[3 * (size_t)i] * k : 0.f;
+    mean[3 * (size_t)i + 1] = n > 0 ? sums[3 * (size_t)i + 1] * k : 0.f;
+    mean[3 * (size_t)i + 2] = n > 0 ? sums[3 * (size_t)i + 2] * k : 0.f;
+    if (count_out) count_out[i] = n;
+  }
+  const uint64_t mask = __ballot(n < budget);
+  if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = __popcll(mask);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int below = wc[0] + wc[1] + wc[2] + wc[3];
+    if (below) atomicAdd(&lvl[kLvlBelow], below);
+  }
+}
+
 // Stable compaction of the surviving rows in three kernels, none of which waits on
 // another block: per-block counts, one block's scan of them, then the scatter.
 // A row's rank in its block is its rank in its wave (ballot + mbcnt) plus the
@@ -5206,6 +5278,25 @@ void launch_adaptive_fold(const AdaptiveFold& A, hipStream_t st) {
     hipLaunchKernelGGL(dev::k_adaptive_fold<true>, g, dim3(256), 0, st, A);
   else
     hipLaunchKernelGGL(dev::k_adaptive_fold<false>, g, dim3(256), 0, st, A);
+}
+
+void launch_adaptive_level_select(int n_slots, const int32_t* count, const float2* mom, const AdaptiveRule& R,
+                                  uint8_t* live, uint8_t* keep, int32_t* lvl, hipStream_t st) {
+  if (n_slots <= 0) return;
+  const dim3 g((n_slots + 255) / 256);
+  (void)hipMemsetD32Async((hipDeviceptr_t)(lvl + kLvlLevel), INT_MAX, 1, st);
+  (void)hipMemsetD32Async((hipDeviceptr_t)(lvl + kLvlLive), 0, 1, st);
+  hipLaunchKernelGGL(dev::k_adaptive_level, g, dim3(256), 0, st, n_slots, count, mom, R, live, lvl);
+  hipLaunchKernelGGL(dev::k_adaptive_select, g, dim3(256), 0, st, n_slots, count, (const uint8_t*)live,
+                     (const int32_t*)lvl, keep);
+}
+
+void launch_adaptive_finish(int n_slots, const float* sums, const int32_t* count, int budget, float* mean,
+                            int32_t* count_out, int32_t* lvl, hipStream_t st) {
+  if (n_slots <= 0) return;
+  (void)hipMemsetD32Async((hipDeviceptr_t)(lvl + kLvlBelow), 0, 1, st);
+  hipLaunchKernelGGL(dev::k_adaptive_finish, dim3((n_slots + 255) / 256), dim3(256), 0, st, n_slots, sums, count,
+                     budget, mean, count_out, lvl);
 }
 
 void launch_adaptive_compact(const uint8_t* keep, const int32_t* active_slot, int n_active, const int32_t* pixels,

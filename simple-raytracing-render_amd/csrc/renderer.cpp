@@ -289,8 +289,10 @@ static int begin_accum(srr_renderer* r, const srr_params* p, int64_t npix, hipSt
       return SRR_EINVAL;
     }
     std::copy(key, key + 5, r->acc_key);
+    r->adaptive.sums_valid = false;  // the render adds to acc
     return 0;
   }
+  r->adaptive.sums_valid = false;  // acc is zeroed: an adaptive state's sums go with it
   if (zero_pending) *zero_pending = true;
   else RCHK(hipMemsetAsync(r->acc.get(), 0, 3 * npix * sizeof(float), st));
   r->acc_npix = npix;
@@ -316,6 +318,7 @@ hipError_t ensure_pixels(srr_renderer* r, int64_t npix) {
   r->acc_npix = 0;
   r->acc_samples = 0;
   std::fill(r->acc_key, r->acc_key + 5, -1);
+  r->adaptive.sums_valid = false;
   return grow_pair(r->pixels, (size_t)npix, r->acc, 3 * (size_t)npix);
 }
 
@@ -775,6 +778,10 @@ static int ensure_adaptive(AdaptiveState& A, size_t npix, std::string& err) {
   if (npix <= A.cap) return 0;
   A = AdaptiveState{};  // every old buffer goes before the first new one comes
   RMEM(A.mom.grow(npix), "adaptive moments");
+  RMEM(A.count.grow(npix), "adaptive counts");
+  RMEM(A.live.grow(npix), "adaptive live flags");
+  RMEM(A.lvl.grow(kLvlWords), "adaptive resume words");
+  RMEM(A.lvl_host.grow(kLvlWords), "adaptive resume words' host mirror");
   for (int k = 0; k < 2; ++k) {
     RMEM(A.slot[k].grow(npix), "adaptive slot list");
     RMEM(A.pixel[k].grow(npix), "adaptive pixel list");
@@ -783,6 +790,28 @@ static int ensure_adaptive(AdaptiveState& A, size_t npix, std::string& err) {
   RMEM(A.blk.grow((npix + 255) / 256 + 1), "adaptive compaction scratch");
   RMEM(A.n_host.grow(1), "adaptive count's host mirror");
   A.cap = npix;  // (set last: after a failure above the next call starts afresh)
+  return 0;
+}
+
+// The end of a fresh or resumed frame: counters back, one sync, the stats out.
+static int adaptive_frame_end(FrameSlot& F, srr_adaptive_stats& s, srr_adaptive_stats* stats, std::string& err) {
+  hipStream_t st = F.st;
+  RCHK(hipMemcpyAsync(F.ctr_host.get(), F.ctr.get(), kPathsCtrWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  RCHK(hipEventRecord(F.ev_end, st));
+  RCHK(hipStreamSynchronize(st));
+  RCHK(hipGetLastError());
+  if (F.ctr_host.get()[kCtrError]) {
+    err = "k_paths index guard tripped (bits " + std::to_string(F.ctr_host.get()[kCtrError]) + ")";
+    return SRR_EIO;
+  }
+  float total = 0;
+  RCHK(hipEventElapsedTime(&total, F.ev_beg, F.ev_end));
+  s.world_rays = (int64_t)F.ctr_host.get()[kCtrWorldRays];
+  s.total_ms = total;
+  if (stats) {
+    s.struct_size = stats->struct_size;
+    *stats = s;
+  }
   return 0;
 }
 
@@ -837,7 +866,7 @@ static int adaptive_passes(srr_renderer* r, FrameSlot& F, const srr_params* p, c
       f.abs_eps = a->abs_eps;
       f.keep = A.keep.get();
       f.mean = d_mean;
-      f.count = d_count;
+      f.count = A.count.get();
       launch_adaptive_fold(f, st);
     }
     n = n_new;
@@ -860,18 +889,88 @@ static int adaptive_passes(srr_renderer* r, FrameSlot& F, const srr_params* p, c
     n_act = n_next;
     cur = nxt;
   }
-  RCHK(hipMemcpyAsync(F.ctr_host.get(), F.ctr.get(), kPathsCtrWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  RCHK(hipEventRecord(F.ev_end, st));
-  RCHK(hipStreamSynchronize(st));
-  RCHK(hipGetLastError());
-  if (F.ctr_host.get()[kCtrError]) {
-    err = "k_paths index guard tripped (bits " + std::to_string(F.ctr_host.get()[kCtrError]) + ")";
-    return SRR_EIO;
+  // every slot retired in some pass's fold, which left its count in the state
+  if (d_count)
+    RCHK(hipMemcpyAsync(d_count, A.count.get(), (size_t)npix * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+  return adaptive_frame_end(F, s, stats, err);
+}
+
+// The pass loop of a resumed frame (include/srr_capi.h): the slots of the state hold
+// different counts, so each pass takes the live slots of the least count -- one common
+// s_base per k_paths launch, as in a fresh frame -- and retirement is evaluated afresh
+// from the state (k_adaptive_level) before every pass.  Checked and sized like
+// adaptive_passes: only HIP itself can fail here.
+static int adaptive_resume_passes(srr_renderer* r, FrameSlot& F, const srr_params* p, const srr_adaptive_params* a,
+                                  const PathsSetup& ps, bool identity, int64_t npix, size_t win_cap, float* d_mean,
+                                  int32_t* d_count, srr_adaptive_stats* stats, std::string& err) {
+  AdaptiveState& A = r->adaptive;
+  hipStream_t st = F.st;
+  const int budget = p->spp;
+  const int32_t* shard_pixels = identity ? nullptr : r->pixels.get();
+  const AdaptiveRule rule{budget, a->min_spp, a->rel_tol, a->abs_eps};
+  int32_t* lvl = A.lvl.get();
+  srr_adaptive_stats s{};
+  RCHK(hipMemsetAsync(F.ctr.get(), 0, kPathsCtrWords * sizeof(unsigned long long), st));
+  RCHK(hipEventRecord(F.ev_beg, st));
+  bool first_launch = true;
+  int prev_level = -1;
+  for (;;) {
+    launch_adaptive_level_select((int)npix, A.count.get(), A.mom.get(), rule, A.live.get(), A.keep.get(), lvl, st);
+    launch_adaptive_compact(A.keep.get(), nullptr, (int)npix, shard_pixels, A.blk.get(), A.slot[0].get(),
+                            A.pixel[0].get(), lvl + kLvlActive, st);
+    // the one host round trip of a pass: the active count sizes the launch, the level is its s_base
+    RCHK(hipMemcpyAsync(A.lvl_host.get(), lvl, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    RCHK(hipStreamSynchronize(st));
+    const int64_t n_act = A.lvl_host.get()[kLvlActive];
+    const int n = A.lvl_host.get()[kLvlLevel];
+    if (n_act == 0 && n == INT_MAX) break;  // every slot is retired
+    // a live slot holds fewer samples than the budget, and a pass raises the least live count
+    if (n_act < 1 || n_act > npix || n < 0 || n >= budget || n <= prev_level) {
+      err = "adaptive level selection returned " + std::to_string(n_act) + " of " + std::to_string(npix) +
+            " slots at " + std::to_string(n) + " samples (budget " + std::to_string(budget) + ")";
+      return SRR_EIO;
+    }
+    prev_level = n;
+    const int w = std::min(a->batch_spp, budget - n), n_new = n + w;
+    int W = (int)std::min<int64_t>(window_samples(ps, n_act, w), (int64_t)(win_cap / (size_t)n_act));
+    if (W < w && W >= 16) W &= ~3;
+    for (int s0 = 0; s0 < w; s0 += W) {
+      const int Wn = std::min(W, w - s0);
+      const PathWork pw = paths_work(r, F, p, ps, A.pixel[0].get(), n_act, n + s0, Wn);
+      if (!first_launch) RCHK(hipMemsetAsync(pw.cursor, 0, sizeof(unsigned long long), st));  // first: zeroed with ctr
+      first_launch = false;
+      if (launch_paths(r->view, pw, r->diffuse_only ? 0 : 1, st) != 0) {
+        err = "k_paths refused the launch";  // (stack_cap was checked before the first pass)
+        return SRR_EINVAL;
+      }
+      AdaptiveFold f{};
+      f.sample = F.sample.get();
+      f.active_slot = A.slot[0].get();
+      f.n_active = (int)n_act;
+      f.spp_w = Wn;
+      f.sums = r->acc.get();
+      f.mom = A.mom.get();
+      f.init = n + s0 == 0;
+      // the fold's own verdict is not used: with the budget at n_new its last window writes
+      // every active slot's count (and a mean that k_adaptive_finish writes again)
+      f.decide = s0 + Wn >= w;
+      f.n_new = n_new;
+      f.budget = n_new;
+      f.rel_tol = a->rel_tol;
+      f.abs_eps = a->abs_eps;
+      f.keep = A.keep.get();
+      f.mean = d_mean;
+      f.count = A.count.get();
+      launch_adaptive_fold(f, st);
+    }
+    s.passes += 1;
+    s.paths += n_act * w;
   }
-  float total = 0;
-  RCHK(hipEventElapsedTime(&total, F.ev_beg, F.ev_end));
-  s.world_rays = (int64_t)F.ctr_host.get()[kCtrWorldRays];
-  s.total_ms = total;
+  launch_adaptive_finish((int)npix, r->acc.get(), A.count.get(), budget, d_mean, d_count, lvl, st);
+  RCHK(hipMemcpyAsync(A.lvl_host.get(), lvl, kLvlWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  const int rc = adaptive_frame_end(F, s, nullptr, err);
+  if (rc < 0) return rc;
+  s.pixels_retired = A.lvl_host.get()[kLvlBelow];
   if (stats) {
     s.struct_size = stats->struct_size;
     *stats = s;
@@ -879,13 +978,18 @@ static int adaptive_passes(srr_renderer* r, FrameSlot& F, const srr_params* p, c
   return 0;
 }
 
+// resume: continue the renderer's adaptive state (capi.cpp has checked that it is valid and
+// belongs to this frame) instead of starting from sample 0
 int render_adaptive(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, const int32_t* pix,
-                    int64_t npix, float* d_mean, int32_t* d_count, srr_adaptive_stats* stats, std::string& err) {
+                    int64_t npix, float* d_mean, int32_t* d_count, srr_adaptive_stats* stats, bool resume,
+                    std::string& err) {
   if (const char* e = getenv("SRR_ENGINE"); e && !strcmp(e, "wave")) {
     err = "srr_render_adaptive: path engine only (SRR_ENGINE=wave is set)";
     return SRR_EINVAL;
   }
-  r->adaptive.valid_npix = 0;  // the moments are this frame's from here on, and valid once it succeeds
+  // the state is this frame's from here on, and valid once it succeeds
+  r->adaptive.valid_npix = 0;
+  r->adaptive.sums_valid = false;
   RCHK(hipSetDevice(r->device));
   // the rgb sums of the pass loop live in the progressive accumulator: whatever it
   // held is gone, and what this frame leaves (pixels of different sample counts) is
@@ -925,10 +1029,51 @@ int render_adaptive(srr_renderer* r, const srr_params* p, const srr_adaptive_par
     const int rc = ensure_adaptive(r->adaptive, (size_t)npix, err);
     if (rc < 0) return rc;
   }
-  const int rc = adaptive_passes(r, F, p, a, ps, identity, npix, win_cap, d_mean, d_count, stats, err);
+  const int rc = (resume ? adaptive_resume_passes : adaptive_passes)(r, F, p, a, ps, identity, npix, win_cap, d_mean,
+                                                                    d_count, stats, err);
   if (rc < 0) (void)hipStreamSynchronize(F.st);  // passes already enqueued must not outlive the error
-  if (rc == 0) r->adaptive.valid_npix = npix;
+  if (rc == 0) {
+    AdaptiveState& A = r->adaptive;
+    A.valid_npix = npix;
+    A.sums_valid = true;
+    const int key[5] = {p->nx, p->ny, p->shard_index, p->shard_count, p->tile};
+    std::copy(key, key + 5, A.key);
+  }
   return rc;
+}
+
+int adaptive_state_get(srr_renderer* r, float* sums, float* mom, int32_t* count, std::string& err) {
+  const AdaptiveState& A = r->adaptive;
+  const size_t n = (size_t)A.valid_npix;
+  RCHK(hipSetDevice(r->device));
+  // (every frame and every set has synchronised its stream before it returned)
+  if (sums) RCHK(hipMemcpy(sums, r->acc.get(), 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+  if (mom) RCHK(hipMemcpy(mom, A.mom.get(), n * sizeof(float2), hipMemcpyDeviceToHost));
+  if (count) RCHK(hipMemcpy(count, A.count.get(), n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int adaptive_state_set(srr_renderer* r, const srr_params* p, const float* sums, const float* mom,
+                       const int32_t* count, int64_t npix, std::string& err) {
+  AdaptiveState& A = r->adaptive;
+  A.valid_npix = 0;  // valid again once every copy below has succeeded
+  A.sums_valid = false;
+  RCHK(hipSetDevice(r->device));
+  drain_async(r);  // frames in flight read the pixel list this may reallocate
+  r->acc_npix = 0;  // the sums are an adaptive frame's: nothing a SRR_FLAG_CONTINUE render may build on
+  RMEM(ensure_pixels(r, npix), "pixel list and running sums");
+  {
+    const int rc = ensure_adaptive(A, (size_t)npix, err);
+    if (rc < 0) return rc;
+  }
+  RCHK(hipMemcpy(r->acc.get(), sums, 3 * (size_t)npix * sizeof(float), hipMemcpyHostToDevice));
+  RCHK(hipMemcpy(A.mom.get(), mom, (size_t)npix * sizeof(float2), hipMemcpyHostToDevice));
+  RCHK(hipMemcpy(A.count.get(), count, (size_t)npix * sizeof(int32_t), hipMemcpyHostToDevice));
+  A.valid_npix = npix;
+  A.sums_valid = true;
+  const int key[5] = {p->nx, p->ny, p->shard_index, p->shard_count, p->tile};
+  std::copy(key, key + 5, A.key);
+  return 0;
 }
 
 int adaptive_variance(srr_renderer* r, const int32_t* d_count, float* d_var, std::string& err) {

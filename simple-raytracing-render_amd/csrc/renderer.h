@@ -87,7 +87,16 @@ struct AdaptiveState {
   // slots whose moments the most recent successful frame left in `mom` (0: none);
   // srr_adaptive_variance reads them
   int64_t valid_npix = 0;
+  // srr_renderer::acc still holds that state's rgb sums: every other writer of acc clears
+  // this (begin_accum, ensure_pixels, srr_accum_set), and srr_render_adaptive_resume needs it
+  bool sums_valid = false;
+  // the frame and shard the state belongs to: {nx, ny, shard_index, shard_count, tile}
+  int key[5] = {-1, -1, -1, -1, -1};
   DeviceMem<float2> mom;       // [slot] luminance moments (s1, s2)
+  DeviceMem<int32_t> count;    // [slot] samples held (n_i): the folds' count target
+  DeviceMem<uint8_t> live;     // [slot] not retired (a resume's k_adaptive_level)
+  DeviceMem<int32_t> lvl;      // a resume's words (kernels.h kLvl*)
+  PinnedMem<int32_t> lvl_host; // their mirror
   DeviceMem<int32_t> slot[2];   // active slots, ping-pong over the compactions
   DeviceMem<int32_t> pixel[2];  // their image pixels (PathWork::pixels)
   DeviceMem<uint8_t> keep;      // [active row] survives the pass
@@ -179,8 +188,15 @@ int render_device(srr_renderer* r, const srr_params* p, const int32_t* pix, int6
 int render_device_async(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t npix, float* d_mean,
                         int64_t* ticket, std::string& err);
 // srr_render_adaptive on a one-device renderer, its arguments already validated (capi.cpp)
+// resume: srr_render_adaptive_resume, the renderer's adaptive state being valid and this frame's
 int render_adaptive(srr_renderer* r, const srr_params* p, const srr_adaptive_params* a, const int32_t* pix,
-                    int64_t npix, float* d_mean, int32_t* d_count, srr_adaptive_stats* stats, std::string& err);
+                    int64_t npix, float* d_mean, int32_t* d_count, srr_adaptive_stats* stats, bool resume,
+                    std::string& err);
+// srr_adaptive_state_get / _set on a one-device renderer, arguments validated (capi.cpp);
+// get copies the valid_npix slots of the buffers asked for (nullptr: not asked for)
+int adaptive_state_get(srr_renderer* r, float* sums, float* mom, int32_t* count, std::string& err);
+int adaptive_state_set(srr_renderer* r, const srr_params* p, const float* sums, const float* mom,
+                       const int32_t* count, int64_t npix, std::string& err);
 // srr_adaptive_variance on a one-device renderer that holds a valid adaptive frame (capi.cpp)
 int adaptive_variance(srr_renderer* r, const int32_t* d_count, float* d_var, std::string& err);
 // srr_render_aov on a one-device renderer, its arguments already validated (capi.cpp);

@@ -147,6 +147,11 @@ def lib():
                                                    vp, vp, ctypes.POINTER(AdaptiveStats)]
             L.srr_adaptive_converged.argtypes = [ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                                  ctypes.c_float]
+        if hasattr(L, "srr_render_adaptive_resume"):  # (as above)
+            L.srr_render_adaptive_resume.argtypes = L.srr_render_adaptive.argtypes
+            L.srr_render_adaptive_resume_host.argtypes = L.srr_render_adaptive_host.argtypes
+            L.srr_adaptive_state_get.argtypes = [vp, vp, vp, vp, i64p]
+            L.srr_adaptive_state_set.argtypes = [vp, ctypes.POINTER(Params), vp, vp, vp, ctypes.c_int64]
         if hasattr(L, "srr_denoise"):  # (as above)
             dpp = ctypes.POINTER(DenoiseParams)
             L.srr_render_aov.argtypes = [vp, ctypes.POINTER(Params), ip, vp, vp, vp]
@@ -335,6 +340,54 @@ class Renderer:
                                          ctypes.c_void_p(d_mean_ptr), ctypes.c_void_p(d_count_ptr or None),
                                          ctypes.byref(st)))
         return st.as_dict()
+
+    def render_adaptive_resume(self, nx, ny, max_spp, max_depth=50, batch_spp=16, min_spp=16, rel_tol=0.02,
+                               abs_eps=1e-3, **kw):
+        """Continue the renderer's adaptive state (srr_render_adaptive_resume) under
+        these parameters: arguments and result as render_adaptive; mean and count
+        cover every pixel, stats this call's passes, paths and world rays."""
+        size = kw.pop("struct_size", ctypes.sizeof(AdaptiveParams))
+        p = make_params(nx, ny, max_spp, max_depth, **kw)
+        a = AdaptiveParams(size, batch_spp, min_spp, rel_tol, abs_eps)
+        n = nx * ny if self.transport != "none" else shard_pixels(p).size
+        mean = np.zeros((n, 3), np.float32)
+        count = np.zeros(n, np.int32)
+        img8 = np.zeros((n, 3), np.uint8)
+        st = AdaptiveStats(ctypes.sizeof(AdaptiveStats))
+        _check(lib().srr_render_adaptive_resume_host(self.h, ctypes.byref(p), ctypes.byref(a), _ptr(mean),
+                                                     _ptr(count), _ptr(img8), ctypes.byref(st)))
+        return dict(mean=mean, count=count, img8=img8, stats=st.as_dict())
+
+    def render_adaptive_resume_device(self, params: Params, adaptive: AdaptiveParams, d_mean_ptr: int,
+                                      d_count_ptr: int = 0) -> dict:
+        """srr_render_adaptive_resume into device buffers (e.g. torch tensors' data_ptr())."""
+        st = AdaptiveStats(ctypes.sizeof(AdaptiveStats))
+        _check(lib().srr_render_adaptive_resume(self.h, ctypes.byref(params), ctypes.byref(adaptive),
+                                                ctypes.c_void_p(d_mean_ptr or None),
+                                                ctypes.c_void_p(d_count_ptr or None), ctypes.byref(st)))
+        return st.as_dict()
+
+    def adaptive_state(self) -> dict:
+        """The adaptive state (srr_adaptive_state_get): dict(sums[n,3], mom[n,2] (s1, s2),
+        count[n]) in shard-pixel order."""
+        n = ctypes.c_int64()
+        _check(lib().srr_adaptive_state_get(self.h, None, None, None, ctypes.byref(n)))
+        out = dict(sums=np.zeros((n.value, 3), np.float32), mom=np.zeros((n.value, 2), np.float32),
+                   count=np.zeros(n.value, np.int32))
+        _check(lib().srr_adaptive_state_get(self.h, _ptr(out["sums"]), _ptr(out["mom"]), _ptr(out["count"]), None))
+        return out
+
+    def set_adaptive_state(self, nx, ny, sums, mom, count, npix=None, **kw) -> None:
+        """Install an adaptive state (srr_adaptive_state_set) of the frame nx x ny (kw:
+        shard, tile); npix defaults to count's size.  A render_adaptive_resume continues it."""
+        p = make_params(nx, ny, 1, **kw)
+        sums = np.ascontiguousarray(sums, np.float32)
+        mom = np.ascontiguousarray(mom, np.float32)
+        count = np.ascontiguousarray(count, np.int32).ravel()
+        n = count.size if npix is None else int(npix)
+        if sums.size != 3 * count.size or mom.size != 2 * count.size:
+            raise SrrError("set_adaptive_state needs sums[n, 3], mom[n, 2] and count[n]")
+        _check(lib().srr_adaptive_state_set(self.h, ctypes.byref(p), _ptr(sums), _ptr(mom), _ptr(count), n))
 
     def adaptive_variance(self, count) -> np.ndarray:
         """The variance of every pixel's mean luminance (srr_adaptive_variance_host) from
