@@ -32,6 +32,11 @@
  *   --batch-spp 16 --min-spp 16  its samples per pass / fewest samples per pixel
  *   --count-map FILE             its per-pixel sample counts as a PNG of grey
  *                                levels 255 * count / ns
+ *   --adaptive-pass-spp N        speculative passes of up to N samples per pixel
+ *                                (srr_adaptive_speculate): the same image in fewer
+ *                                passes; 0 = off
+ *   --adaptive-fill P            the pass size, in paths, they aim at (0: the
+ *                                library's default)
  *   --denoise                    one GPU, with fixed spp or --adaptive: filter the
  *                                frame with srr_denoise (its defaults) over the
  *                                first-hit AOVs of srr_render_aov; --out is then
@@ -84,13 +89,16 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
   double adaptive = -1;  // --adaptive REL_TOL (< 0: fixed spp)
   int batch_spp = 16, min_spp = 16;
   std::string count_map;
+  int pass_spp = 0;         // --adaptive-pass-spp
+  long long fill_paths = 0;  // --adaptive-fill
   bool denoise = false, denoise_var = false;
   int aov_spp = 0;  // 0: min(ns, 16)
   std::string aov_out;
   auto usage = [&]() {
     std::fprintf(stderr, "usage: %s [--sceneid N | --scene NAME] [--nx N] [--ny N] [--ns N] [--max-depth N] "
                          "[--device N] [--gpus N | --devices a,b,..] [--tile N] [--out FILE] [--dry-run] "
-                         "[--adaptive REL_TOL [--batch-spp N] [--min-spp N] [--count-map FILE]] "
+                         "[--adaptive REL_TOL [--batch-spp N] [--min-spp N] [--count-map FILE] "
+                         "[--adaptive-pass-spp N [--adaptive-fill P]]] "
                          "[--denoise | --denoise-var] [--aov-spp N] [--aov-out PREFIX]\nscenes:",
                  argv[0]);
     for (int k = 0; k < n_scenes; ++k) std::fprintf(stderr, " %d:%s", scenes[k].sceneid, scenes[k].name);
@@ -126,6 +134,8 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
     else if (a == "--batch-spp") ok = num(batch_spp) && batch_spp >= 1;
     else if (a == "--min-spp") ok = num(min_spp) && min_spp >= 1;
     else if (a == "--count-map" && i + 1 < argc) count_map = argv[++i];
+    else if (a == "--adaptive-pass-spp") ok = num(pass_spp) && pass_spp >= 0;
+    else if (a == "--adaptive-fill" && i + 1 < argc) ok = (fill_paths = std::atoll(argv[++i])) >= 0;
     else if (a == "--denoise") denoise = true;
     else if (a == "--denoise-var") denoise_var = true;
     else if (a == "--aov-spp") ok = num(aov_spp) && aov_spp >= 1;
@@ -138,6 +148,7 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
     if (name.empty() ? scenes[k].sceneid == sceneid : name == scenes[k].name) e = &scenes[k];
   if ((!e && text_path.empty()) || nx < 1 || ny < 1 || ns < 1) return usage();
   if (adaptive < 0 && !count_map.empty()) return usage();
+  if (adaptive < 0 && (pass_spp || fill_paths)) return usage();
   if (denoise && denoise_var) return usage();
   if ((denoise || denoise_var || !aov_out.empty()) && (gpus > 1 || !devices.empty())) return usage();  // one GPU
   if (aov_spp == 0) aov_spp = ns < 16 ? ns : 16;
@@ -216,7 +227,9 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
     ap.abs_eps = 1e-3f;
     ast.struct_size = sizeof ast;
     count.resize((size_t)nx * ny);
-    rc = srr_render_adaptive_host(r, &p, &ap, want_aov ? mean.data() : nullptr, count.data(), rgb8.data(), &ast);
+    rc = pass_spp || fill_paths ? srr_adaptive_speculate(r, pass_spp, (int64_t)fill_paths) : 0;
+    if (rc == 0)
+      rc = srr_render_adaptive_host(r, &p, &ap, want_aov ? mean.data() : nullptr, count.data(), rgb8.data(), &ast);
     st.world_rays = ast.world_rays;
   } else {
     rc = srr_render(r, &p, want_aov ? mean.data() : nullptr, rgb8.data(), &st);
@@ -276,9 +289,15 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
     }
     rc = srr_write_png(count_map.c_str(), nx, ny, grey.data());
   }
-  if (rc == 0 && adaptive >= 0)
-    std::fprintf(stderr, "adaptive: %lld of %lld samples in %d passes, %lld pixels stopped early\n",
-                 (long long)ast.paths, (long long)nx * ny * ns, (int)ast.passes, (long long)ast.pixels_retired);
+  if (rc == 0 && adaptive >= 0) {
+    srr_adaptive_spec_stats sp{};
+    sp.struct_size = sizeof sp;
+    rc = srr_adaptive_last_spec_stats(r, &sp);
+    std::fprintf(stderr, "adaptive: %lld of %lld samples in %d passes, %lld pixels stopped early; %lld traced, "
+                         "%lld discarded\n",
+                 (long long)ast.paths, (long long)nx * ny * ns, (int)ast.passes, (long long)ast.pixels_retired,
+                 (long long)sp.paths_traced, (long long)sp.paths_discarded);
+  }
   if (rc < 0) std::fprintf(stderr, "%s\n", srr_last_error());
   else {
     std::printf("%dms\n", (int)ms);  // :934-937

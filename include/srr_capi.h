@@ -371,6 +371,57 @@ int srr_adaptive_state_get(srr_renderer* r, float* sums, float* mom, int32_t* co
 int srr_adaptive_state_set(srr_renderer* r, const srr_params* p, const float* sums, const float* mom,
                            const int32_t* count, int64_t npix);
 
+/* ---- Speculative passes: the same adaptive frame in fewer, larger passes.  After the
+ * first pass only a few slots stay active, and a pass of few paths is bound by k_paths'
+ * ramp and drain and by the host round trip behind it.  Under this setting a pass at
+ * level n (the count its n_active slots hold) gives every slot
+ *   kmax = max(1, pass_spp_max / batch_spp)                      (integer division)
+ *   k    = clamp(fill_paths / (n_active * batch_spp), 1, kmax)   (integer division, 64-bit)
+ *   w    = min(k * batch_spp, B - n)
+ * samples in one k_paths launch, and its fold asks the retirement rule at every count
+ * n + batch_spp, n + 2*batch_spp, ... and n + w: a slot stops at the first of them where
+ * it is retired, and the samples traced for it beyond that count are thrown away; a
+ * slot that reaches n + w unretired stays live there.  k = 1 is the pass of the loops
+ * above.  A slot is asked at exactly the counts at which those loops ask it, from
+ * moments folded from the same samples in the same order, and nothing past its stop is
+ * folded: the state and every output of a frame are bit for bit what they are without
+ * speculation, whatever pass_spp_max and fill_paths are.
+ *
+ * srr_adaptive_speculate sets it for srr_render_adaptive / _resume (and their _host
+ * forms) on this renderer, from the next such call on, until changed.  pass_spp_max: the
+ * most samples a pass may give a slot; a value below 2 * batch_spp of a call (0, the
+ * default, among them) switches speculation off for that call, which then launches
+ * exactly what it launches today.  fill_paths: the pass size the schedule aims at, in
+ * paths; 0 = srr_adaptive_fill_default().  SRR_EINVAL for a negative argument and for
+ * a multi-device renderer.
+ *
+ * srr_adaptive_stats under speculation: paths stays the samples added to the per-pixel
+ * counts in the call (paths_traced - paths_discarded below); pixels_retired keeps its
+ * meaning and value; passes counts the passes launched, so it shrinks; world_rays counts
+ * the rays of every traced path, the discarded ones included, so identities between
+ * world_rays and those of fixed-spp frames hold only with speculation off (or where
+ * nothing was discarded).
+ *
+ * srr_adaptive_last_spec_stats: the launches of the most recent successful adaptive or
+ * resume call on the renderer, with or without speculation.  SRR_EINVAL for a NULL
+ * argument, a struct_size smaller than the struct, a multi-device renderer, and before
+ * any such call has succeeded.
+ * srr_adaptive_pass_width: w of the schedule above on the host (no GPU); SRR_EINVAL
+ * unless n_active >= 1, 0 <= n < budget, batch_spp >= 1, pass_spp_max >= 0 and
+ * fill_paths >= 0. */
+int srr_adaptive_speculate(srr_renderer* r, int pass_spp_max, int64_t fill_paths);
+typedef struct srr_adaptive_spec_stats {
+  uint32_t struct_size;     /* sizeof(srr_adaptive_spec_stats) of the caller (set before the call) */
+  int32_t windows;          /* k_paths launches of the most recent adaptive call */
+  int64_t paths_traced;     /* camera paths those launches traced                 */
+  int64_t paths_discarded;  /* of them, traced past their slot's stopping count   */
+} srr_adaptive_spec_stats;
+int srr_adaptive_last_spec_stats(const srr_renderer* r, srr_adaptive_spec_stats* out);
+int srr_adaptive_pass_width(int64_t n_active, int n, int budget, int batch_spp, int pass_spp_max,
+                            int64_t fill_paths);
+/* The fill_paths that 0 stands for. */
+int64_t srr_adaptive_fill_default(void);
+
 /* ---- Variance of a pixel's mean luminance, from the moments (s1, s2) that the
  * adaptive frame keeps for the rule above, for a pixel that holds n samples.  Every
  * operation in float32, in exactly this order, without fused multiply-add; rdiv is

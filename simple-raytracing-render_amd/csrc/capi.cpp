@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "adaptive_schedule.h"
 #include "capi_internal.h"
 #include "denoise.h"
 #include "imageio.h"
@@ -607,6 +608,43 @@ int srr_adaptive_state_set(srr_renderer* r, const srr_params* p, const float* su
 int srr_adaptive_converged(int32_t n, float s1, float s2, float rel_tol, float abs_eps) {
   return adaptive_converged_host(n, s1, s2, rel_tol, abs_eps);
 }
+
+int srr_adaptive_speculate(srr_renderer* r, int pass_spp_max, int64_t fill_paths) {
+  if (!r) return fail(SRR_EINVAL, "null renderer");
+  if (r->multi) return fail(SRR_EINVAL, "srr_adaptive_speculate: one-device renderers only");
+  if (pass_spp_max < 0 || fill_paths < 0)
+    return fail(SRR_EINVAL, "srr_adaptive_speculate: pass_spp_max >= 0, fill_paths >= 0");
+  r->adaptive.pass_spp_max = pass_spp_max;
+  r->adaptive.fill_paths = fill_paths;
+  return 0;
+}
+
+int srr_adaptive_last_spec_stats(const srr_renderer* r, srr_adaptive_spec_stats* out) {
+  if (!r || !out) return fail(SRR_EINVAL, "null argument");
+  if (out->struct_size < sizeof(srr_adaptive_spec_stats))
+    return fail(SRR_EINVAL, "srr_adaptive_spec_stats.struct_size " + std::to_string(out->struct_size) +
+                                " is smaller than the " + std::to_string(sizeof(srr_adaptive_spec_stats)) +
+                                " bytes this library writes");
+  if (r->multi) return fail(SRR_EINVAL, "srr_adaptive_last_spec_stats: one-device renderers only");
+  const AdaptiveState& A = r->adaptive;
+  if (A.spec_windows < 0)
+    return fail(SRR_EINVAL, "srr_adaptive_last_spec_stats: no adaptive call has succeeded on this renderer yet");
+  out->windows = A.spec_windows;
+  out->paths_traced = A.spec_traced;
+  out->paths_discarded = A.spec_discarded;
+  return 0;
+}
+
+int srr_adaptive_pass_width(int64_t n_active, int n, int budget, int batch_spp, int pass_spp_max,
+                            int64_t fill_paths) {
+  const int w = adaptive_pass_width(n_active, n, budget, batch_spp, pass_spp_max, fill_paths);
+  if (w < 0)
+    return fail(SRR_EINVAL, "srr_adaptive_pass_width: n_active >= 1, 0 <= n < budget, batch_spp >= 1, "
+                            "pass_spp_max >= 0, fill_paths >= 0");
+  return w;
+}
+
+int64_t srr_adaptive_fill_default(void) { return kAdaptiveFillDefault; }
 
 float srr_variance_of_mean(int32_t n, float s1, float s2) { return variance_of_mean_host(n, s1, s2); }
 

@@ -435,6 +435,34 @@ struct AdaptiveFold {
   int32_t* count;  // [slot]
 };
 void launch_adaptive_fold(const AdaptiveFold& A, hipStream_t st);
+// One sample window of a SPECULATIVE pass (include/srr_capi.h srr_adaptive_speculate): the
+// pass gives every active slot, which holds n samples, the w samples [n, n + w); this
+// window holds the spp_w of them from n + s0 on, rows as in AdaptiveFold.  The fold adds a
+// row's samples in order and asks the rule at every boundary c of the pass ((c - n) %
+// batch_spp == 0, or c == n + w): the slot stops at the first c with c >= budget, or
+// c >= min_spp, rel_tol > 0 and the rule holding -- nothing past c is folded, count[slot]
+// = c, mean[slot] = sums * (float)(1.0 / (float)c) and keep[j] = 0.  A slot that does not
+// stop leaves count[slot] = n + s0 + spp_w and keep[j] = 1.  In a window with s0 > 0 a
+// slot whose count is not n + s0, or that is retired at n + s0 when that is a boundary,
+// stopped in an earlier window of the pass: it is left as it is.  ctr[0] += the samples
+// of the window that lie past their slot's stop, ctr[1] += the slots that stopped in it
+// below the budget.
+struct AdaptiveSpecFold {
+  const float* sample;
+  const int32_t* active_slot;
+  int n_active, spp_w;
+  float* sums;   // [slot][3]
+  float2* mom;   // [slot] (s1, s2)
+  int n, w, s0;
+  int batch_spp, min_spp, budget;
+  float rel_tol, abs_eps;
+  uint8_t* keep;   // [n_active]
+  float* mean;     // [slot][3]
+  int32_t* count;  // [slot]
+  unsigned long long* ctr;  // [kSpecDiscarded], [kSpecStopped]
+};
+enum { kSpecDiscarded = 0, kSpecStopped = 1, kSpecWords = 2 };
+void launch_adaptive_fold_spec(const AdaptiveSpecFold& A, hipStream_t st);
 // Stable compaction of the rows with keep[j] != 0, in ascending j: slot_out[k] =
 // their slots, pixel_out[k] = pixels[slot] (nullptr: the slot itself), *n_out = how
 // many.  blk: scratch of (n_active + 255) / 256 ints.  The lists must not alias.

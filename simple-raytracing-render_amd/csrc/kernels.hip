@@ -4090,6 +4090,116 @@ SRR_D bool adaptive_retired(int n, float2 m, const AdaptiveRule& R) {
   return n >= R.budget || (n >= R.min_spp && R.rel_tol > 0.f && adaptive_converged(n, m.x, m.y, R.rel_tol, R.abs_eps));
 }
 
+// The fold of one sample window of a speculative pass (kernels.h AdaptiveSpecFold):
+// k_adaptive_fold's staging and additions, with the rule asked at every batch boundary of
+// the pass.  A thread whose slot stops folds no further sample but keeps staging and
+// meeting the barriers: nothing returns before the last __syncthreads.  The samples past
+// the stops are summed per block (shuffle, then LDS) into one 64-bit atomic.
+template <bool V4>
+__global__ void __launch_bounds__(256) k_adaptive_fold_spec(AdaptiveSpecFold A) {
+  __shared__ float tile[256 * (3 * kAccChunk + 1)];
+  __shared__ int wd[4], wq[4];
+  const int j0 = blockIdx.x * 256;
+  const int j = j0 + threadIdx.x;
+  const int nr = min(256, A.n_active - j0);
+  const int spp_w = A.spp_w;
+  const bool mine = j < A.n_active;
+  const int slot = !mine ? 0 : A.active_slot ? A.active_slot[j] : j;
+  const AdaptiveRule R{A.budget, A.min_spp, A.rel_tol, A.abs_eps};
+  const int c0 = A.n + A.s0, c_end = A.n + A.w;  // the counts at the window's base and the pass's end
+  float cx = 0, cy = 0, cz = 0, s1 = 0, s2 = 0;
+  // stopped in an earlier window of this pass: the count it left is not this window's base,
+  // or it is and the slot retired exactly there
+  bool before = mine && A.s0 > 0 && A.count[slot] != c0;
+  if (mine && !before && c0 != 0) {
+    cx = A.sums[3 * (size_t)slot];
+    cy = A.sums[3 * (size_t)slot + 1];
+    cz = A.sums[3 * (size_t)slot + 2];
+    const float2 m = A.mom[slot];
+    s1 = m.x;
+    s2 = m.y;
+    if (A.s0 > 0 && A.s0 % A.batch_spp == 0) before = adaptive_retired(c0, m, R);
+  }
+  int next_b = A.n + (A.s0 / A.batch_spp + 1) * A.batch_spp;  // the next batch boundary above c0
+  int c_stop = 0;  // > 0: the slot stopped there, in this window
+  for (int s0 = 0; s0 < spp_w; s0 += kAccChunk) {
+    const int n = min(kAccChunk, spp_w - s0);
+    if (V4) {
+      const float4* sample4 = (const float4*)A.sample;
+      const int qn = 3 * n / 4;  // float4 per row chunk (n is a multiple of 4)
+      for (int i = threadIdx.x; i < nr * qn; i += 256) {
+        const int px = i / qn, f4 = i - px * qn;
+        const float4 v = ntl(&sample4[((size_t)(j0 + px) * spp_w + s0) * 3 / 4 + f4]);
+        float* d = &tile[px * (3 * kAccChunk + 1) + 4 * f4];
+        d[0] = v.x;
+        d[1] = v.y;
+        d[2] = v.z;
+        d[3] = v.w;
+      }
+    } else {
+      const int row = 3 * n;
+      for (int i = threadIdx.x; i < nr * row; i += 256) {
+        const int px = i / row, f = i - px * row;
+        tile[px * (3 * kAccChunk + 1) + f] = ntl(&A.sample[((size_t)(j0 + px) * spp_w + s0) * 3 + f]);
+      }
+    }
+    __syncthreads();
+    if (mine && !before && c_stop == 0) {
+      const float* t = &tile[threadIdx.x * (3 * kAccChunk + 1)];
+      for (int k = 0; k < n; ++k) {
+        const float r = t[3 * k], g = t[3 * k + 1], b = t[3 * k + 2];
+        cx += r;
+        cy += g;
+        cz += b;
+        const float y = (0.2126f * r + 0.7152f * g) + 0.0722f * b;
+        s1 += y;
+        s2 += y * y;
+        const int c = c0 + s0 + k + 1;  // samples the slot holds now
+        if (c != next_b && c != c_end) continue;
+        if (c == next_b) next_b += A.batch_spp;
+        if (adaptive_retired(c, make_float2(s1, s2), R)) {
+          c_stop = c;
+          break;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  int discard = 0, stopped = 0;
+  if (mine && before) discard = spp_w;
+  if (mine && !before) {
+    A.sums[3 * (size_t)slot] = cx;
+    A.sums[3 * (size_t)slot + 1] = cy;
+    A.sums[3 * (size_t)slot + 2] = cz;
+    A.mom[slot] = make_float2(s1, s2);
+    A.count[slot] = c_stop ? c_stop : c0 + spp_w;
+    A.keep[j] = c_stop ? 0 : 1;
+    if (c_stop) {
+      const float k = 1.0 / (float)c_stop;  // k_finish
+      A.mean[3 * (size_t)slot] = cx * k;
+      A.mean[3 * (size_t)slot + 1] = cy * k;
+      A.mean[3 * (size_t)slot + 2] = cz * k;
+      discard = c0 + spp_w - c_stop;
+      stopped = c_stop < A.budget ? 1 : 0;
+    }
+  }
+  // (a window has fewer than 2^31 paths: a block's sum stays far below that)
+  for (int d = 32; d > 0; d >>= 1) {
+    discard += __shfl_down(discard, d);
+    stopped += __shfl_down(stopped, d);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    wd[threadIdx.x >> 6] = discard;
+    wq[threadIdx.x >> 6] = stopped;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int bd = wd[0] + wd[1] + wd[2] + wd[3], bq = wq[0] + wq[1] + wq[2] + wq[3];
+    if (bd) atomicAdd(&A.ctr[kSpecDiscarded], (unsigned long long)bd);
+    if (bq) atomicAdd(&A.ctr[kSpecStopped], (unsigned long long)bq);
+  }
+}
+
 // One thread per slot: live[i] = the slot is not retired; lvl[kLvlLevel] = the least
 // count of the live slots (the host set it to INT_MAX), lvl[kLvlLive] += how many
 // there are.  A block reduces both in LDS and issues one atomic of each.
@@ -5278,6 +5388,15 @@ void launch_adaptive_fold(const AdaptiveFold& A, hipStream_t st) {
     hipLaunchKernelGGL(dev::k_adaptive_fold<true>, g, dim3(256), 0, st, A);
   else
     hipLaunchKernelGGL(dev::k_adaptive_fold<false>, g, dim3(256), 0, st, A);
+}
+
+void launch_adaptive_fold_spec(const AdaptiveSpecFold& A, hipStream_t st) {
+  if (A.n_active <= 0 || A.spp_w <= 0) return;
+  const dim3 g((A.n_active + 255) / 256);
+  if (A.spp_w % 4 == 0 && ((uintptr_t)A.sample & 15) == 0)
+    hipLaunchKernelGGL(dev::k_adaptive_fold_spec<true>, g, dim3(256), 0, st, A);
+  else
+    hipLaunchKernelGGL(dev::k_adaptive_fold_spec<false>, g, dim3(256), 0, st, A);
 }
 
 void launch_adaptive_level_select(int n_slots, const int32_t* count, const float2* mom, const AdaptiveRule& R,

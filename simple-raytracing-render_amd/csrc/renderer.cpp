@@ -2,6 +2,7 @@
 #include "renderer.h"
 
 #include "multi.h"
+#include "adaptive_schedule.h"
 
 #include <algorithm>
 #include <chrono>
@@ -776,7 +777,11 @@ static int render_paths(srr_renderer* r, const srr_params* p, const int32_t* pix
 // ---- adaptive sampling (include/srr_capi.h srr_render_adaptive)
 static int ensure_adaptive(AdaptiveState& A, size_t npix, std::string& err) {
   if (npix <= A.cap) return 0;
+  const int pass_spp_max = A.pass_spp_max;
+  const int64_t fill_paths = A.fill_paths;
   A = AdaptiveState{};  // every old buffer goes before the first new one comes
+  A.pass_spp_max = pass_spp_max;  // (the setting of srr_adaptive_speculate stays)
+  A.fill_paths = fill_paths;
   RMEM(A.mom.grow(npix), "adaptive moments");
   RMEM(A.count.grow(npix), "adaptive counts");
   RMEM(A.live.grow(npix), "adaptive live flags");
@@ -789,6 +794,8 @@ static int ensure_adaptive(AdaptiveState& A, size_t npix, std::string& err) {
   RMEM(A.keep.grow(npix), "adaptive keep flags");
   RMEM(A.blk.grow((npix + 255) / 256 + 1), "adaptive compaction scratch");
   RMEM(A.n_host.grow(1), "adaptive count's host mirror");
+  RMEM(A.spec_ctr.grow(kSpecWords), "speculative fold counters");
+  RMEM(A.spec_ctr_host.grow(kSpecWords), "speculative fold counters' host mirror");
   A.cap = npix;  // (set last: after a failure above the next call starts afresh)
   return 0;
 }
@@ -815,6 +822,69 @@ static int adaptive_frame_end(FrameSlot& F, srr_adaptive_stats& s, srr_adaptive_
   return 0;
 }
 
+// Speculative passes (include/srr_capi.h srr_adaptive_speculate) of one call: whether the
+// setting gives this call's batch_spp two batches or more, the width of each pass, and
+// what srr_adaptive_last_spec_stats reports afterwards.
+struct SpecCall {
+  bool on = false;
+  int pass_spp_max = 0;
+  int64_t fill_paths = 0;
+  int32_t windows = 0;
+  int64_t traced = 0;
+};
+
+static SpecCall spec_call(const AdaptiveState& A, const srr_adaptive_params* a) {
+  SpecCall sc;
+  sc.pass_spp_max = A.pass_spp_max;
+  sc.fill_paths = A.fill_paths;
+  sc.on = A.pass_spp_max / a->batch_spp >= 2;
+  return sc;
+}
+
+// samples the pass at level n gives each of its n_act slots
+static int spec_width(const SpecCall& sc, const srr_adaptive_params* a, int64_t n_act, int n, int budget) {
+  if (!sc.on) return std::min(a->batch_spp, budget - n);
+  return adaptive_pass_width(n_act, n, budget, a->batch_spp, sc.pass_spp_max, sc.fill_paths);
+}
+
+// One window (s0, Wn) of the speculative pass (n, w) over the n_act rows of `slots`.
+static void spec_fold(srr_renderer* r, FrameSlot& F, const srr_adaptive_params* a, const int32_t* slots, int64_t n_act,
+                      int n, int w, int s0, int Wn, int budget, float* d_mean) {
+  AdaptiveState& A = r->adaptive;
+  AdaptiveSpecFold f{};
+  f.sample = F.sample.get();
+  f.active_slot = slots;
+  f.n_active = (int)n_act;
+  f.spp_w = Wn;
+  f.sums = r->acc.get();
+  f.mom = A.mom.get();
+  f.n = n;
+  f.w = w;
+  f.s0 = s0;
+  f.batch_spp = a->batch_spp;
+  f.min_spp = a->min_spp;
+  f.budget = budget;
+  f.rel_tol = a->rel_tol;
+  f.abs_eps = a->abs_eps;
+  f.keep = A.keep.get();
+  f.mean = d_mean;
+  f.count = A.count.get();
+  f.ctr = A.spec_ctr.get();
+  launch_adaptive_fold_spec(f, F.st);
+}
+
+// After the frame's sync: the call's stats without the samples traced past a stop, and
+// the record for srr_adaptive_last_spec_stats.  stopped (may be nullptr) += the slots that
+// stopped below the budget inside speculative passes.
+static void spec_frame_end(AdaptiveState& A, const SpecCall& sc, srr_adaptive_stats& s, int64_t* stopped) {
+  const int64_t discarded = sc.on ? (int64_t)A.spec_ctr_host.get()[kSpecDiscarded] : 0;
+  if (sc.on && stopped) *stopped += (int64_t)A.spec_ctr_host.get()[kSpecStopped];
+  s.paths = sc.traced - discarded;
+  A.spec_windows = sc.windows;
+  A.spec_traced = sc.traced;
+  A.spec_discarded = discarded;
+}
+
 // The pass loop: everything that can refuse the frame has been checked and every
 // buffer sized (render_adaptive), so from here on only HIP itself can fail.
 // win_cap: paths the slot's sample window holds.
@@ -827,16 +897,21 @@ static int adaptive_passes(srr_renderer* r, FrameSlot& F, const srr_params* p, c
   const int32_t* shard_pixels = identity ? nullptr : r->pixels.get();
   int32_t* n_dev = A.blk.get() + (A.cap + 255) / 256;
   srr_adaptive_stats s{};
+  SpecCall sc = spec_call(A, a);
   RCHK(hipMemsetAsync(F.ctr.get(), 0, kPathsCtrWords * sizeof(unsigned long long), st));
+  if (sc.on) RCHK(hipMemsetAsync(A.spec_ctr.get(), 0, kSpecWords * sizeof(unsigned long long), st));
   RCHK(hipEventRecord(F.ev_beg, st));
   int n = 0;     // samples every active pixel holds
   int cur = -1;  // the active lists are A.slot / A.pixel[cur]; -1: every slot, in order
   int64_t n_act = npix;
   bool first_launch = true;
   while (n_act > 0 && n < budget) {
-    const int w = std::min(a->batch_spp, budget - n), n_new = n + w;
-    // can a pixel retire after this pass?  (if none can, no flags, no compaction, no read-back)
+    const int w = spec_width(sc, a, n_act, n, budget), n_new = n + w;
+    // can a pixel retire after this pass?  (if none can, no flags, no compaction, no read-back:
+    // n_new is the last boundary of a speculative pass, so none of its boundaries asks the rule)
     const bool decide = n_new >= budget || (n_new >= a->min_spp && a->rel_tol > 0.f);
+    // several batches in one pass: the fold asks the rule at every batch boundary
+    const bool spec = w > a->batch_spp && decide;
     const int32_t* slots = cur < 0 ? nullptr : A.slot[cur].get();
     const int32_t* pixels = cur < 0 ? shard_pixels : A.pixel[cur].get();
     // the pass in sample windows that fit the slot's buffer (one, unless the frame is huge)
@@ -850,6 +925,11 @@ static int adaptive_passes(srr_renderer* r, FrameSlot& F, const srr_params* p, c
       if (launch_paths(r->view, pw, r->diffuse_only ? 0 : 1, st) != 0) {
         err = "k_paths refused the launch";  // (stack_cap was checked before the first pass)
         return SRR_EINVAL;
+      }
+      sc.windows += 1;
+      if (spec) {
+        spec_fold(r, F, a, slots, n_act, n, w, s0, Wn, budget, d_mean);
+        continue;
       }
       AdaptiveFold f{};
       f.sample = F.sample.get();
@@ -871,7 +951,7 @@ static int adaptive_passes(srr_renderer* r, FrameSlot& F, const srr_params* p, c
     }
     n = n_new;
     s.passes += 1;
-    s.paths += n_act * w;
+    sc.traced += n_act * w;
     if (n >= budget) break;  // the fold retired every active pixel at the budget
     if (!decide) continue;
     const int nxt = cur < 0 ? 0 : cur ^ 1;
@@ -885,14 +965,26 @@ static int adaptive_passes(srr_renderer* r, FrameSlot& F, const srr_params* p, c
       err = "adaptive compaction returned " + std::to_string(n_next) + " of " + std::to_string(n_act) + " pixels";
       return SRR_EIO;
     }
-    s.pixels_retired += n_act - n_next;
+    // (the slots that stop inside a speculative pass are counted by its folds: the pass that
+    // reaches the budget is followed by no compaction)
+    if (!spec) s.pixels_retired += n_act - n_next;
     n_act = n_next;
     cur = nxt;
   }
   // every slot retired in some pass's fold, which left its count in the state
   if (d_count)
     RCHK(hipMemcpyAsync(d_count, A.count.get(), (size_t)npix * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-  return adaptive_frame_end(F, s, stats, err);
+  if (sc.on)
+    RCHK(hipMemcpyAsync(A.spec_ctr_host.get(), A.spec_ctr.get(), kSpecWords * sizeof(unsigned long long),
+                        hipMemcpyDeviceToHost, st));
+  const int rc = adaptive_frame_end(F, s, nullptr, err);
+  if (rc < 0) return rc;
+  spec_frame_end(A, sc, s, &s.pixels_retired);
+  if (stats) {
+    s.struct_size = stats->struct_size;
+    *stats = s;
+  }
+  return 0;
 }
 
 // The pass loop of a resumed frame (include/srr_capi.h): the slots of the state hold
@@ -910,7 +1002,9 @@ static int adaptive_resume_passes(srr_renderer* r, FrameSlot& F, const srr_param
   const AdaptiveRule rule{budget, a->min_spp, a->rel_tol, a->abs_eps};
   int32_t* lvl = A.lvl.get();
   srr_adaptive_stats s{};
+  SpecCall sc = spec_call(A, a);
   RCHK(hipMemsetAsync(F.ctr.get(), 0, kPathsCtrWords * sizeof(unsigned long long), st));
+  if (sc.on) RCHK(hipMemsetAsync(A.spec_ctr.get(), 0, kSpecWords * sizeof(unsigned long long), st));
   RCHK(hipEventRecord(F.ev_beg, st));
   bool first_launch = true;
   int prev_level = -1;
@@ -931,7 +1025,10 @@ static int adaptive_resume_passes(srr_renderer* r, FrameSlot& F, const srr_param
       return SRR_EIO;
     }
     prev_level = n;
-    const int w = std::min(a->batch_spp, budget - n), n_new = n + w;
+    const int w = spec_width(sc, a, n_act, n, budget), n_new = n + w;
+    // several batches in one pass: the fold asks the rule at every batch boundary, and the
+    // next k_adaptive_level finds the slots that stopped retired, from the same moments
+    const bool spec = w > a->batch_spp;
     int W = (int)std::min<int64_t>(window_samples(ps, n_act, w), (int64_t)(win_cap / (size_t)n_act));
     if (W < w && W >= 16) W &= ~3;
     for (int s0 = 0; s0 < w; s0 += W) {
@@ -942,6 +1039,11 @@ static int adaptive_resume_passes(srr_renderer* r, FrameSlot& F, const srr_param
       if (launch_paths(r->view, pw, r->diffuse_only ? 0 : 1, st) != 0) {
         err = "k_paths refused the launch";  // (stack_cap was checked before the first pass)
         return SRR_EINVAL;
+      }
+      sc.windows += 1;
+      if (spec) {
+        spec_fold(r, F, a, A.slot[0].get(), n_act, n, w, s0, Wn, budget, d_mean);
+        continue;
       }
       AdaptiveFold f{};
       f.sample = F.sample.get();
@@ -964,12 +1066,16 @@ static int adaptive_resume_passes(srr_renderer* r, FrameSlot& F, const srr_param
       launch_adaptive_fold(f, st);
     }
     s.passes += 1;
-    s.paths += n_act * w;
+    sc.traced += n_act * w;
   }
   launch_adaptive_finish((int)npix, r->acc.get(), A.count.get(), budget, d_mean, d_count, lvl, st);
   RCHK(hipMemcpyAsync(A.lvl_host.get(), lvl, kLvlWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (sc.on)
+    RCHK(hipMemcpyAsync(A.spec_ctr_host.get(), A.spec_ctr.get(), kSpecWords * sizeof(unsigned long long),
+                        hipMemcpyDeviceToHost, st));
   const int rc = adaptive_frame_end(F, s, nullptr, err);
   if (rc < 0) return rc;
+  spec_frame_end(A, sc, s, nullptr);
   s.pixels_retired = A.lvl_host.get()[kLvlBelow];
   if (stats) {
     s.struct_size = stats->struct_size;
@@ -990,6 +1096,7 @@ int render_adaptive(srr_renderer* r, const srr_params* p, const srr_adaptive_par
   // the state is this frame's from here on, and valid once it succeeds
   r->adaptive.valid_npix = 0;
   r->adaptive.sums_valid = false;
+  r->adaptive.spec_windows = -1;  // (srr_adaptive_last_spec_stats: none until this call succeeds)
   RCHK(hipSetDevice(r->device));
   // the rgb sums of the pass loop live in the progressive accumulator: whatever it
   // held is gone, and what this frame leaves (pixels of different sample counts) is
@@ -1016,7 +1123,15 @@ int render_adaptive(srr_renderer* r, const srr_params* p, const srr_adaptive_par
     return SRR_EINVAL;
   }
   // the first pass has the most paths: its window serves every later one
-  const size_t win_cap = (size_t)npix * window_samples(ps, npix, std::min(a->batch_spp, p->spp));
+  size_t win_cap = (size_t)npix * window_samples(ps, npix, std::min(a->batch_spp, p->spp));
+  if (const SpecCall sc = spec_call(r->adaptive, a); sc.on) {
+    // the widest pass the schedule can produce: n_act slots get at most w_max samples each and,
+    // beyond one batch, at most fill_paths paths together (a pass that still does not fit
+    // is cut into sample windows, like any other)
+    const int w_max = (int)std::min<int64_t>((int64_t)(sc.pass_spp_max / a->batch_spp) * a->batch_spp, p->spp);
+    const size_t fill = (size_t)(sc.fill_paths ? sc.fill_paths : kAdaptiveFillDefault);
+    win_cap = std::max(win_cap, std::min((size_t)npix * window_samples(ps, npix, w_max), fill));
+  }
   if (win_cap >= ((size_t)1 << 31)) {
     err = "frame too large for one sample window (npix >= 2^31)";
     return SRR_EINVAL;

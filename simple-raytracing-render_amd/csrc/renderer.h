@@ -102,6 +102,14 @@ struct AdaptiveState {
   DeviceMem<uint8_t> keep;      // [active row] survives the pass
   DeviceMem<int32_t> blk;       // compaction scratch: per-block counts / offsets, then [nb] the new active count
   PinnedMem<int32_t> n_host;    // mirror of the new active count
+  // speculative passes (srr_adaptive_speculate): the setting, which outlives the buffers,
+  // and what srr_adaptive_last_spec_stats reports of the most recent frame (windows < 0: none yet)
+  int pass_spp_max = 0;
+  int64_t fill_paths = 0;
+  int32_t spec_windows = -1;
+  int64_t spec_traced = 0, spec_discarded = 0;
+  DeviceMem<unsigned long long> spec_ctr;       // kernels.h kSpec* words of the frame's speculative folds
+  PinnedMem<unsigned long long> spec_ctr_host;  // their mirror
 };
 
 // Buffers of srr_render_aov (renderer.cpp render_aov): a stream, a pixel list, Sobol

@@ -60,6 +60,14 @@ class AdaptiveStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
 
 
+class AdaptiveSpecStats(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("windows", ctypes.c_int32), ("paths_traced", ctypes.c_int64),
+                ("paths_discarded", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
 class DenoiseParams(ctypes.Structure):
     """srr_denoise_params; ``DenoiseParams.defaults()`` is srr_denoise_defaults."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("iterations", ctypes.c_int), ("k_c", ctypes.c_float),
@@ -152,6 +160,12 @@ def lib():
             L.srr_render_adaptive_resume_host.argtypes = L.srr_render_adaptive_host.argtypes
             L.srr_adaptive_state_get.argtypes = [vp, vp, vp, vp, i64p]
             L.srr_adaptive_state_set.argtypes = [vp, ctypes.POINTER(Params), vp, vp, vp, ctypes.c_int64]
+        if hasattr(L, "srr_adaptive_speculate"):  # (as above)
+            L.srr_adaptive_speculate.argtypes = [vp, ip, ctypes.c_int64]
+            L.srr_adaptive_last_spec_stats.argtypes = [vp, ctypes.POINTER(AdaptiveSpecStats)]
+            L.srr_adaptive_pass_width.argtypes = [ctypes.c_int64, ip, ip, ip, ip, ctypes.c_int64]
+            L.srr_adaptive_fill_default.argtypes = []
+            L.srr_adaptive_fill_default.restype = ctypes.c_int64
         if hasattr(L, "srr_denoise"):  # (as above)
             dpp = ctypes.POINTER(DenoiseParams)
             L.srr_render_aov.argtypes = [vp, ctypes.POINTER(Params), ip, vp, vp, vp]
@@ -367,6 +381,20 @@ class Renderer:
                                                 ctypes.c_void_p(d_count_ptr or None), ctypes.byref(st)))
         return st.as_dict()
 
+    def adaptive_speculate(self, pass_spp_max: int, fill_paths: int = 0) -> None:
+        """Speculative passes (srr_adaptive_speculate) for the adaptive and resume calls
+        that follow on this renderer: a pass may give a slot up to pass_spp_max samples,
+        aiming at fill_paths paths (0: the library's default); pass_spp_max = 0 switches
+        it off.  The frames' outputs do not change, only how many passes they take."""
+        _check(lib().srr_adaptive_speculate(self.h, int(pass_spp_max), int(fill_paths)))
+
+    def adaptive_spec_stats(self) -> dict:
+        """dict(windows, paths_traced, paths_discarded) of the most recent adaptive or
+        resume call on this renderer (srr_adaptive_last_spec_stats)."""
+        st = AdaptiveSpecStats(ctypes.sizeof(AdaptiveSpecStats))
+        _check(lib().srr_adaptive_last_spec_stats(self.h, ctypes.byref(st)))
+        return st.as_dict()
+
     def adaptive_state(self) -> dict:
         """The adaptive state (srr_adaptive_state_get): dict(sums[n,3], mom[n,2] (s1, s2),
         count[n]) in shard-pixel order."""
@@ -445,6 +473,17 @@ class Renderer:
         st = Stats()
         _check(lib().srr_render_wait(self.h, ctypes.c_int64(ticket), ctypes.byref(st)))
         return st.as_dict()
+
+
+def adaptive_pass_width(n_active, n, budget, batch_spp, pass_spp_max, fill_paths=0) -> int:
+    """Samples per slot of the next speculative pass (srr_adaptive_pass_width; host, no GPU)."""
+    return _check(lib().srr_adaptive_pass_width(int(n_active), int(n), int(budget), int(batch_spp),
+                                                int(pass_spp_max), int(fill_paths)))
+
+
+def adaptive_fill_default() -> int:
+    """The fill_paths that 0 stands for (srr_adaptive_fill_default)."""
+    return int(lib().srr_adaptive_fill_default())
 
 
 def adaptive_converged(n, s1, s2, rel_tol, abs_eps) -> bool:

@@ -17,6 +17,8 @@ srr_render_adaptive_resume): step(spp) raises the per-pixel budget by spp, pixel
 on their own once they meet the tolerance, ``count`` holds each pixel's samples, and
 the saved state is the adaptive state (sums, moments, counts).  A pixel that holds
 n_i samples is bitwise the fixed-spp frame at n_i, however the budget was stepped.
+``pass_spp_max`` / ``fill_paths`` switch the renderer's speculative passes on
+(srr_adaptive_speculate): the same frames in fewer passes.
 ``denoise`` may then also be a capi.DenoiseVarParams: step() returns srr_denoise_var
 of the mean, the variance of the pixels' mean luminance and the AOVs.
 """
@@ -32,7 +34,8 @@ from . import capi
 
 class Progressive:
     def __init__(self, renderer: "capi.Renderer", nx: int, ny: int, max_depth: int = 50, flags: int = 0,
-                 denoise=None, aov_spp: int = 16, adaptive=None, **params):
+                 denoise=None, aov_spp: int = 16, adaptive=None, pass_spp_max: int = 0, fill_paths: int = 0,
+                 **params):
         self.r = renderer
         self.nx, self.ny, self.max_depth = nx, ny, max_depth
         self.flags = flags  # engine flags (e.g. capi.FLAG_WAVEFRONT)
@@ -44,6 +47,11 @@ class Progressive:
         if adaptive is True:
             adaptive = capi.AdaptiveParams(ctypes.sizeof(capi.AdaptiveParams), 16, 16, 0.02, 1e-3)
         self.adaptive = adaptive or None
+        # adaptive: speculative passes (capi.Renderer.adaptive_speculate) for every step; the frame does not change
+        if pass_spp_max or fill_paths:
+            if self.adaptive is None:
+                raise capi.SrrError("pass_spp_max and fill_paths are an adaptive frame's: set adaptive")
+            renderer.adaptive_speculate(pass_spp_max, fill_paths)
         self.count = None     # adaptive: samples per pixel
         self._resumable = False  # adaptive: the renderer holds this frame's state
         if isinstance(denoise, capi.DenoiseVarParams) and self.adaptive is None:

@@ -7,8 +7,11 @@ format of Raytracing_n.cpp:850-886).
 
     python -m srr.render_main [--sceneid 2] [--nx 1000] [--ny 1000] [--ns 50] [--max-depth 50] [--out out.ppm]
                               [--gpus N]   (srr_renderer_create_multi: one RCCL gather at frame end)
-                              [--adaptive REL_TOL [--batch-spp 16] [--min-spp 16] [--count-map FILE]]
-                                           (srr_render_adaptive: --ns is the per-pixel budget; one GPU)
+                              [--adaptive REL_TOL [--batch-spp 16] [--min-spp 16] [--count-map FILE]
+                                                  [--adaptive-pass-spp N [--adaptive-fill P]]]
+                                           (srr_render_adaptive: --ns is the per-pixel budget; one GPU;
+                                            --adaptive-pass-spp: speculative passes of up to N samples,
+                                            srr_adaptive_speculate -- the same image in fewer passes)
                               [--denoise [--aov-spp N] [--aov-out PREFIX]]
                                            (srr_denoise over the first-hit AOVs of srr_render_aov; one GPU;
                                             --out is the tone-mapped denoised frame; PREFIX_albedo.png,
@@ -56,6 +59,10 @@ def parse(argv=None):
     ap.add_argument("--min-spp", type=int, default=16, help="adaptive: no pixel stops with fewer samples")
     ap.add_argument("--count-map", default=None, metavar="FILE",
                     help="adaptive: PNG of the samples each pixel took, as grey level count / ns")
+    ap.add_argument("--adaptive-pass-spp", type=int, default=0, metavar="N",
+                    help="adaptive: speculative passes of up to N samples per pixel (0: off); the image does not change")
+    ap.add_argument("--adaptive-fill", type=int, default=0, metavar="P",
+                    help="adaptive: the pass size, in paths, that speculative passes aim at (0: the library's default)")
     ap.add_argument("--denoise", action="store_true",
                     help="filter the frame with the a-trous denoiser over its first-hit AOVs (one GPU)")
     ap.add_argument("--denoise-var", action="store_true",
@@ -103,6 +110,11 @@ def main(argv=None) -> int:
     if (a.denoise or a.aov_out) and a.gpus != 1:
         print("--denoise and --aov-out need one GPU", file=sys.stderr)
         return 2
+    if a.adaptive is None and (a.adaptive_pass_spp or a.adaptive_fill):
+        print("--adaptive-pass-spp and --adaptive-fill need --adaptive", file=sys.stderr)
+        return 2
+    if a.adaptive_pass_spp or a.adaptive_fill:
+        r.adaptive_speculate(a.adaptive_pass_spp, a.adaptive_fill)
     t0 = time.perf_counter()
     if a.adaptive is not None:
         out = r.render_adaptive(a.nx, a.ny, a.ns, a.max_depth, batch_spp=a.batch_spp, min_spp=a.min_spp,
@@ -133,8 +145,10 @@ def main(argv=None) -> int:
     capi.write_ppm(a.out, a.nx, a.ny, out["img8"])
     st = out["stats"]
     if a.adaptive is not None:
+        sp = r.adaptive_spec_stats()
         print(f"adaptive: {st['paths']} of {a.nx * a.ny * a.ns} samples in {st['passes']} passes, "
-              f"{st['pixels_retired']} pixels stopped early", file=sys.stderr)
+              f"{st['pixels_retired']} pixels stopped early; {sp['paths_traced']} traced, "
+              f"{sp['paths_discarded']} discarded", file=sys.stderr)
         if a.count_map:
             capi.write_png(a.count_map, a.nx, a.ny, count_map(out["count"], a.ns))
     print(f"{SCENE_NAMES[a.sceneid]}: {a.nx}x{a.ny}x{a.ns}, {st['world_rays']} world rays, "
