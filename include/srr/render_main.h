@@ -52,6 +52,9 @@
  *   --aov-out PREFIX             write PREFIX_albedo.png (255.99 * albedo, clamped),
  *                                PREFIX_normal.png (255.99 * (n / 2 + 1/2)) and
  *                                PREFIX_depth.png (grey 255 * depth / max depth)
+ *   --aov-through-specular       one GPU, with --denoise, --denoise-var or --aov-out:
+ *                                their AOVs are those of the first hit that is neither
+ *                                metal nor dielectric (srr_render_aov_through)
  * Differences, all forced by the reference: its render threads race on shared
  * state and its pixel mapping scrambles non-square frames (Q12);
  * srr renders every (pixel, sample) path with its per-path seed.  Exit codes:
@@ -94,12 +97,14 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
   bool denoise = false, denoise_var = false;
   int aov_spp = 0;  // 0: min(ns, 16)
   std::string aov_out;
+  bool aov_through = false;  // --aov-through-specular
   auto usage = [&]() {
     std::fprintf(stderr, "usage: %s [--sceneid N | --scene NAME] [--nx N] [--ny N] [--ns N] [--max-depth N] "
                          "[--device N] [--gpus N | --devices a,b,..] [--tile N] [--out FILE] [--dry-run] "
                          "[--adaptive REL_TOL [--batch-spp N] [--min-spp N] [--count-map FILE] "
                          "[--adaptive-pass-spp N [--adaptive-fill P]]] "
-                         "[--denoise | --denoise-var] [--aov-spp N] [--aov-out PREFIX]\nscenes:",
+                         "[--denoise | --denoise-var] [--aov-spp N] [--aov-out PREFIX] "
+                         "[--aov-through-specular]\nscenes:",
                  argv[0]);
     for (int k = 0; k < n_scenes; ++k) std::fprintf(stderr, " %d:%s", scenes[k].sceneid, scenes[k].name);
     std::fprintf(stderr, "\n");
@@ -140,6 +145,7 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
     else if (a == "--denoise-var") denoise_var = true;
     else if (a == "--aov-spp") ok = num(aov_spp) && aov_spp >= 1;
     else if (a == "--aov-out" && i + 1 < argc) aov_out = argv[++i];
+    else if (a == "--aov-through-specular") aov_through = true;
     else ok = false;
     if (!ok) return usage();
   }
@@ -151,6 +157,8 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
   if (adaptive < 0 && (pass_spp || fill_paths)) return usage();
   if (denoise && denoise_var) return usage();
   if ((denoise || denoise_var || !aov_out.empty()) && (gpus > 1 || !devices.empty())) return usage();  // one GPU
+  if (aov_through && !(denoise || denoise_var || !aov_out.empty())) return usage();
+  if (aov_through && (gpus > 1 || !devices.empty())) return usage();  // one GPU
   if (aov_spp == 0) aov_spp = ns < 16 ? ns : 16;
   const char* scene_name = text_path.empty() ? e->name : text_path.c_str();
 
@@ -241,8 +249,10 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
     depth.resize(npix);
     srr_params pa = p;
     pa.spp = aov_spp;
-    rc = srr_render_aov_host(r, &pa, SRR_AOV_ALBEDO | SRR_AOV_NORMAL | SRR_AOV_DEPTH, albedo.data(), normal.data(),
-                             depth.data());
+    const int which = SRR_AOV_ALBEDO | SRR_AOV_NORMAL | SRR_AOV_DEPTH;
+    rc = aov_through
+             ? srr_render_aov_through_host(r, &pa, which, albedo.data(), normal.data(), depth.data(), nullptr)
+             : srr_render_aov_host(r, &pa, which, albedo.data(), normal.data(), depth.data());
   }
   if (rc == 0 && denoise_var) {
     srr_denoise_var_params dp{};

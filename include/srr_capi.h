@@ -488,6 +488,65 @@ int srr_render_aov(srr_renderer* r, const srr_params* p, int which, float* d_alb
 /* The same with host buffers. */
 int srr_render_aov_host(srr_renderer* r, const srr_params* p, int which, float* albedo, float* normal, float* depth);
 
+/* ---- First-diffuse-hit feature buffers: the AOVs above, traced through mirrors and
+ * glass to the first hit that is neither metal nor dielectric (what OIDN, OptiX and
+ * SVGF call guides "at the first non-specular hit").  No reference counterpart.
+ * Chain.  For every shard pixel and sample the path starts as that sample of
+ * srr_render_device starts (per-path seed, Sobol point, lens draw, time) and keeps that
+ * path's RNG streams from then on.  depth = 0, ray r_0 = the primary ray; then, as
+ * color() (Raytracing_n.cpp:56-105):
+ *   1. world->hit(r_depth, 0.001, FLT_MAX); a constant_medium draws inside hit what it
+ *      draws in the beauty frame.  o_j is the origin of r_j, p_j its hit point.
+ *   2. While the hit's material is metal or dielectric AND depth < p->max_depth: a_depth
+ *      = the metal's colour or (1, 1, 1); the material's scatter draws exactly what it
+ *      draws in the beauty frame (metal: random_in_unit_sphere; dielectric: one drand)
+ *      and gives r_(depth+1), time 0; depth += 1; step 1 again.
+ *   3. Any other result is TERMINAL, k = depth bounces behind it: a miss, a null
+ *      material, a non-specular material (isotropic is not followed: a medium is a
+ *      terminal hit), or a metal / dielectric reached with depth == p->max_depth.
+ * Per sample:
+ *   albedo  e = the terminal hit's albedo by srr_render_aov's rule, but (0, 0, 0) for a
+ *           metal or dielectric at the depth limit (color() returns emitted() there);
+ *           albedo = a_0 * (a_1 * ( ... (a_(k-1) * e))), folded back to front,
+ *           componentwise in float32 -- the order in which the recursion returns.
+ *   normal  the terminal hit's normal as color() sees it (world space, not reflected
+ *           back); (0, 0, 0) for a miss, a constant_medium and a chain stopped at the
+ *           depth limit.
+ *   depth   d_j = sqrtf(dot(p_j - o_j, p_j - o_j)) per segment, summed front to back in
+ *           float32, ((d_0 + d_1) + d_2) + ... + d_k; 0 when the last segment misses.
+ * De_nan, the per-pixel fold in sample order and sum * (float)(1.0 / (float)spp) are
+ * exactly srr_render_aov's.  Consequences: on a scene without metal and dielectric the
+ * three buffers are bitwise srr_render_aov's; a buffer is a pure function of (scene,
+ * pixel, sample range, max_depth), whatever p->batch_paths; and the albedo is, bit for
+ * bit, the beauty image of the scene's "specular twin" (every material but metal and
+ * dielectric replaced by a two-sided diffuse_light of its albedo) at the same max_depth.
+ * stats (may be NULL; set stats->struct_size = sizeof(srr_aov_stats) before the call):
+ * paths = primary rays; world_rays = world->hit calls, primary rays included;
+ * chained_paths = paths that took at least one specular step (first hit metal or
+ * dielectric, max_depth > 0); longest_chain = the most steps any path took.
+ * Buffers, `which`, p->max_depth (0..64) and p->batch_paths as for srr_render_aov; with
+ * batch_paths = 0 the batch is min(2^20, 256 MiB / (172 + 12 * max_depth) B) paths, so
+ * that the per-path state of this call's batch (172 B + 12 B per bounce of max_depth)
+ * stays within 256 MiB; the 160 B per path of it that are srr_render_aov's buffers are
+ * shared with that call and keep the largest batch either has used.  Synchronous.
+ * SRR_EINVAL, before
+ * anything is allocated or enqueued, in every case srr_render_aov refuses, and for a
+ * stats->struct_size smaller than the struct.  Like srr_render_aov the call uses buffers
+ * and a stream of its own and leaves running sums, the held pixel list, adaptive state
+ * and async frames untouched. */
+typedef struct srr_aov_stats {
+  uint32_t struct_size;   /* sizeof(srr_aov_stats) of the caller, set before the call */
+  int32_t  longest_chain; /* most specular bounces any path followed */
+  int64_t  paths;         /* primary rays traced */
+  int64_t  world_rays;    /* world->hit calls, primary rays included */
+  int64_t  chained_paths; /* paths whose first hit was metal or dielectric (and was followed) */
+} srr_aov_stats;
+int srr_render_aov_through(srr_renderer* r, const srr_params* p, int which, float* d_albedo, float* d_normal,
+                           float* d_depth, srr_aov_stats* stats /* may be NULL */);
+/* The same with host buffers. */
+int srr_render_aov_through_host(srr_renderer* r, const srr_params* p, int which, float* albedo, float* normal,
+                                float* depth, srr_aov_stats* stats /* may be NULL */);
+
 /* ---- Feature-guided denoiser: an edge-avoiding a-trous wavelet filter (Dammertz,
  * Sewtz, Hanika, Lensch 2010) over a colour image and the AOVs above.  Nothing of it
  * is the reference's.  Inputs and the output are whole images in PPM order on HIP

@@ -716,6 +716,17 @@ int srr_render_aov(srr_renderer* r, const srr_params* p, int which, float* d_alb
   return rc < 0 ? fail(rc, err) : 0;
 }
 
+// the staged images d = albedo [3 npix], normal [3 npix], depth [npix] to the host buffers asked for
+static int aov_copy_out(int which, const float* d, int64_t npix, float* albedo, float* normal, float* depth) {
+  hipError_t e = hipSuccess;
+  if (which & SRR_AOV_ALBEDO) e = hipMemcpy(albedo, d, 3 * npix * sizeof(float), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && (which & SRR_AOV_NORMAL))
+    e = hipMemcpy(normal, d + 3 * npix, 3 * npix * sizeof(float), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && (which & SRR_AOV_DEPTH))
+    e = hipMemcpy(depth, d + 6 * npix, npix * sizeof(float), hipMemcpyDeviceToHost);
+  return e == hipSuccess ? 0 : fail(SRR_EIO, hipGetErrorString(e));
+}
+
 int srr_render_aov_host(srr_renderer* r, const srr_params* p, int which, float* albedo, float* normal, float* depth) {
   if (const int rc = aov_check(r, p, which, albedo, normal, depth)) return rc;
   const int64_t npix = srr_shard_pixels(p, nullptr);
@@ -726,15 +737,49 @@ int srr_render_aov_host(srr_renderer* r, const srr_params* p, int which, float* 
   MEMCHK(buf.grow(7 * npix), SRR_EIO, "AOV staging images");
   float* const d = buf.get();
   int rc = srr_render_aov(r, p, which, d, d + 3 * npix, d + 6 * npix);
-  if (rc == 0) {
-    hipError_t e = hipSuccess;
-    if (which & SRR_AOV_ALBEDO) e = hipMemcpy(albedo, d, 3 * npix * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && (which & SRR_AOV_NORMAL))
-      e = hipMemcpy(normal, d + 3 * npix, 3 * npix * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && (which & SRR_AOV_DEPTH))
-      e = hipMemcpy(depth, d + 6 * npix, npix * sizeof(float), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = fail(SRR_EIO, hipGetErrorString(e));
+  if (rc == 0) rc = aov_copy_out(which, d, npix, albedo, normal, depth);
+  return rc;
+}
+
+// ---- through-specular AOVs: srr_render_aov's checks, then the stats struct's
+static int aov_through_check(const srr_renderer* r, const srr_params* p, int which, const void* a, const void* n,
+                             const void* z, const srr_aov_stats* stats) {
+  if (const int rc = aov_check(r, p, which, a, n, z)) return rc;
+  if (stats && stats->struct_size < sizeof(srr_aov_stats))
+    return fail(SRR_EINVAL, "srr_render_aov_through: stats->struct_size is smaller than srr_aov_stats");
+  return 0;
+}
+
+int srr_render_aov_through(srr_renderer* r, const srr_params* p, int which, float* d_albedo, float* d_normal,
+                           float* d_depth, srr_aov_stats* stats) {
+  // every refusal comes before anything is allocated or enqueued
+  if (const int rc = aov_through_check(r, p, which, d_albedo, d_normal, d_depth, stats)) return rc;
+  const int64_t npix = srr_shard_pixels(p, nullptr);
+  if (npix < 0) return (int)npix;
+  if (npix == 0) {
+    if (stats) *stats = srr_aov_stats{stats->struct_size, 0, 0, 0, 0};
+    return 0;
   }
+  std::vector<int32_t> pix(npix);
+  srr_shard_pixels(p, pix.data());
+  std::string err;
+  const int rc = render_aov_through(r, p, pix.data(), npix, (which & SRR_AOV_ALBEDO) ? d_albedo : nullptr,
+                                    (which & SRR_AOV_NORMAL) ? d_normal : nullptr,
+                                    (which & SRR_AOV_DEPTH) ? d_depth : nullptr, stats, err);
+  return rc < 0 ? fail(rc, err) : 0;
+}
+
+int srr_render_aov_through_host(srr_renderer* r, const srr_params* p, int which, float* albedo, float* normal,
+                                float* depth, srr_aov_stats* stats) {
+  if (const int rc = aov_through_check(r, p, which, albedo, normal, depth, stats)) return rc;
+  const int64_t npix = srr_shard_pixels(p, nullptr);
+  if (npix < 0) return (int)npix;
+  DeviceMem<float> buf;  // albedo [3 npix], normal [3 npix], depth [npix]
+  HIPCHK(hipSetDevice(r->device));
+  MEMCHK(buf.grow(7 * npix), SRR_EIO, "AOV staging images");
+  float* const d = buf.get();
+  int rc = srr_render_aov_through(r, p, which, d, d + 3 * npix, d + 6 * npix, stats);
+  if (rc == 0 && npix > 0) rc = aov_copy_out(which, d, npix, albedo, normal, depth);
   return rc;
 }
 

@@ -514,6 +514,24 @@ struct AovFold {
   float* depth;
 };
 void launch_aov_fold(const AovFold& A, hipStream_t st);
+// ---- through-specular AOVs (srr_render_aov_through, renderer.cpp render_aov_through)
+// One bounce after launch_trace over the *count paths of `active`: a path whose hit is
+// metal or dielectric below max_depth takes that specular step (record, running depth,
+// scatter<FAM_SPEC>, next ray, depth + 1) and is appended to next / *next_count; every
+// other path ends and leaves val[2p], val[2p + 1] as launch_aov_eval does, the albedo
+// folded back to front through the path's metal records.  max_n >= *count sizes the grid.
+struct AovChain {
+  const int32_t* active;
+  const int32_t* count;
+  int32_t* next;
+  int32_t* next_count;  // zeroed by the caller
+  int max_depth;
+  int cap;              // paths of the call's batch: chain's size, rec's stride
+  int2* chain;          // [cap] (running depth as float bits, metal records written)
+  float* rec;           // [max_depth][cap][3] metal colours, in bounce order per path
+  float4* val;          // [>= cap][2]
+};
+void launch_aov_chain(const SceneView& S, const PathState& P, const AovChain& C, int max_n, hipStream_t st);
 // image[index[i]] = packed[i] (float3 per pixel) for i < n: multi-device frame assembly
 void launch_scatter_pixels(const float* packed, const int32_t* index, int64_t n, float* image, hipStream_t st);
 

@@ -2655,49 +2655,49 @@ __global__ void __launch_bounds__(256) k_record(SceneView S, PathState P, const 
   }
 }
 
-// First-hit AOVs (srr_render_aov, include/srr_capi.h).  One thread per primary ray
-// of a batch that k_raygen laid out pixel-major in slots 0 .. n-1 and k_trace /
-// k_record resolved: val[2p] = (albedo.rgb, depth), val[2p + 1] = (normal.xyz, 0),
-// de_nan'd.  k_record writes no record for a null material, so that hit's record
-// is recomputed here with the same world_record.
-__global__ void __launch_bounds__(256) k_aov_eval(SceneView S, PathState P, int n, float4* __restrict__ val) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n) return;
-  const int4 hw = ntl(&P.hit_w[p]);
-  V3 alb = v3(0.f), nrm = v3(0.f);
-  float depth = 0.f;
-  if (hw.x >= 0) {
-    const float4 ro = ntl(&P.ray_o[p]);
-    V3 hp, hn;
-    float hu, hv;
-    if (hw.w >= 0) {
-      const float4 a = ntl(&P.hit_p[p]), b = ntl(&P.hit_n[p]);
-      hp = v3(a.x, a.y, a.z);
-      hn = v3(b.x, b.y, b.z);
-      hu = a.w;
-      hv = b.w;
-    } else {
-      const float4 rdv = ntl(&P.ray_d[p]);
-      const Ray r{v3(ro.x, ro.y, ro.z), v3(rdv.x, rdv.y, rdv.z), ro.w};
-      const HitRec h = world_record(S, r, WorldHit{hw.x, hw.y, __int_as_float(hw.z)});
-      hp = h.p;
-      hn = h.n;
-      hu = h.u;
-      hv = h.v;
-    }
-    DObj ob = S.objs[hw.x];  // the primitive that was hit (hit_material)
-    if (ob.kind == OBJ_OBVH) ob = S.objs[hw.y];
-    else if (ob.kind == OBJ_SGROUP) ob = S.objs[S.sg_items[hw.y].obj];
-    if (ob.kind != OBJ_MEDIUM) nrm = hn;
-    const V3 d = hp - v3(ro.x, ro.y, ro.z);
-    depth = rsqrt_exact(dot(d, d));
-    if (hw.w >= 0) {
-      const DMat M = S.mats[hw.w];
-      if (M.kind == MAT_METAL) alb = v3(M.p[0], M.p[1], M.p[2]);
-      else if (M.kind == MAT_DIELECTRIC) alb = v3(1.f);
-      else alb = tex_value(S, M.tex, hu, hv, hp);
-    }
+// The AOV values of the traced ray of path p (hit hw, ray origin ro), before de_nan:
+// albedo, normal and segment length by srr_render_aov's rules (include/srr_capi.h).
+// k_record writes no record for a null material, so that hit's record is recomputed
+// here with the same world_record.
+SRR_D void aov_hit_values(const SceneView& S, const PathState& P, int p, int4 hw, float4 ro, V3& alb, V3& nrm,
+                          float& depth) {
+  alb = v3(0.f);
+  nrm = v3(0.f);
+  depth = 0.f;
+  if (hw.x < 0) return;
+  V3 hp, hn;
+  float hu, hv;
+  if (hw.w >= 0) {
+    const float4 a = ntl(&P.hit_p[p]), b = ntl(&P.hit_n[p]);
+    hp = v3(a.x, a.y, a.z);
+    hn = v3(b.x, b.y, b.z);
+    hu = a.w;
+    hv = b.w;
+  } else {
+    const float4 rdv = ntl(&P.ray_d[p]);
+    const Ray r{v3(ro.x, ro.y, ro.z), v3(rdv.x, rdv.y, rdv.z), ro.w};
+    const HitRec h = world_record(S, r, WorldHit{hw.x, hw.y, __int_as_float(hw.z)});
+    hp = h.p;
+    hn = h.n;
+    hu = h.u;
+    hv = h.v;
   }
+  DObj ob = S.objs[hw.x];  // the primitive that was hit (hit_material)
+  if (ob.kind == OBJ_OBVH) ob = S.objs[hw.y];
+  else if (ob.kind == OBJ_SGROUP) ob = S.objs[S.sg_items[hw.y].obj];
+  if (ob.kind != OBJ_MEDIUM) nrm = hn;
+  const V3 d = hp - v3(ro.x, ro.y, ro.z);
+  depth = rsqrt_exact(dot(d, d));
+  if (hw.w >= 0) {
+    const DMat M = S.mats[hw.w];
+    if (M.kind == MAT_METAL) alb = v3(M.p[0], M.p[1], M.p[2]);
+    else if (M.kind == MAT_DIELECTRIC) alb = v3(1.f);
+    else alb = tex_value(S, M.tex, hu, hv, hp);
+  }
+}
+
+// val[2p] = (albedo.rgb, depth), val[2p + 1] = (normal.xyz, 0) of path p, de_nan'd
+SRR_D void aov_store(float4* __restrict__ val, int p, V3 alb, V3 nrm, float depth) {
   // de_nan (Raytracing_n.cpp:47-53)
   if (!(alb.x == alb.x)) alb.x = 0;
   if (!(alb.y == alb.y)) alb.y = 0;
@@ -2708,6 +2708,18 @@ __global__ void __launch_bounds__(256) k_aov_eval(SceneView S, PathState P, int 
   if (!(depth == depth)) depth = 0;
   nts(&val[2 * (size_t)p], make_float4(alb.x, alb.y, alb.z, depth));
   nts(&val[2 * (size_t)p + 1], make_float4(nrm.x, nrm.y, nrm.z, 0.f));
+}
+
+// First-hit AOVs (srr_render_aov, include/srr_capi.h).  One thread per primary ray
+// of a batch that k_raygen laid out pixel-major in slots 0 .. n-1 and k_trace /
+// k_record resolved.
+__global__ void __launch_bounds__(256) k_aov_eval(SceneView S, PathState P, int n, float4* __restrict__ val) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  V3 alb, nrm;
+  float depth;
+  aov_hit_values(S, P, p, ntl(&P.hit_w[p]), ntl(&P.ray_o[p]), alb, nrm, depth);
+  aov_store(val, p, alb, nrm, depth);
 }
 
 // The AOV fold: thread (pixel lp, word c of the pixel's 8) adds the batch's spp_b
@@ -2961,6 +2973,81 @@ SRR_D bool shade_one(const SceneView& S, const PathState& P, int p, int max_dept
   nts(&P.depth[p], depth + 1);
   nts(&P.spec[p], spec);
   return true;
+}
+
+// One bounce of the through-specular AOVs (srr_render_aov_through, include/srr_capi.h):
+// one thread per ACTIVE path of the bounce that k_trace / k_record just resolved.  A
+// metal or dielectric hit below the depth limit is a specular step of color(): a metal's
+// colour goes to the path's next record C.rec[k * C.cap + p] (a dielectric's (1, 1, 1)
+// needs none: 1 * x is x), the segment length is added to the running depth, and
+// scatter<FAM_SPEC> draws what the beauty frame draws and leaves the next ray, as
+// shade_one does; the path enters the next bounce's list, one atomic per wave (append).
+// Any other hit ends the path: its values are those of aov_hit_values -- albedo and
+// normal (0, 0, 0) for a specular hit at the depth limit, whose emitted() is 0 -- the
+// albedo folded through the records back to front (finish_path's order), the depth the
+// running sum plus this segment, 0 after a miss.  C.chain[p] = (running depth bits,
+// records written), not read at depth 0.
+__global__ void __launch_bounds__(256) k_aov_chain(SceneView S, PathState P, AovChain C) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  const int n = *C.count;
+  int p = -1;
+  bool go_on = false;
+  if (q < n) {
+    p = C.active[q];
+    const int4 hw = ntl(&P.hit_w[p]);
+    const float4 ro = ntl(&P.ray_o[p]);
+    const int depth = ntl(&P.depth[p]);
+    int2 ch = make_int2(0, 0);
+    if (depth > 0) ch = C.chain[p];
+    int kind = -1;
+    if (hw.x >= 0 && hw.w >= 0) kind = S.mats[hw.w].kind;
+    const bool specular = kind == MAT_METAL || kind == MAT_DIELECTRIC;
+    if (specular && depth < C.max_depth) {
+      const DMat M = S.mats[hw.w];
+      const float4 hp = ntl(&P.hit_p[p]), hn = ntl(&P.hit_n[p]), rdv = ntl(&P.ray_d[p]);
+      const V3 hpt = v3(hp.x, hp.y, hp.z);
+      const V3 d = hpt - v3(ro.x, ro.y, ro.z);
+      const float seg = rsqrt_exact(dot(d, d));
+      ch.x = __float_as_int(depth == 0 ? seg : __int_as_float(ch.x) + seg);
+      Rng rng{ntl(&P.lcg[p]), ntl(&P.pcg[p])};
+      V3 ndir;
+      float ntime;
+      float4 rec;
+      bool sp;
+      scatter<FAM_SPEC>(S, M, v3(rdv.x, rdv.y, rdv.z), ro.w, hpt, v3(hn.x, hn.y, hn.z), hp.w, hn.w, rng, rec, sp, ndir,
+                        ntime);
+      if (kind == MAT_METAL) {
+        float* e = C.rec + 3 * ((size_t)ch.y * C.cap + p);
+        e[0] = rec.x;
+        e[1] = rec.y;
+        e[2] = rec.z;
+        ch.y += 1;
+      }
+      C.chain[p] = ch;
+      nts(&P.ray_o[p], make_float4(hpt.x, hpt.y, hpt.z, ntime));
+      nts(&P.ray_d[p], make_float4(ndir.x, ndir.y, ndir.z, 0.f));
+      nts(&P.lcg[p], rng.lcg);
+      nts(&P.pcg[p], rng.pcg);
+      nts(&P.depth[p], depth + 1);
+      go_on = true;
+    } else {
+      V3 alb, nrm;
+      float seg;
+      aov_hit_values(S, P, p, hw, ro, alb, nrm, seg);
+      if (specular) {  // the depth limit: color() returns emitted(), 0 for these materials
+        alb = v3(0.f);
+        nrm = v3(0.f);
+      }
+      for (int k = ch.y - 1; k >= 0; --k) {
+        const float* e = C.rec + 3 * ((size_t)k * C.cap + p);
+        alb = v3(e[0], e[1], e[2]) * alb;
+      }
+      float dist = 0.f;
+      if (hw.x >= 0) dist = depth == 0 ? seg : __int_as_float(ch.x) + seg;
+      aov_store(C.val, p, alb, nrm, dist);
+    }
+  }
+  append(go_on, p, C.next, C.next_count);
 }
 
 // ===================================================== path-resident engine
@@ -5132,6 +5219,9 @@ void launch_finish(const float* acc, float* mean, int64_t n, int ns, hipStream_t
 
 void launch_aov_eval(const SceneView& S, const PathState& P, int n, float4* val, hipStream_t st) {
   hipLaunchKernelGGL(dev::k_aov_eval, dim3((n + 255) / 256), dim3(256), 0, st, S, P, n, val);
+}
+void launch_aov_chain(const SceneView& S, const PathState& P, const AovChain& C, int max_n, hipStream_t st) {
+  hipLaunchKernelGGL(dev::k_aov_chain, dim3((max_n + 255) / 256), dim3(256), 0, st, S, P, C);
 }
 void launch_aov_fold(const AovFold& A, hipStream_t st) {
   const int64_t g = (8 * (int64_t)A.np + 255) / 256;

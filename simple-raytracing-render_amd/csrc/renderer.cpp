@@ -1513,7 +1513,8 @@ int render_device(srr_renderer* r, const srr_params* p, const int32_t* pix, int6
 // ---- first-hit AOVs
 // Per path in flight: PathState's depth-0 members (rays 32 B, RNG 16 B, depth 4 B, spec
 // 8 B, hit record 48 B), the active list (4 B), the family lists (16 B) and the values
-// (32 B): 160 B, 160 MiB at the default batch of 2^20 paths.
+// (32 B): 160 B, 160 MiB at the default batch of 2^20 paths.  srr_render_aov_through adds
+// 12 B + 12 B x max_depth per path of its own, smaller default batch (ensure_aov_through).
 static int ensure_aov(AovState& A, size_t n, size_t npix, int n_sobol, std::string& err) {
   if (!A.st) RCHK(hipStreamCreateWithFlags(&A.st, hipStreamNonBlocking));
   if (n > A.cap) {
@@ -1529,6 +1530,44 @@ static int ensure_aov(AovState& A, size_t n, size_t npix, int n_sobol, std::stri
   RMEM(grow_pair(A.pixels, npix, A.acc, 8 * npix), "AOV pixel list and sums");
   RMEM(ensure_sobol(A.sobol, A.sobol_n, n_sobol), "AOV Sobol points");
   return 0;
+}
+
+// one batch of the AOV calls: pixels [p0, p0 + np) x samples [s0, s0 + min(S, spp - s0)),
+// laid out from slot 0 in A.active
+static BatchInfo aov_batch(const AovState& A, const srr_params* p, int p0, int np, int s0, int S) {
+  BatchInfo B{};
+  B.active = A.active;
+  B.count = A.cnt;
+  B.act0 = 0;
+  B.slot0 = 0;
+  B.pixels = A.pixels.get();
+  B.sobol = A.sobol.get() + 2 * (size_t)p->sample_begin;
+  B.s_base = p->sample_begin;
+  B.p0 = p0;
+  B.spp_batch = std::min(S, p->spp - s0);
+  B.n_paths = np * B.spp_batch;
+  B.s0 = s0;
+  B.nx = p->nx;
+  B.ny = p->ny;
+  B.base_seed = p->base_seed;
+  return B;
+}
+// ... and the fold of its values
+static AovFold aov_fold(const AovState& A, const srr_params* p, const BatchInfo& B, int np, float* d_albedo,
+                        float* d_normal, float* d_depth) {
+  AovFold F{};
+  F.val = (const float*)A.val;
+  F.np = np;
+  F.spp_b = B.spp_batch;
+  F.acc = A.acc.get();
+  F.init = B.s0 == 0;
+  F.finish = B.s0 + B.spp_batch == p->spp;
+  F.ns = p->spp;
+  F.p0 = B.p0;
+  F.albedo = d_albedo;
+  F.normal = d_normal;
+  F.depth = d_depth;
+  return F;
 }
 
 int render_aov(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t npix, float* d_albedo,
@@ -1553,43 +1592,120 @@ int render_aov(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t
   for (int64_t p0 = 0; p0 < npix; p0 += pix_chunk) {
     const int np = (int)std::min<int64_t>(pix_chunk, npix - p0);
     for (int s0 = 0; s0 < p->spp; s0 += S) {
-      BatchInfo B{};
-      B.active = A.active;
-      B.count = A.cnt;
-      B.act0 = 0;
-      B.slot0 = 0;
-      B.pixels = A.pixels.get();
-      B.sobol = A.sobol.get() + 2 * (size_t)p->sample_begin;
-      B.s_base = p->sample_begin;
-      B.p0 = (int)p0;
-      B.spp_batch = std::min(S, p->spp - s0);
-      B.n_paths = np * B.spp_batch;
-      B.s0 = s0;
-      B.nx = p->nx;
-      B.ny = p->ny;
-      B.base_seed = p->base_seed;
+      const BatchInfo B = aov_batch(A, p, (int)p0, np, s0, S);
       RCHK(hipMemsetAsync(A.cnt, 0, 8 * sizeof(int32_t), A.st));
       launch_raygen(r->view, A.P, B, A.st);
       launch_trace(r->view, A.P, A.active, A.cnt, B.n_paths, A.lists, (int)A.cap, A.cnt + 1, A.cnt + 5, p->max_depth,
                    nullptr, A.st);
       launch_aov_eval(r->view, A.P, B.n_paths, A.val, A.st);
-      AovFold F{};
-      F.val = (const float*)A.val;
-      F.np = np;
-      F.spp_b = B.spp_batch;
-      F.acc = A.acc.get();
-      F.init = s0 == 0;
-      F.finish = s0 + B.spp_batch == p->spp;
-      F.ns = p->spp;
-      F.p0 = (int)p0;
-      F.albedo = d_albedo;
-      F.normal = d_normal;
-      F.depth = d_depth;
-      launch_aov_fold(F, A.st);
+      launch_aov_fold(aov_fold(A, p, B, np, d_albedo, d_normal, d_depth), A.st);
     }
   }
   RCHK(hipGetLastError());
   RCHK(hipStreamSynchronize(A.st));
+  return 0;
+}
+
+// ---- through-specular AOVs
+// Per path of the call's batch, besides ensure_aov's 160 B: the second active list (4 B), the
+// running depth and record count (8 B) and max_depth metal records of 12 B: 172 B + 12 B x
+// max_depth, 940 B at the largest max_depth of 64.  The default batch keeps that within
+// kAovThroughBytes: 2^20 paths up to max_depth 7, 285,569 at 64.  These buffers are sized and
+// strided by the call's own batch and replaced, not grown, when it needs more; only ensure_aov's
+// buffers, shared with srr_render_aov, keep the largest batch either call has used.
+constexpr int64_t kAovThroughBytes = (int64_t)256 << 20;
+static int64_t aov_through_path_bytes(int max_depth) { return 172 + 12 * (int64_t)max_depth; }
+
+static int ensure_aov_through(AovState& A, size_t n, int depth, std::string& err) {
+  const size_t words = 3 * n * (size_t)std::max(depth, 1);
+  if (n > A.t_cap || words > A.t_rec) {
+    A.t_bufs.clear();
+    A.t_cap = A.t_rec = 0;
+    RMEM(A.t_bufs.add(&A.next, n), "AOV second active list");
+    RMEM(A.t_bufs.add(&A.chain, n), "AOV chain state");
+    RMEM(A.t_bufs.add(&A.rec, words), "AOV metal records");
+    A.t_cap = n;
+    A.t_rec = words;
+  }
+  RMEM(A.n_host.grow(4), "AOV active count's host mirror");
+  return 0;
+}
+
+int render_aov_through(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t npix, float* d_albedo,
+                       float* d_normal, float* d_depth, srr_aov_stats* stats, std::string& err) {
+  RCHK(hipSetDevice(r->device));
+  const int64_t N = p->batch_paths > 0
+                        ? p->batch_paths
+                        : std::min<int64_t>((int64_t)1 << 20, kAovThroughBytes / aov_through_path_bytes(p->max_depth));
+  const int64_t pix_chunk = std::min<int64_t>(npix, N);
+  const int S = (int)std::max<int64_t>(1, std::min<int64_t>(p->spp, N / pix_chunk));
+  const int64_t region = pix_chunk * S;
+  if (region > INT32_MAX / 8) {
+    err = "batch_paths too large";
+    return SRR_EINVAL;
+  }
+  AovState& A = r->aov;
+  {  // every allocation comes before the first launch
+    int rc = ensure_aov(A, (size_t)region, (size_t)npix, p->sample_begin + p->spp, err);
+    if (rc == 0) rc = ensure_aov_through(A, (size_t)region, p->max_depth, err);
+    if (rc < 0) return rc;
+  }
+  srr_aov_stats s{};
+  RCHK(hipMemcpyAsync(A.pixels.get(), pix, npix * sizeof(int32_t), hipMemcpyHostToDevice, A.st));
+  for (int64_t p0 = 0; p0 < npix; p0 += pix_chunk) {
+    const int np = (int)std::min<int64_t>(pix_chunk, npix - p0);
+    for (int s0 = 0; s0 < p->spp; s0 += S) {
+      const BatchInfo B = aov_batch(A, p, (int)p0, np, s0, S);
+      RCHK(hipMemsetAsync(A.cnt, 0, 8 * sizeof(int32_t), A.st));
+      launch_raygen(r->view, A.P, B, A.st);
+      s.paths += B.n_paths;
+      // the bounce loop: the lists alternate, their counts are cnt[0] and cnt[6]; the host
+      // reads each bounce's survivor count, which sizes the next launch and ends the loop
+      int32_t* list[2] = {A.active, A.next};
+      int32_t* count[2] = {A.cnt, A.cnt + 6};
+      int n = B.n_paths;
+      for (int bounce = 0, cur = 0; n > 0; ++bounce, cur ^= 1) {
+        if (bounce > p->max_depth) {
+          err = "through-specular AOVs: a path outlived max_depth";
+          (void)hipStreamSynchronize(A.st);
+          return SRR_EIO;
+        }
+        RCHK(hipMemsetAsync(A.cnt + 1, 0, 5 * sizeof(int32_t), A.st));  // family counts, fetch
+        RCHK(hipMemsetAsync(count[cur ^ 1], 0, sizeof(int32_t), A.st));
+        launch_trace(r->view, A.P, list[cur], count[cur], n, A.lists, (int)A.cap, A.cnt + 1, A.cnt + 5, p->max_depth,
+                     nullptr, A.st);
+        AovChain C{};
+        C.active = list[cur];
+        C.count = count[cur];
+        C.next = list[cur ^ 1];
+        C.next_count = count[cur ^ 1];
+        C.max_depth = p->max_depth;
+        C.cap = (int)region;
+        C.chain = A.chain;
+        C.rec = A.rec;
+        C.val = A.val;
+        launch_aov_chain(r->view, A.P, C, n, A.st);
+        RCHK(hipMemcpyAsync(A.n_host.get(), count[cur ^ 1], sizeof(int32_t), hipMemcpyDeviceToHost, A.st));
+        RCHK(hipStreamSynchronize(A.st));
+        s.world_rays += n;
+        s.longest_chain = std::max(s.longest_chain, bounce);
+        n = *A.n_host.get();
+        if (n < 0 || n > B.n_paths) {
+          err = "through-specular AOVs: active count out of range";
+          (void)hipStreamSynchronize(A.st);
+          return SRR_EIO;
+        }
+        if (bounce == 0) s.chained_paths += n;
+      }
+      launch_aov_fold(aov_fold(A, p, B, np, d_albedo, d_normal, d_depth), A.st);
+    }
+  }
+  RCHK(hipGetLastError());
+  RCHK(hipStreamSynchronize(A.st));
+  if (stats) {
+    s.struct_size = stats->struct_size;
+    *stats = s;
+  }
   return 0;
 }
 

@@ -127,6 +127,14 @@ struct AovState {
   DeviceMem<float> acc;      // [pixels][8], sized with the list
   DeviceMem<double> sobol;
   int sobol_n = 0;
+  // srr_render_aov_through only (renderer.cpp ensure_aov_through), sized by that call's own
+  // batch: t_cap paths, t_rec floats of metal records
+  size_t t_cap = 0, t_rec = 0;
+  int32_t* next = nullptr;   // the other active list of the bounce loop
+  int2* chain = nullptr;     // kernels.h AovChain::chain
+  float* rec = nullptr;      // kernels.h AovChain::rec
+  DeviceBag t_bufs;          // what next, chain and rec point to
+  PinnedMem<int32_t> n_host;  // mirror of the next bounce's active count
 };
 
 struct Multi;  // multi.h
@@ -211,6 +219,9 @@ int adaptive_variance(srr_renderer* r, const int32_t* d_count, float* d_var, std
 // a nullptr buffer is not asked for
 int render_aov(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t npix, float* d_albedo,
                float* d_normal, float* d_depth, std::string& err);
+// srr_render_aov_through likewise; stats may be nullptr
+int render_aov_through(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t npix, float* d_albedo,
+                       float* d_normal, float* d_depth, srr_aov_stats* stats, std::string& err);
 // The pixel list and the running sums hold npix pixels (contents not preserved).  Growing
 // replaces both buffers, and the held list (pix_key) and the running sums' bookkeeping
 // (acc_npix, acc_samples, acc_key) are forgotten with them; on failure both are empty.

@@ -68,6 +68,15 @@ class AdaptiveSpecStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
 
 
+class AovStats(ctypes.Structure):
+    """srr_aov_stats of srr_render_aov_through."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("longest_chain", ctypes.c_int32), ("paths", ctypes.c_int64),
+                ("world_rays", ctypes.c_int64), ("chained_paths", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
 class DenoiseParams(ctypes.Structure):
     """srr_denoise_params; ``DenoiseParams.defaults()`` is srr_denoise_defaults."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("iterations", ctypes.c_int), ("k_c", ctypes.c_float),
@@ -173,6 +182,9 @@ def lib():
             L.srr_denoise_defaults.argtypes = [dpp]
             L.srr_denoise.argtypes = [ip, ip, ip, dpp, vp, vp, vp, vp, vp]
             L.srr_denoise_host.argtypes = [ip, ip, ip, dpp, vp, vp, vp, vp, vp]
+        if hasattr(L, "srr_render_aov_through"):  # (as above)
+            L.srr_render_aov_through.argtypes = [vp, ctypes.POINTER(Params), ip, vp, vp, vp, ctypes.POINTER(AovStats)]
+            L.srr_render_aov_through_host.argtypes = L.srr_render_aov_through.argtypes
         if hasattr(L, "srr_denoise_var"):  # (as above)
             dvp = ctypes.POINTER(DenoiseVarParams)
             L.srr_variance_of_mean.argtypes = [ctypes.c_int32, ctypes.c_float, ctypes.c_float]
@@ -431,10 +443,13 @@ class Renderer:
         _check(lib().srr_adaptive_variance(self.h, ctypes.c_void_p(d_count_ptr or None),
                                            ctypes.c_void_p(d_var_ptr or None)))
 
-    def render_aov(self, nx, ny, spp, which=AOV_ALBEDO | AOV_NORMAL | AOV_DEPTH, max_depth=50, **kw):
+    def render_aov(self, nx, ny, spp, which=AOV_ALBEDO | AOV_NORMAL | AOV_DEPTH, max_depth=50,
+                   through_specular=False, **kw):
         """First-hit feature buffers (srr_render_aov_host) of the samples
         [sample_begin, sample_begin + spp): dict(albedo[n,3], normal[n,3], depth[n])
-        with the buffers selected in `which`; kw as make_params."""
+        with the buffers selected in `which`; kw as make_params.  through_specular: the
+        buffers of the first hit that is neither metal nor dielectric instead
+        (srr_render_aov_through_host), and the call's srr_aov_stats under "stats"."""
         p = make_params(nx, ny, spp, max_depth, **kw)
         n = shard_pixels(p).size
         out = {}
@@ -444,15 +459,27 @@ class Renderer:
             out["normal"] = np.zeros((n, 3), np.float32)
         if which & AOV_DEPTH:
             out["depth"] = np.zeros(n, np.float32)
-        _check(lib().srr_render_aov_host(self.h, ctypes.byref(p), which, _ptr(out.get("albedo")),
-                                         _ptr(out.get("normal")), _ptr(out.get("depth"))))
+        bufs = (_ptr(out.get("albedo")), _ptr(out.get("normal")), _ptr(out.get("depth")))
+        if through_specular:
+            st = AovStats(ctypes.sizeof(AovStats))
+            _check(lib().srr_render_aov_through_host(self.h, ctypes.byref(p), which, *bufs, ctypes.byref(st)))
+            out["stats"] = st.as_dict()
+        else:
+            _check(lib().srr_render_aov_host(self.h, ctypes.byref(p), which, *bufs))
         return out
 
     def render_aov_device(self, params: Params, which: int, d_albedo_ptr: int = 0, d_normal_ptr: int = 0,
-                          d_depth_ptr: int = 0) -> None:
-        """srr_render_aov into device buffers (e.g. torch tensors' data_ptr())."""
-        _check(lib().srr_render_aov(self.h, ctypes.byref(params), which, ctypes.c_void_p(d_albedo_ptr or None),
-                                    ctypes.c_void_p(d_normal_ptr or None), ctypes.c_void_p(d_depth_ptr or None)))
+                          d_depth_ptr: int = 0, through_specular=False):
+        """srr_render_aov into device buffers (e.g. torch tensors' data_ptr());
+        through_specular: srr_render_aov_through, returning its stats as a dict."""
+        bufs = (ctypes.c_void_p(d_albedo_ptr or None), ctypes.c_void_p(d_normal_ptr or None),
+                ctypes.c_void_p(d_depth_ptr or None))
+        if not through_specular:
+            _check(lib().srr_render_aov(self.h, ctypes.byref(params), which, *bufs))
+            return None
+        st = AovStats(ctypes.sizeof(AovStats))
+        _check(lib().srr_render_aov_through(self.h, ctypes.byref(params), which, *bufs, ctypes.byref(st)))
+        return st.as_dict()
 
     def render_device(self, params: Params, d_mean_ptr: int) -> dict:
         """Render into a device buffer (e.g. a torch tensor's data_ptr())."""

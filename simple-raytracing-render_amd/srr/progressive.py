@@ -11,6 +11,8 @@ samples (tests/test_progressive.py).
 With ``denoise`` set, step() returns the a-trous filtered frame (srr_denoise over
 the first-hit AOVs, rendered once at ``aov_spp`` samples); the running sums and
 ``mean`` stay the undenoised ones, so the filter never feeds back into the frame.
+``aov_through_specular`` takes the guides of either denoiser from the first hit that is
+neither metal nor dielectric (srr_render_aov_through) instead of the first hit.
 
 With ``adaptive`` set the frame is an adaptive one (srr_render_adaptive, continued by
 srr_render_adaptive_resume): step(spp) raises the per-pixel budget by spp, pixels stop
@@ -35,7 +37,7 @@ from . import capi
 class Progressive:
     def __init__(self, renderer: "capi.Renderer", nx: int, ny: int, max_depth: int = 50, flags: int = 0,
                  denoise=None, aov_spp: int = 16, adaptive=None, pass_spp_max: int = 0, fill_paths: int = 0,
-                 **params):
+                 aov_through_specular: bool = False, **params):
         self.r = renderer
         self.nx, self.ny, self.max_depth = nx, ny, max_depth
         self.flags = flags  # engine flags (e.g. capi.FLAG_WAVEFRONT)
@@ -59,6 +61,7 @@ class Progressive:
         # denoise: None / False (off), True (srr_denoise_defaults) or a capi.DenoiseParams
         self.denoise = capi.DenoiseParams.defaults() if denoise is True else (denoise or None)
         self.aov_spp = aov_spp
+        self.aov_through_specular = bool(aov_through_specular)
         self.denoised = None
         self._aov = None
         if self.denoise is not None and params.get("shard", (0, 1))[1] > 1:
@@ -78,13 +81,17 @@ class Progressive:
         if self.denoise is None:
             return self.mean
         if self._aov is None:  # the AOV call leaves the running sums alone
-            kw = {k: v for k, v in self.params.items() if k in ("base_seed", "batch_paths")}
-            self._aov = self.r.render_aov(self.nx, self.ny, self.aov_spp, max_depth=self.max_depth, **kw)
+            self._aov = self._render_aov()
         shape = (self.ny, self.nx, 3)
         a = self._aov
         self.denoised = capi.denoise(self.mean.reshape(shape), a["albedo"].reshape(shape), a["normal"].reshape(shape),
                                      a["depth"].reshape(self.ny, self.nx), self.denoise).reshape(-1, 3)
         return self.denoised
+
+    def _render_aov(self) -> dict:
+        kw = {k: v for k, v in self.params.items() if k in ("base_seed", "batch_paths")}
+        return self.r.render_aov(self.nx, self.ny, self.aov_spp, max_depth=self.max_depth,
+                                 through_specular=self.aov_through_specular, **kw)
 
     def _step_adaptive(self, spp: int) -> np.ndarray:
         a = self.adaptive
@@ -97,8 +104,7 @@ class Progressive:
         if self.denoise is None:
             return self.mean
         if self._aov is None:  # the AOV call leaves the adaptive state alone
-            kw = {k: v for k, v in self.params.items() if k in ("base_seed", "batch_paths")}
-            self._aov = self.r.render_aov(self.nx, self.ny, self.aov_spp, max_depth=self.max_depth, **kw)
+            self._aov = self._render_aov()
         shape = (self.ny, self.nx, 3)
         aov = self._aov
         feats = (aov["albedo"].reshape(shape), aov["normal"].reshape(shape), aov["depth"].reshape(self.ny, self.nx))

@@ -21,6 +21,10 @@ format of Raytracing_n.cpp:850-886).
                                             pixel's mean luminance; not with --denoise; without --adaptive the
                                             frame is one srr_render_adaptive pass at rel_tol 0, bitwise the
                                             fixed-spp frame)
+                              [--aov-through-specular]
+                                           (with --denoise, --denoise-var or --aov-out: their AOVs are those of
+                                            the first hit that is neither metal nor dielectric,
+                                            srr_render_aov_through; one GPU)
 
 Defaults are the reference's globals (Raytracing_n.cpp:39-43).  Differences, all
 forced by the reference: its 8 render threads race on shared state
@@ -70,6 +74,9 @@ def parse(argv=None):
     ap.add_argument("--aov-spp", type=int, default=None, help="samples of the AOVs (default min(ns, 16))")
     ap.add_argument("--aov-out", default=None, metavar="PREFIX",
                     help="write PREFIX_albedo.png, PREFIX_normal.png, PREFIX_depth.png")
+    ap.add_argument("--aov-through-specular", action="store_true",
+                    help="the AOVs of --denoise, --denoise-var and --aov-out follow mirrors and glass to the first "
+                         "diffuse hit (one GPU)")
     return ap.parse_args(argv)
 
 
@@ -101,6 +108,12 @@ def main(argv=None) -> int:
     if a.denoise_var and a.gpus != 1:
         print("--denoise-var needs one GPU", file=sys.stderr)
         return 2
+    if a.aov_through_specular and not (a.denoise or a.denoise_var or a.aov_out):
+        print("--aov-through-specular needs --denoise, --denoise-var or --aov-out", file=sys.stderr)
+        return 2
+    if a.aov_through_specular and a.gpus != 1:
+        print("--aov-through-specular needs one GPU", file=sys.stderr)
+        return 2
     sc = ref_scenes.BY_SCENEID[a.sceneid](float(a.nx) / float(a.ny), contents=a.contents)  # :894-919
     r = (capi.Renderer(sc.text(), device=a.device) if a.gpus == 1 else
          capi.Renderer(sc.text(), devices=list(range(a.device, a.device + a.gpus))))
@@ -124,7 +137,8 @@ def main(argv=None) -> int:
     else:
         out = r.render(a.nx, a.ny, a.ns, a.max_depth, tile=1)
     if a.denoise or a.denoise_var or a.aov_out:
-        aov = r.render_aov(a.nx, a.ny, a.aov_spp or min(a.ns, 16), max_depth=a.max_depth)
+        aov = r.render_aov(a.nx, a.ny, a.aov_spp or min(a.ns, 16), max_depth=a.max_depth,
+                           through_specular=a.aov_through_specular)
         if a.denoise:
             shape = (a.ny, a.nx, 3)
             den = capi.denoise(out["mean"].reshape(shape), aov["albedo"].reshape(shape), aov["normal"].reshape(shape),
