@@ -55,6 +55,15 @@
  *   --aov-through-specular       one GPU, with --denoise, --denoise-var or --aov-out:
  *                                their AOVs are those of the first hit that is neither
  *                                metal nor dielectric (srr_render_aov_through)
+ *   --denoise-emission           one GPU, with --denoise or --denoise-var: the filter
+ *                                runs on the frame less its emission and adds it back
+ *                                (srr_denoise_emission / srr_denoise_var_emission).  The
+ *                                emission is rendered by srr_render_aov_emission in a
+ *                                call of its own over the frame's samples (ns, not
+ *                                --aov-spp; with --adaptive every pixel's own count),
+ *                                through specular with --aov-through-specular;
+ *                                --aov-out also writes PREFIX_emission.png, tone-mapped
+ *                                like the frame
  * Differences, all forced by the reference: its render threads race on shared
  * state and its pixel mapping scrambles non-square frames (Q12);
  * srr renders every (pixel, sample) path with its per-path seed.  Exit codes:
@@ -98,13 +107,14 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
   int aov_spp = 0;  // 0: min(ns, 16)
   std::string aov_out;
   bool aov_through = false;  // --aov-through-specular
+  bool denoise_emission = false;
   auto usage = [&]() {
     std::fprintf(stderr, "usage: %s [--sceneid N | --scene NAME] [--nx N] [--ny N] [--ns N] [--max-depth N] "
                          "[--device N] [--gpus N | --devices a,b,..] [--tile N] [--out FILE] [--dry-run] "
                          "[--adaptive REL_TOL [--batch-spp N] [--min-spp N] [--count-map FILE] "
                          "[--adaptive-pass-spp N [--adaptive-fill P]]] "
                          "[--denoise | --denoise-var] [--aov-spp N] [--aov-out PREFIX] "
-                         "[--aov-through-specular]\nscenes:",
+                         "[--aov-through-specular] [--denoise-emission]\nscenes:",
                  argv[0]);
     for (int k = 0; k < n_scenes; ++k) std::fprintf(stderr, " %d:%s", scenes[k].sceneid, scenes[k].name);
     std::fprintf(stderr, "\n");
@@ -146,6 +156,7 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
     else if (a == "--aov-spp") ok = num(aov_spp) && aov_spp >= 1;
     else if (a == "--aov-out" && i + 1 < argc) aov_out = argv[++i];
     else if (a == "--aov-through-specular") aov_through = true;
+    else if (a == "--denoise-emission") denoise_emission = true;
     else ok = false;
     if (!ok) return usage();
   }
@@ -159,6 +170,7 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
   if ((denoise || denoise_var || !aov_out.empty()) && (gpus > 1 || !devices.empty())) return usage();  // one GPU
   if (aov_through && !(denoise || denoise_var || !aov_out.empty())) return usage();
   if (aov_through && (gpus > 1 || !devices.empty())) return usage();  // one GPU
+  if (denoise_emission && !(denoise || denoise_var)) return usage();
   if (aov_spp == 0) aov_spp = ns < 16 ? ns : 16;
   const char* scene_name = text_path.empty() ? e->name : text_path.c_str();
 
@@ -254,14 +266,23 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
              ? srr_render_aov_through_host(r, &pa, which, albedo.data(), normal.data(), depth.data(), nullptr)
              : srr_render_aov_host(r, &pa, which, albedo.data(), normal.data(), depth.data());
   }
+  std::vector<float> emission;
+  if (rc == 0 && denoise_emission) {  // the emission of exactly the samples the frame holds
+    emission.resize(3 * npix);
+    rc = srr_render_aov_emission_host(r, &p, SRR_AOV_EMISSION, aov_through ? 1 : 0, nullptr, nullptr, nullptr,
+                                      emission.data(), adaptive >= 0 ? count.data() : nullptr, nullptr);
+  }
   if (rc == 0 && denoise_var) {
     srr_denoise_var_params dp{};
     std::vector<float> var(npix), den(3 * npix);
     rc = srr_adaptive_variance_host(r, count.data(), var.data());
     if (rc == 0) rc = srr_denoise_var_defaults(&dp);
     if (rc == 0)
-      rc = srr_denoise_var_host(devices[0], nx, ny, &dp, mean.data(), var.data(), albedo.data(), normal.data(),
-                                depth.data(), den.data(), nullptr);
+      rc = denoise_emission
+               ? srr_denoise_var_emission_host(devices[0], nx, ny, &dp, mean.data(), var.data(), emission.data(),
+                                               albedo.data(), normal.data(), depth.data(), den.data(), nullptr)
+               : srr_denoise_var_host(devices[0], nx, ny, &dp, mean.data(), var.data(), albedo.data(), normal.data(),
+                                      depth.data(), den.data(), nullptr);
     if (rc == 0) rc = srr_tonemap(den.data(), (int64_t)npix, rgb8.data());
   }
   if (rc == 0 && denoise) {
@@ -269,8 +290,11 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
     std::vector<float> den(3 * npix);
     rc = srr_denoise_defaults(&dp);
     if (rc == 0)
-      rc = srr_denoise_host(devices[0], nx, ny, &dp, mean.data(), albedo.data(), normal.data(), depth.data(),
-                            den.data());
+      rc = denoise_emission
+               ? srr_denoise_emission_host(devices[0], nx, ny, &dp, mean.data(), emission.data(), albedo.data(),
+                                           normal.data(), depth.data(), den.data())
+               : srr_denoise_host(devices[0], nx, ny, &dp, mean.data(), albedo.data(), normal.data(), depth.data(),
+                                  den.data());
     if (rc == 0) rc = srr_tonemap(den.data(), (int64_t)npix, rgb8.data());
   }
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -290,6 +314,10 @@ inline int render_main(int argc, char** argv, const scene_entry* scenes, int n_s
     for (size_t i = 0; i < npix; ++i)
       img[3 * i] = img[3 * i + 1] = img[3 * i + 2] = byte(zmax > 0.f ? depth[i] / zmax : 0.f);
     if (rc == 0) rc = srr_write_png((aov_out + "_depth.png").c_str(), nx, ny, img.data());
+    if (rc == 0 && denoise_emission) {
+      rc = srr_tonemap(emission.data(), (int64_t)npix, img.data());
+      if (rc == 0) rc = srr_write_png((aov_out + "_emission.png").c_str(), nx, ny, img.data());
+    }
   }
   if (rc == 0 && !count_map.empty()) {  // grey level 255 * count / ns, rounded down
     std::vector<unsigned char> grey(3 * count.size());

@@ -547,6 +547,55 @@ int srr_render_aov_through(srr_renderer* r, const srr_params* p, int which, floa
 int srr_render_aov_through_host(srr_renderer* r, const srr_params* p, int which, float* albedo, float* normal,
                                 float* depth, srr_aov_stats* stats /* may be NULL */);
 
+/* ---- Emission buffer: the light a camera path sees before its first diffuse bounce, the
+ * part of a frame a denoiser should take out before it filters (SVGF filters emission
+ * apart).  No reference counterpart.  srr_render_aov_emission is srr_render_aov
+ * (through_specular == 0) or srr_render_aov_through (through_specular == 1) with a fourth
+ * buffer: `which` is a non-empty set of the four SRR_AOV_* bits, d_albedo, d_normal, d_depth
+ * and stats mean exactly what they mean in that call (first hit: paths = world_rays = primary
+ * rays, chained_paths = longest_chain = 0), and d_emission is a DEVICE pointer of
+ * n_shard_pixels*3 floats in srr_shard_pixels() order.  Per sample:
+ *   First hit.  emission = emitted() of the primary ray's hit as color() evaluates it
+ *     (Raytracing_n.cpp:61, material.h:348-354): the diffuse_light's texture at the hit's
+ *     (u, v, p) when dot(normal, ray direction) < 0; (0, 0, 0) for every other material, a
+ *     null material, the back of a light and a miss.  Unlike the albedo it depends on the
+ *     face that was hit.
+ *   Through specular.  e = emitted() of the terminal hit of srr_render_aov_through's chain,
+ *     (0, 0, 0) for a metal or dielectric reached at the depth limit;
+ *     emission = a_0 * (a_1 * ( ... (a_(k-1) * e))), folded back to front, componentwise in
+ *     float32: the same records in the same order as the albedo.
+ * De_nan, the per-pixel fold in sample order over [p->sample_begin, p->sample_begin + p->spp)
+ * and sum * (float)(1.0 / (float)n) are srr_render_aov's.  Consequences: the first-hit
+ * emission is bitwise srr_render_device at max_depth = 0; the through-specular emission is
+ * bitwise the beauty frame of the scene's "emission twin" (metal, dielectric and
+ * diffuse_light kept, every other material replaced by a diffuse_light of a constant
+ * (0, 0, 0) texture) at the same max_depth, on every pixel, with no lit-pixel mask; on a
+ * scene without metal and dielectric the two emissions are bitwise equal.  An isotropic
+ * terminal hit emits 0.
+ * d_count (DEVICE pointer, n_shard_pixels int32, may be NULL; read for the emission buffer
+ * only): pixel i's emission is folded over its first n_i = d_count[i] samples of the range
+ * and divided by n_i, the division of a fixed-spp frame of that count, so that an adaptive
+ * frame, where pixel i holds n_i samples, can subtract the emission of exactly the samples
+ * it holds.  A count outside 1..p->spp is clamped into it (the _host form refuses it
+ * instead).  NULL means p->spp for every pixel.  Albedo, normal and depth ignore it.
+ * Batches: with batch_paths = 0, first hit as srr_render_aov; through specular
+ * min(2^20, 256 MiB / (188 + 12 * max_depth) B) paths when bit 8 is set (a path's emission
+ * values are 16 B of their own, allocated the first time bit 8 is asked for; the state and
+ * default batches of the two calls above are unchanged), else as srr_render_aov_through.
+ * Synchronous.  SRR_EINVAL, before anything is allocated or enqueued, in every case those
+ * calls refuse (with the fourth bit known), for a NULL d_emission with bit 8 set, for
+ * through_specular outside 0 / 1, and in the _host form for a count outside 1..p->spp.  Like
+ * them it uses the AOV stream and buffers and leaves running sums, the held pixel list,
+ * adaptive state and async frames untouched. */
+#define SRR_AOV_EMISSION 8
+int srr_render_aov_emission(srr_renderer* r, const srr_params* p, int which, int through_specular, float* d_albedo,
+                            float* d_normal, float* d_depth, float* d_emission,
+                            const int32_t* d_count /* may be NULL */, srr_aov_stats* stats /* may be NULL */);
+/* The same with host buffers. */
+int srr_render_aov_emission_host(srr_renderer* r, const srr_params* p, int which, int through_specular, float* albedo,
+                                 float* normal, float* depth, float* emission,
+                                 const int32_t* count /* may be NULL */, srr_aov_stats* stats /* may be NULL */);
+
 /* ---- Feature-guided denoiser: an edge-avoiding a-trous wavelet filter (Dammertz,
  * Sewtz, Hanika, Lensch 2010) over a colour image and the AOVs above.  Nothing of it
  * is the reference's.  Inputs and the output are whole images in PPM order on HIP
@@ -643,6 +692,35 @@ int srr_denoise_var(int device, int nx, int ny, const srr_denoise_var_params* dp
 int srr_denoise_var_host(int device, int nx, int ny, const srr_denoise_var_params* dp, const float* color,
                          const float* var, const float* albedo, const float* normal, const float* depth, float* out,
                          float* var_out);
+
+/* ---- Emission-separated filtering: srr_denoise / srr_denoise_var on the colour less the
+ * emission buffer above, which is added back unfiltered.  A pixel on the rim of a light in
+ * view averages samples of 0 and of the light; with the emission taken out, the step is gone
+ * from the signal the filter sees and the light's edge stays where the renderer put it.
+ * d_emission: nx*ny*3 floats in PPM order (srr_render_aov_emission over the samples the
+ * colour holds).  The definitions are those above with two changes, in float32, without
+ * fused multiply-add:
+ *   Set-up.  Per channel c' = c - e, and c' takes the place of c: x = c - e, or with
+ *     SRR_DENOISE_DEMODULATE x = rdiv(c - e, a + 1e-3f).
+ *   Output.  Per channel out = y + e, y being what the unchanged definition writes (with
+ *     the flag the remodulated x * (a + 1e-3f): the multiply and the add are two roundings).
+ * The variance input and var_out are unchanged: var is the variance of lum(c), emission
+ * included, so at a light's rim it overstates the variance of c - e, and the filter is more
+ * permissive there, on a signal that no longer has the step.
+ * tests/denoise_emission_ref.py restates both in numpy, bit for bit.
+ * SRR_EINVAL as in the base calls; d_emission must not be NULL, and no output may overlap it. */
+int srr_denoise_emission(int device, int nx, int ny, const srr_denoise_params* dp, const float* d_color,
+                         const float* d_emission, const float* d_albedo, const float* d_normal, const float* d_depth,
+                         float* d_out);
+int srr_denoise_emission_host(int device, int nx, int ny, const srr_denoise_params* dp, const float* color,
+                              const float* emission, const float* albedo, const float* normal, const float* depth,
+                              float* out);
+int srr_denoise_var_emission(int device, int nx, int ny, const srr_denoise_var_params* dp, const float* d_color,
+                             const float* d_var, const float* d_emission, const float* d_albedo,
+                             const float* d_normal, const float* d_depth, float* d_out, float* d_var_out);
+int srr_denoise_var_emission_host(int device, int nx, int ny, const srr_denoise_var_params* dp, const float* color,
+                                  const float* var, const float* emission, const float* albedo, const float* normal,
+                                  const float* depth, float* out, float* var_out);
 
 /* Progressive rendering with resume: the renderer's per-pixel running sums
  * (3 floats per shard pixel, in srr_shard_pixels order) and the samples per pixel

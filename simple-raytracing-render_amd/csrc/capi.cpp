@@ -783,6 +783,78 @@ int srr_render_aov_through_host(srr_renderer* r, const srr_params* p, int which,
   return rc;
 }
 
+// ---- the emission AOV: the checks of the two calls above on the three old bits, then its own
+static int aov_emission_check(const srr_renderer* r, const srr_params* p, int which, int through, const void* a,
+                              const void* n, const void* z, const void* e, const srr_aov_stats* stats) {
+  if (!r || !p) return fail(SRR_EINVAL, "null argument");
+  if (which == 0 || (which & ~(SRR_AOV_ALBEDO | SRR_AOV_NORMAL | SRR_AOV_DEPTH | SRR_AOV_EMISSION)))
+    return fail(SRR_EINVAL, "srr_render_aov_emission: which must be a non-empty set of SRR_AOV_* bits");
+  if (through != 0 && through != 1) return fail(SRR_EINVAL, "srr_render_aov_emission: through_specular must be 0 or 1");
+  if ((which & SRR_AOV_EMISSION) && !e)
+    return fail(SRR_EINVAL, "srr_render_aov_emission: a buffer selected in `which` is NULL");
+  const int old = which & ~SRR_AOV_EMISSION;
+  // (with bit 8 alone the old checks run on a stand-in bit whose buffer is the emission's)
+  if (const int rc = aov_through_check(r, p, old ? old : SRR_AOV_ALBEDO, old ? a : e, n, z, stats)) return rc;
+  return 0;
+}
+
+int srr_render_aov_emission(srr_renderer* r, const srr_params* p, int which, int through_specular, float* d_albedo,
+                            float* d_normal, float* d_depth, float* d_emission, const int32_t* d_count,
+                            srr_aov_stats* stats) {
+  // every refusal comes before anything is allocated or enqueued
+  if (const int rc = aov_emission_check(r, p, which, through_specular, d_albedo, d_normal, d_depth, d_emission, stats))
+    return rc;
+  const int64_t npix = srr_shard_pixels(p, nullptr);
+  if (npix < 0) return (int)npix;
+  if (npix == 0) {
+    if (stats) *stats = srr_aov_stats{stats->struct_size, 0, 0, 0, 0};
+    return 0;
+  }
+  std::vector<int32_t> pix(npix);
+  srr_shard_pixels(p, pix.data());
+  std::string err;
+  const bool em = (which & SRR_AOV_EMISSION) != 0;
+  const int rc = render_aov_emission(r, p, pix.data(), npix, through_specular,
+                                     (which & SRR_AOV_ALBEDO) ? d_albedo : nullptr,
+                                     (which & SRR_AOV_NORMAL) ? d_normal : nullptr,
+                                     (which & SRR_AOV_DEPTH) ? d_depth : nullptr, em ? d_emission : nullptr,
+                                     em ? d_count : nullptr, stats, err);
+  return rc < 0 ? fail(rc, err) : 0;
+}
+
+int srr_render_aov_emission_host(srr_renderer* r, const srr_params* p, int which, int through_specular, float* albedo,
+                                 float* normal, float* depth, float* emission, const int32_t* count,
+                                 srr_aov_stats* stats) {
+  if (const int rc = aov_emission_check(r, p, which, through_specular, albedo, normal, depth, emission, stats))
+    return rc;
+  const int64_t npix = srr_shard_pixels(p, nullptr);
+  if (npix < 0) return (int)npix;
+  const bool em = (which & SRR_AOV_EMISSION) != 0;
+  if (em && count)
+    for (int64_t i = 0; i < npix; ++i)
+      if (count[i] < 1 || count[i] > p->spp)
+        return fail(SRR_EINVAL, "srr_render_aov_emission_host: count[" + std::to_string(i) + "] is outside 1..spp");
+  DeviceMem<float> buf;  // albedo [3 npix], normal [3 npix], depth [npix], emission [3 npix]
+  DeviceMem<int32_t> dc;
+  HIPCHK(hipSetDevice(r->device));
+  MEMCHK(buf.grow(10 * npix), SRR_EIO, "AOV staging images");
+  float* const d = buf.get();
+  if (em && count && npix > 0) {
+    MEMCHK(dc.grow(at_least_16_bytes<int32_t>(npix)), SRR_EIO, "AOV staging counts");
+    const hipError_t e = hipMemcpy(dc.get(), count, npix * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(SRR_EIO, hipGetErrorString(e));
+  }
+  int rc = srr_render_aov_emission(r, p, which, through_specular, d, d + 3 * npix, d + 6 * npix, d + 7 * npix,
+                                   em && count ? dc.get() : nullptr, stats);
+  if (rc == 0 && npix > 0 && (which & ~SRR_AOV_EMISSION))
+    rc = aov_copy_out(which, d, npix, albedo, normal, depth);
+  if (rc == 0 && npix > 0 && em) {
+    const hipError_t e = hipMemcpy(emission, d + 7 * npix, 3 * npix * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(SRR_EIO, hipGetErrorString(e));
+  }
+  return rc;
+}
+
 // ---- the a-trous denoisers (denoise.hip): srr_denoise and srr_denoise_var
 extern "C++" {
 namespace {
@@ -792,14 +864,19 @@ struct DnEntry {
   const char* fn;
   const char* k0;
   AtrousStop stop;
+  bool emission = false;
 };
 const DnEntry kDnColour{"srr_denoise", "k_c", kColourStop}, kDnVar{"srr_denoise_var", "k_l", kVarianceStop};
+// the emission-separated entries: the same filters, d_emission required
+const DnEntry kDnColourE{"srr_denoise_emission", "k_c", kColourStop, true},
+    kDnVarE{"srr_denoise_var_emission", "k_l", kVarianceStop, true};
 float dn_k0(const srr_denoise_params& p) { return p.k_c; }
 float dn_k0(const srr_denoise_var_params& p) { return p.k_l; }
 
 struct DnBuffers {  // var and var_out: srr_denoise_var only (var_out may be NULL there too)
   const float *color, *var, *albedo, *normal, *depth;
   float *out, *var_out;
+  const float* emission = nullptr;  // the _emission entries only
 };
 
 struct Image {  // a caller's buffer and, in the _host entries, its part of the staging allocation
@@ -830,8 +907,10 @@ int denoise_check(const DnEntry& E, int device, int nx, int ny, const Params* dp
   const bool has_var = E.stop == kVarianceStop;
   if (!b.color || (has_var && !b.var) || !b.albedo || !b.normal || !b.depth || !b.out)
     return fail(SRR_EINVAL, fn + ": null buffer");
+  if (E.emission && !b.emission) return fail(SRR_EINVAL, fn + ": null buffer");
   const size_t n = (size_t)nx * ny;
-  const Image in[] = {{b.color, 3 * n}, {b.var, n}, {b.albedo, 3 * n}, {b.normal, 3 * n}, {b.depth, n}};
+  const Image in[] = {{b.color, 3 * n},  {b.var, n},   {b.albedo, 3 * n},
+                      {b.normal, 3 * n}, {b.depth, n}, {b.emission, 3 * n}};
   const Image outs[] = {{b.out, 3 * n}, {b.var_out, n}};
   for (const Image& o : outs)
     for (const Image& i : in)
@@ -870,7 +949,8 @@ int denoise_device(const DnEntry& E, int device, int nx, int ny, const Params* d
   float4* guide = W.get() + 2 * n;
   const bool demod = (dp->flags & SRR_DENOISE_DEMODULATE) != 0;
   hipStream_t st = nullptr;  // the caller's inputs were written on the legacy stream or are complete
-  launch_atrous_pack(E.stop, (int64_t)n, b.color, b.var, demod ? b.albedo : nullptr, b.normal, b.depth, x[0], guide, st);
+  launch_atrous_pack(E.stop, (int64_t)n, b.color, b.var, b.emission, demod ? b.albedo : nullptr, b.normal, b.depth,
+                     x[0], guide, st);
   for (int k = 0; k < dp->iterations; ++k) {
     const bool last = k + 1 == dp->iterations;
     AtrousIter I{};
@@ -886,6 +966,7 @@ int denoise_device(const DnEntry& E, int device, int nx, int ny, const Params* d
     I.out = last ? b.out : nullptr;
     I.var_out = last ? b.var_out : nullptr;
     I.albedo = last && demod ? b.albedo : nullptr;
+    I.emission = last ? b.emission : nullptr;
     launch_atrous_iter(E.stop, I, denoise_variant(), st);
   }
   HIPCHK(hipGetLastError());
@@ -926,14 +1007,15 @@ template <class Params>
 int denoise_host(const DnEntry& E, int device, int nx, int ny, const Params* dp, const DnBuffers& h) {
   if (const int rc = denoise_check(E, device, nx, ny, dp, h)) return rc;
   const size_t n = (size_t)nx * ny;
-  Image img[] = {{h.color, 3 * n}, {h.var, n}, {h.albedo, 3 * n}, {h.normal, 3 * n}, {h.depth, n},
-                 {h.out, 3 * n},   {h.var_out, n}};
+  Image img[] = {{h.color, 3 * n}, {h.var, n},        {h.albedo, 3 * n}, {h.normal, 3 * n},
+                 {h.depth, n},     {h.emission, 3 * n}, {h.out, 3 * n},    {h.var_out, n}};
   DeviceMem<float> buf;
   HIPCHK(hipSetDevice(device));
-  if (const int rc = stage_in(buf, std::string(E.fn) + "_host: staging images", img, 5)) return rc;
-  const int rc = denoise_device(E, device, nx, ny, dp,
-                                {img[0].dev, img[1].dev, img[2].dev, img[3].dev, img[4].dev, img[5].dev, img[6].dev});
-  return rc ? rc : stage_out(img, 5);
+  if (const int rc = stage_in(buf, std::string(E.fn) + "_host: staging images", img, 6)) return rc;
+  const int rc = denoise_device(
+      E, device, nx, ny, dp,
+      {img[0].dev, img[1].dev, img[2].dev, img[3].dev, img[4].dev, img[6].dev, img[7].dev, img[5].dev});
+  return rc ? rc : stage_out(img, 6);
 }
 }  // namespace
 }  // extern "C++"
@@ -973,6 +1055,32 @@ int srr_denoise_var_host(int device, int nx, int ny, const srr_denoise_var_param
                          const float* var, const float* albedo, const float* normal, const float* depth, float* out,
                          float* var_out) {
   return denoise_host(kDnVar, device, nx, ny, dp, {color, var, albedo, normal, depth, out, var_out});
+}
+
+int srr_denoise_emission(int device, int nx, int ny, const srr_denoise_params* dp, const float* d_color,
+                         const float* d_emission, const float* d_albedo, const float* d_normal, const float* d_depth,
+                         float* d_out) {
+  return denoise_device(kDnColourE, device, nx, ny, dp,
+                        {d_color, nullptr, d_albedo, d_normal, d_depth, d_out, nullptr, d_emission});
+}
+
+int srr_denoise_emission_host(int device, int nx, int ny, const srr_denoise_params* dp, const float* color,
+                              const float* emission, const float* albedo, const float* normal, const float* depth,
+                              float* out) {
+  return denoise_host(kDnColourE, device, nx, ny, dp, {color, nullptr, albedo, normal, depth, out, nullptr, emission});
+}
+
+int srr_denoise_var_emission(int device, int nx, int ny, const srr_denoise_var_params* dp, const float* d_color,
+                             const float* d_var, const float* d_emission, const float* d_albedo,
+                             const float* d_normal, const float* d_depth, float* d_out, float* d_var_out) {
+  return denoise_device(kDnVarE, device, nx, ny, dp,
+                        {d_color, d_var, d_albedo, d_normal, d_depth, d_out, d_var_out, d_emission});
+}
+
+int srr_denoise_var_emission_host(int device, int nx, int ny, const srr_denoise_var_params* dp, const float* color,
+                                  const float* var, const float* emission, const float* albedo, const float* normal,
+                                  const float* depth, float* out, float* var_out) {
+  return denoise_host(kDnVarE, device, nx, ny, dp, {color, var, albedo, normal, depth, out, var_out, emission});
 }
 
 int srr_render_wait(srr_renderer* r, int64_t ticket, srr_stats* stats) {

@@ -19,6 +19,9 @@
 //     and the 25-fold reuse is left to the L2.
 // No kernel waits on another block; the iterations are separate launches on one
 // stream.  The last iteration writes the 3-float output, remodulated.
+// Emission-separated filtering (srr_denoise_emission, srr_denoise_var_emission): pack
+// subtracts the emission image from the colour and the last store adds it back; the
+// iterations are the same kernels on the same words.
 //
 // The policies.  ColourStop (srr_denoise) weighs a tap by its squared colour
 // difference and leaves x's fourth word 0.  VarianceStop (srr_denoise_var; the
@@ -189,6 +192,11 @@ SRR_D void atrous_pixel(const AtrousIter& I, int px, int py, int s, const Src& s
       const float mr = I.albedo[3 * pi] + 1e-3f, mg = I.albedo[3 * pi + 1] + 1e-3f, mb = I.albedo[3 * pi + 2] + 1e-3f;
       v = make_float4(v.x * mr, v.y * mg, v.z * mb, P::remod4(v.w, mr, mg, mb));
     }
+    if (I.emission) {  // emission-separated: what pack took out goes back in, one more rounding
+      v.x = v.x + I.emission[3 * pi];
+      v.y = v.y + I.emission[3 * pi + 1];
+      v.z = v.z + I.emission[3 * pi + 2];
+    }
     I.out[3 * pi] = v.x;
     I.out[3 * pi + 1] = v.y;
     I.out[3 * pi + 2] = v.z;
@@ -200,12 +208,18 @@ SRR_D void atrous_pixel(const AtrousIter& I, int px, int py, int s, const Src& s
 
 template <class P>
 __global__ void __launch_bounds__(256) k_atrous_pack(int64_t n, const float* __restrict__ color,
-                                                     const float* __restrict__ var, const float* __restrict__ albedo,
+                                                     const float* __restrict__ var, const float* __restrict__ emission,
+                                                     const float* __restrict__ albedo,
                                                      const float* __restrict__ normal, const float* __restrict__ depth,
                                                      float4* __restrict__ x, float4* __restrict__ g) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float4 v = make_float4(color[3 * i], color[3 * i + 1], color[3 * i + 2], P::in4(var, i));
+  if (emission) {  // emission-separated (srr_denoise_emission): c - e takes the place of c
+    v.x = v.x - emission[3 * i];
+    v.y = v.y - emission[3 * i + 1];
+    v.z = v.z - emission[3 * i + 2];
+  }
   if (albedo) {  // demodulate
     const float mr = albedo[3 * i] + 1e-3f, mg = albedo[3 * i + 1] + 1e-3f, mb = albedo[3 * i + 2] + 1e-3f;
     v = make_float4(rdiv(v.x, mr), rdiv(v.y, mg), rdiv(v.z, mb), P::demod4(v.w, mr, mg, mb));
@@ -260,10 +274,12 @@ void launch_iter(const AtrousIter& I, int variant, hipStream_t st) {
 
 }  // namespace dev
 
-void launch_atrous_pack(AtrousStop stop, int64_t n, const float* color, const float* var, const float* albedo,
-                        const float* normal, const float* depth, float4* x, float4* g, hipStream_t st) {
+void launch_atrous_pack(AtrousStop stop, int64_t n, const float* color, const float* var, const float* emission,
+                        const float* albedo, const float* normal, const float* depth, float4* x, float4* g,
+                        hipStream_t st) {
   const auto k = stop == kVarianceStop ? dev::k_atrous_pack<dev::VarianceStop> : dev::k_atrous_pack<dev::ColourStop>;
-  hipLaunchKernelGGL(k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, color, var, albedo, normal, depth, x, g);
+  hipLaunchKernelGGL(k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, color, var, emission, albedo, normal,
+                     depth, x, g);
 }
 
 void launch_atrous_iter(AtrousStop stop, const AtrousIter& I, int variant, hipStream_t st) {

@@ -500,7 +500,9 @@ void launch_finish(const float* acc, float* mean, int64_t n, int ns, hipStream_t
 // ---- first-hit AOVs (srr_render_aov, renderer.cpp render_aov)
 // After launch_raygen (slot0 = act0 = 0) and launch_trace of a batch of n primary rays:
 // val[2p] = (albedo.rgb, depth), val[2p + 1] = (normal.xyz, 0) of path p, de_nan'd.
-void launch_aov_eval(const SceneView& S, const PathState& P, int n, float4* val, hipStream_t st);
+// emit != nullptr (srr_render_aov_emission): also emit[p] = (emitted().rgb, 0), by the
+// kernel's other instantiation; nullptr launches the kernel that does no emission work.
+void launch_aov_eval(const SceneView& S, const PathState& P, int n, float4* val, float4* emit, hipStream_t st);
 // acc[8 lp + c] (+)= the batch's spp_b samples of pixel lp in sample order (init: the
 // sums start from 0); finish: also the means sum * (float)(1.0 / (float)ns) to the
 // caller's buffers (nullptr: not asked for) at shard pixel p0 + lp.
@@ -514,6 +516,19 @@ struct AovFold {
   float* depth;
 };
 void launch_aov_fold(const AovFold& A, hipStream_t st);
+// The emission's fold (srr_render_aov_emission): acc[4 lp + c] (+)= those of the batch's
+// samples [s0, s0 + spp_b) of pixel lp that lie below the pixel's count n_i = count[p0 + lp]
+// clamped into 1..ns (count == nullptr: ns), in sample order, from 0 when s0 == 0; the
+// batch that holds sample n_i - 1 writes sum * (float)(1.0 / (float)n_i) to emission.
+struct AovEmissionFold {
+  const float* emit;  // [np][spp_b][4]
+  int np, spp_b, s0;
+  float* acc;         // [np][4]
+  int ns, p0;
+  const int32_t* count;  // [shard pixels] or nullptr
+  float* emission;       // [shard pixels][3]
+};
+void launch_aov_fold_emission(const AovEmissionFold& A, hipStream_t st);
 // ---- through-specular AOVs (srr_render_aov_through, renderer.cpp render_aov_through)
 // One bounce after launch_trace over the *count paths of `active`: a path whose hit is
 // metal or dielectric below max_depth takes that specular step (record, running depth,
@@ -530,6 +545,7 @@ struct AovChain {
   int2* chain;          // [cap] (running depth as float bits, metal records written)
   float* rec;           // [max_depth][cap][3] metal colours, in bounce order per path
   float4* val;          // [>= cap][2]
+  float4* emit;         // [>= cap] (emission.rgb, 0), or nullptr: the instantiation without emission
 };
 void launch_aov_chain(const SceneView& S, const PathState& P, const AovChain& C, int max_n, hipStream_t st);
 // image[index[i]] = packed[i] (float3 per pixel) for i < n: multi-device frame assembly

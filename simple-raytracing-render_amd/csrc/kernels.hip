@@ -2659,11 +2659,16 @@ __global__ void __launch_bounds__(256) k_record(SceneView S, PathState P, const 
 // albedo, normal and segment length by srr_render_aov's rules (include/srr_capi.h).
 // k_record writes no record for a null material, so that hit's record is recomputed
 // here with the same world_record.
+// EMIT (srr_render_aov_emission): also emit = emitted() of the hit as color() evaluates
+// it (hit_emitted: the light's texture on the face the ray meets from the front, else 0),
+// which for a light is the albedo's texture value, so it is taken from there.
+template <bool EMIT>
 SRR_D void aov_hit_values(const SceneView& S, const PathState& P, int p, int4 hw, float4 ro, V3& alb, V3& nrm,
-                          float& depth) {
+                          float& depth, V3& emit) {
   alb = v3(0.f);
   nrm = v3(0.f);
   depth = 0.f;
+  if (EMIT) emit = v3(0.f);
   if (hw.x < 0) return;
   V3 hp, hn;
   float hu, hv;
@@ -2693,6 +2698,10 @@ SRR_D void aov_hit_values(const SceneView& S, const PathState& P, int p, int4 hw
     if (M.kind == MAT_METAL) alb = v3(M.p[0], M.p[1], M.p[2]);
     else if (M.kind == MAT_DIELECTRIC) alb = v3(1.f);
     else alb = tex_value(S, M.tex, hu, hv, hp);
+    if (EMIT && M.kind == MAT_DIFFUSE_LIGHT) {
+      const float4 rdv = ntl(&P.ray_d[p]);
+      if (dot(hn, v3(rdv.x, rdv.y, rdv.z)) < 0.0) emit = alb;
+    }
   }
 }
 
@@ -2710,16 +2719,29 @@ SRR_D void aov_store(float4* __restrict__ val, int p, V3 alb, V3 nrm, float dept
   nts(&val[2 * (size_t)p + 1], make_float4(nrm.x, nrm.y, nrm.z, 0.f));
 }
 
+// emit[p] = (emission.rgb, 0) of path p, de_nan'd
+SRR_D void aov_store_emission(float4* __restrict__ emit, int p, V3 e) {
+  if (!(e.x == e.x)) e.x = 0;
+  if (!(e.y == e.y)) e.y = 0;
+  if (!(e.z == e.z)) e.z = 0;
+  nts(&emit[p], make_float4(e.x, e.y, e.z, 0.f));
+}
+
 // First-hit AOVs (srr_render_aov, include/srr_capi.h).  One thread per primary ray
 // of a batch that k_raygen laid out pixel-major in slots 0 .. n-1 and k_trace /
 // k_record resolved.
-__global__ void __launch_bounds__(256) k_aov_eval(SceneView S, PathState P, int n, float4* __restrict__ val) {
+// EMIT: also emit[p] = (emission.rgb, 0), for srr_render_aov_emission; the other
+// instantiation is the kernel of srr_render_aov.
+template <bool EMIT>
+__global__ void __launch_bounds__(256) k_aov_eval(SceneView S, PathState P, int n, float4* __restrict__ val,
+                                                  float4* __restrict__ emit) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n) return;
-  V3 alb, nrm;
+  V3 alb, nrm, em;
   float depth;
-  aov_hit_values(S, P, p, ntl(&P.hit_w[p]), ntl(&P.ray_o[p]), alb, nrm, depth);
+  aov_hit_values<EMIT>(S, P, p, ntl(&P.hit_w[p]), ntl(&P.ray_o[p]), alb, nrm, depth, em);
   aov_store(val, p, alb, nrm, depth);
+  if (EMIT) aov_store_emission(emit, p, em);
 }
 
 // The AOV fold: thread (pixel lp, word c of the pixel's 8) adds the batch's spp_b
@@ -2750,6 +2772,32 @@ __global__ void __launch_bounds__(256) k_aov_fold(const float* __restrict__ val,
   } else if (normal) {
     normal[3 * gp + (c - 4)] = m;
   }
+}
+
+// The emission fold (srr_render_aov_emission): thread (pixel lp, word c of the path's 4)
+// adds the samples of the batch [s0, s0 + spp_b) that lie below the pixel's count n_i, in
+// sample order, to acc[4 lp + c] (from 0 when s0 == 0).  n_i = count[p0 + lp] clamped into
+// 1..ns, or ns without a count.  The batch that holds the pixel's last sample n_i - 1
+// writes the mean sum * (float)(1.0 / (float)n_i) to shard pixel p0 + lp.
+__global__ void __launch_bounds__(256) k_aov_fold_emission(const float* __restrict__ emit, int np, int spp_b, int s0,
+                                                           float* acc, int ns, int p0,
+                                                           const int32_t* __restrict__ count, float* emission) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 4 * np) return;
+  const int lp = i >> 2, c = i & 3;
+  if (c == 3) return;
+  const size_t gp = (size_t)p0 + lp;
+  int ni = ns;
+  if (count) ni = min(max(count[gp], 1), ns);
+  if (s0 >= ni) return;  // the pixel's samples ended in an earlier batch
+  const int kn = min(spp_b, ni - s0);
+  float s = s0 == 0 ? 0.f : acc[i];
+  const float* v = emit + (size_t)lp * spp_b * 4 + c;
+  for (int k = 0; k < kn; ++k) s += v[(size_t)k * 4];
+  acc[i] = s;
+  if (s0 + kn != ni) return;
+  const float kinv = 1.0 / (float)ni;
+  emission[3 * gp + c] = s * kinv;
 }
 
 // Diagnostic probes (SRR_PROBE=1, timing attribution only): the trace kernel's
@@ -2987,6 +3035,10 @@ SRR_D bool shade_one(const SceneView& S, const PathState& P, int p, int max_dept
 // albedo folded through the records back to front (finish_path's order), the depth the
 // running sum plus this segment, 0 after a miss.  C.chain[p] = (running depth bits,
 // records written), not read at depth 0.
+// EMIT (srr_render_aov_emission): the terminal hit's emitted() is folded through the same
+// records in the same loop and goes to C.emit[p]; the other instantiation is the kernel
+// of srr_render_aov_through.
+template <bool EMIT>
 __global__ void __launch_bounds__(256) k_aov_chain(SceneView S, PathState P, AovChain C) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   const int n = *C.count;
@@ -3031,20 +3083,23 @@ __global__ void __launch_bounds__(256) k_aov_chain(SceneView S, PathState P, Aov
       nts(&P.depth[p], depth + 1);
       go_on = true;
     } else {
-      V3 alb, nrm;
+      V3 alb, nrm, em;
       float seg;
-      aov_hit_values(S, P, p, hw, ro, alb, nrm, seg);
+      aov_hit_values<EMIT>(S, P, p, hw, ro, alb, nrm, seg, em);
       if (specular) {  // the depth limit: color() returns emitted(), 0 for these materials
         alb = v3(0.f);
         nrm = v3(0.f);
       }
       for (int k = ch.y - 1; k >= 0; --k) {
         const float* e = C.rec + 3 * ((size_t)k * C.cap + p);
-        alb = v3(e[0], e[1], e[2]) * alb;
+        const V3 a = v3(e[0], e[1], e[2]);
+        alb = a * alb;
+        if (EMIT) em = a * em;
       }
       float dist = 0.f;
       if (hw.x >= 0) dist = depth == 0 ? seg : __int_as_float(ch.x) + seg;
       aov_store(C.val, p, alb, nrm, dist);
+      if (EMIT) aov_store_emission(C.emit, p, em);
     }
   }
   append(go_on, p, C.next, C.next_count);
@@ -5217,11 +5272,18 @@ void launch_finish(const float* acc, float* mean, int64_t n, int ns, hipStream_t
   hipLaunchKernelGGL(dev::k_finish, dim3((unsigned)g), dim3(256), 0, st, acc, mean, n, ns);
 }
 
-void launch_aov_eval(const SceneView& S, const PathState& P, int n, float4* val, hipStream_t st) {
-  hipLaunchKernelGGL(dev::k_aov_eval, dim3((n + 255) / 256), dim3(256), 0, st, S, P, n, val);
+void launch_aov_eval(const SceneView& S, const PathState& P, int n, float4* val, float4* emit, hipStream_t st) {
+  const auto k = emit ? dev::k_aov_eval<true> : dev::k_aov_eval<false>;
+  hipLaunchKernelGGL(k, dim3((n + 255) / 256), dim3(256), 0, st, S, P, n, val, emit);
 }
 void launch_aov_chain(const SceneView& S, const PathState& P, const AovChain& C, int max_n, hipStream_t st) {
-  hipLaunchKernelGGL(dev::k_aov_chain, dim3((max_n + 255) / 256), dim3(256), 0, st, S, P, C);
+  const auto k = C.emit ? dev::k_aov_chain<true> : dev::k_aov_chain<false>;
+  hipLaunchKernelGGL(k, dim3((max_n + 255) / 256), dim3(256), 0, st, S, P, C);
+}
+void launch_aov_fold_emission(const AovEmissionFold& A, hipStream_t st) {
+  const int64_t g = ((int64_t)4 * A.np + 255) / 256;
+  hipLaunchKernelGGL(dev::k_aov_fold_emission, dim3((unsigned)g), dim3(256), 0, st, A.emit, A.np, A.spp_b, A.s0, A.acc,
+                     A.ns, A.p0, A.count, A.emission);
 }
 void launch_aov_fold(const AovFold& A, hipStream_t st) {
   const int64_t g = (8 * (int64_t)A.np + 255) / 256;

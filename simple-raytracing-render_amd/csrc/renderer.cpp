@@ -1570,8 +1570,33 @@ static AovFold aov_fold(const AovState& A, const srr_params* p, const BatchInfo&
   return F;
 }
 
-int render_aov(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t npix, float* d_albedo,
-               float* d_normal, float* d_depth, std::string& err) {
+// srr_render_aov_emission's own buffers: 16 B per path of the call's batch for the emission
+// values (the 8-word `val` layout and the other calls' state stay as they are) and 16 B per
+// pixel of sums.  Allocated the first time SRR_AOV_EMISSION is asked for.
+static int ensure_aov_emission(AovState& A, size_t n, size_t npix, std::string& err) {
+  RMEM(A.emit.grow(at_least_16_bytes<float4>(n)), "AOV emission values");
+  RMEM(A.acc_e.grow(at_least_16_bytes<float>(4 * npix)), "AOV emission sums");
+  return 0;
+}
+static AovEmissionFold aov_fold_emission(const AovState& A, const srr_params* p, const BatchInfo& B, int np,
+                                         const int32_t* d_count, float* d_emission) {
+  AovEmissionFold F{};
+  F.emit = (const float*)A.emit.get();
+  F.np = np;
+  F.spp_b = B.spp_batch;
+  F.s0 = B.s0;
+  F.acc = A.acc_e.get() + 4 * (size_t)B.p0;
+  F.ns = p->spp;
+  F.p0 = B.p0;
+  F.count = d_count;
+  F.emission = d_emission;
+  return F;
+}
+
+// srr_render_aov (d_emission == nullptr) and the first-hit form of srr_render_aov_emission
+static int aov_first_hit(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t npix, float* d_albedo,
+                         float* d_normal, float* d_depth, float* d_emission, const int32_t* d_count,
+                         std::string& err) {
   RCHK(hipSetDevice(r->device));
   // batches as in render_device: a pixel chunk x a sample chunk of at most N paths;
   // a pixel chunk sees all its sample chunks, in order, before the next one starts
@@ -1585,9 +1610,11 @@ int render_aov(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t
   }
   AovState& A = r->aov;
   {  // every allocation comes before the first launch
-    const int rc = ensure_aov(A, (size_t)region, (size_t)npix, p->sample_begin + p->spp, err);
+    int rc = ensure_aov(A, (size_t)region, (size_t)npix, p->sample_begin + p->spp, err);
+    if (rc == 0 && d_emission) rc = ensure_aov_emission(A, (size_t)region, (size_t)npix, err);
     if (rc < 0) return rc;
   }
+  const bool old_three = d_albedo || d_normal || d_depth;
   RCHK(hipMemcpyAsync(A.pixels.get(), pix, npix * sizeof(int32_t), hipMemcpyHostToDevice, A.st));
   for (int64_t p0 = 0; p0 < npix; p0 += pix_chunk) {
     const int np = (int)std::min<int64_t>(pix_chunk, npix - p0);
@@ -1597,13 +1624,19 @@ int render_aov(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t
       launch_raygen(r->view, A.P, B, A.st);
       launch_trace(r->view, A.P, A.active, A.cnt, B.n_paths, A.lists, (int)A.cap, A.cnt + 1, A.cnt + 5, p->max_depth,
                    nullptr, A.st);
-      launch_aov_eval(r->view, A.P, B.n_paths, A.val, A.st);
-      launch_aov_fold(aov_fold(A, p, B, np, d_albedo, d_normal, d_depth), A.st);
+      launch_aov_eval(r->view, A.P, B.n_paths, A.val, d_emission ? A.emit.get() : nullptr, A.st);
+      if (old_three) launch_aov_fold(aov_fold(A, p, B, np, d_albedo, d_normal, d_depth), A.st);
+      if (d_emission) launch_aov_fold_emission(aov_fold_emission(A, p, B, np, d_count, d_emission), A.st);
     }
   }
   RCHK(hipGetLastError());
   RCHK(hipStreamSynchronize(A.st));
   return 0;
+}
+
+int render_aov(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t npix, float* d_albedo,
+               float* d_normal, float* d_depth, std::string& err) {
+  return aov_first_hit(r, p, pix, npix, d_albedo, d_normal, d_depth, nullptr, nullptr, err);
 }
 
 // ---- through-specular AOVs
@@ -1613,8 +1646,12 @@ int render_aov(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t
 // kAovThroughBytes: 2^20 paths up to max_depth 7, 285,569 at 64.  These buffers are sized and
 // strided by the call's own batch and replaced, not grown, when it needs more; only ensure_aov's
 // buffers, shared with srr_render_aov, keep the largest batch either call has used.
+// With the emission (srr_render_aov_emission) a path holds 16 B more, 188 B + 12 B x max_depth,
+// and that call's default batch keeps it within the same bound.
 constexpr int64_t kAovThroughBytes = (int64_t)256 << 20;
-static int64_t aov_through_path_bytes(int max_depth) { return 172 + 12 * (int64_t)max_depth; }
+static int64_t aov_through_path_bytes(int max_depth, bool emission) {
+  return (emission ? 188 : 172) + 12 * (int64_t)max_depth;
+}
 
 static int ensure_aov_through(AovState& A, size_t n, int depth, std::string& err) {
   const size_t words = 3 * n * (size_t)std::max(depth, 1);
@@ -1631,12 +1668,17 @@ static int ensure_aov_through(AovState& A, size_t n, int depth, std::string& err
   return 0;
 }
 
-int render_aov_through(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t npix, float* d_albedo,
-                       float* d_normal, float* d_depth, srr_aov_stats* stats, std::string& err) {
+// srr_render_aov_through (d_emission == nullptr) and the through-specular form of
+// srr_render_aov_emission
+static int aov_through(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t npix, float* d_albedo,
+                       float* d_normal, float* d_depth, float* d_emission, const int32_t* d_count,
+                       srr_aov_stats* stats, std::string& err) {
   RCHK(hipSetDevice(r->device));
-  const int64_t N = p->batch_paths > 0
-                        ? p->batch_paths
-                        : std::min<int64_t>((int64_t)1 << 20, kAovThroughBytes / aov_through_path_bytes(p->max_depth));
+  const int64_t N =
+      p->batch_paths > 0
+          ? p->batch_paths
+          : std::min<int64_t>((int64_t)1 << 20,
+                              kAovThroughBytes / aov_through_path_bytes(p->max_depth, d_emission != nullptr));
   const int64_t pix_chunk = std::min<int64_t>(npix, N);
   const int S = (int)std::max<int64_t>(1, std::min<int64_t>(p->spp, N / pix_chunk));
   const int64_t region = pix_chunk * S;
@@ -1648,8 +1690,10 @@ int render_aov_through(srr_renderer* r, const srr_params* p, const int32_t* pix,
   {  // every allocation comes before the first launch
     int rc = ensure_aov(A, (size_t)region, (size_t)npix, p->sample_begin + p->spp, err);
     if (rc == 0) rc = ensure_aov_through(A, (size_t)region, p->max_depth, err);
+    if (rc == 0 && d_emission) rc = ensure_aov_emission(A, (size_t)region, (size_t)npix, err);
     if (rc < 0) return rc;
   }
+  const bool old_three = d_albedo || d_normal || d_depth;
   srr_aov_stats s{};
   RCHK(hipMemcpyAsync(A.pixels.get(), pix, npix * sizeof(int32_t), hipMemcpyHostToDevice, A.st));
   for (int64_t p0 = 0; p0 < npix; p0 += pix_chunk) {
@@ -1684,6 +1728,7 @@ int render_aov_through(srr_renderer* r, const srr_params* p, const int32_t* pix,
         C.chain = A.chain;
         C.rec = A.rec;
         C.val = A.val;
+        C.emit = d_emission ? A.emit.get() : nullptr;
         launch_aov_chain(r->view, A.P, C, n, A.st);
         RCHK(hipMemcpyAsync(A.n_host.get(), count[cur ^ 1], sizeof(int32_t), hipMemcpyDeviceToHost, A.st));
         RCHK(hipStreamSynchronize(A.st));
@@ -1697,7 +1742,8 @@ int render_aov_through(srr_renderer* r, const srr_params* p, const int32_t* pix,
         }
         if (bounce == 0) s.chained_paths += n;
       }
-      launch_aov_fold(aov_fold(A, p, B, np, d_albedo, d_normal, d_depth), A.st);
+      if (old_three) launch_aov_fold(aov_fold(A, p, B, np, d_albedo, d_normal, d_depth), A.st);
+      if (d_emission) launch_aov_fold_emission(aov_fold_emission(A, p, B, np, d_count, d_emission), A.st);
     }
   }
   RCHK(hipGetLastError());
@@ -1707,6 +1753,23 @@ int render_aov_through(srr_renderer* r, const srr_params* p, const int32_t* pix,
     *stats = s;
   }
   return 0;
+}
+
+int render_aov_through(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t npix, float* d_albedo,
+                       float* d_normal, float* d_depth, srr_aov_stats* stats, std::string& err) {
+  return aov_through(r, p, pix, npix, d_albedo, d_normal, d_depth, nullptr, nullptr, stats, err);
+}
+
+int render_aov_emission(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t npix, int through,
+                        float* d_albedo, float* d_normal, float* d_depth, float* d_emission, const int32_t* d_count,
+                        srr_aov_stats* stats, std::string& err) {
+  if (through) return aov_through(r, p, pix, npix, d_albedo, d_normal, d_depth, d_emission, d_count, stats, err);
+  const int rc = aov_first_hit(r, p, pix, npix, d_albedo, d_normal, d_depth, d_emission, d_count, err);
+  if (rc == 0 && stats) {  // every path is its primary ray
+    const int64_t paths = npix * (int64_t)p->spp;
+    *stats = srr_aov_stats{stats->struct_size, 0, paths, paths, 0};
+  }
+  return rc;
 }
 
 }  // namespace srr

@@ -135,6 +135,10 @@ struct AovState {
   float* rec = nullptr;      // kernels.h AovChain::rec
   DeviceBag t_bufs;          // what next, chain and rec point to
   PinnedMem<int32_t> n_host;  // mirror of the next bounce's active count
+  // srr_render_aov_emission only (renderer.cpp ensure_aov_emission), allocated the first time
+  // SRR_AOV_EMISSION is asked for
+  DeviceMem<float4> emit;    // [>= the call's batch] per-path (emission.rgb, 0)
+  DeviceMem<float> acc_e;    // [pixels][4] the emission's sums
 };
 
 struct Multi;  // multi.h
@@ -222,6 +226,12 @@ int render_aov(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t
 // srr_render_aov_through likewise; stats may be nullptr
 int render_aov_through(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t npix, float* d_albedo,
                        float* d_normal, float* d_depth, srr_aov_stats* stats, std::string& err);
+// srr_render_aov_emission likewise: d_emission != nullptr adds the emission buffer (folded over
+// the first d_count[i] samples of the range per pixel when d_count != nullptr), through != 0
+// takes render_aov_through's chain; stats may be nullptr (first hit: paths and world_rays)
+int render_aov_emission(srr_renderer* r, const srr_params* p, const int32_t* pix, int64_t npix, int through,
+                        float* d_albedo, float* d_normal, float* d_depth, float* d_emission, const int32_t* d_count,
+                        srr_aov_stats* stats, std::string& err);
 // The pixel list and the running sums hold npix pixels (contents not preserved).  Growing
 // replaces both buffers, and the held list (pix_key) and the running sums' bookkeeping
 // (acc_npix, acc_samples, acc_key) are forgotten with them; on failure both are empty.

@@ -22,6 +22,7 @@ FLAG_SUMS = 32
 AOV_ALBEDO = 1
 AOV_NORMAL = 2
 AOV_DEPTH = 4
+AOV_EMISSION = 8
 DENOISE_DEMODULATE = 1
 
 
@@ -194,6 +195,14 @@ def lib():
             L.srr_denoise_var_defaults.argtypes = [dvp]
             L.srr_denoise_var.argtypes = [ip, ip, ip, dvp, vp, vp, vp, vp, vp, vp, vp]
             L.srr_denoise_var_host.argtypes = [ip, ip, ip, dvp, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "srr_render_aov_emission"):  # (as above)
+            L.srr_render_aov_emission.argtypes = [vp, ctypes.POINTER(Params), ip, ip, vp, vp, vp, vp, vp,
+                                                  ctypes.POINTER(AovStats)]
+            L.srr_render_aov_emission_host.argtypes = L.srr_render_aov_emission.argtypes
+            L.srr_denoise_emission.argtypes = [ip, ip, ip, dpp, vp, vp, vp, vp, vp, vp]
+            L.srr_denoise_emission_host.argtypes = L.srr_denoise_emission.argtypes
+            L.srr_denoise_var_emission.argtypes = [ip, ip, ip, dvp, vp, vp, vp, vp, vp, vp, vp, vp]
+            L.srr_denoise_var_emission_host.argtypes = L.srr_denoise_var_emission.argtypes
         _LIB = L
     return _LIB
 
@@ -444,15 +453,22 @@ class Renderer:
                                            ctypes.c_void_p(d_var_ptr or None)))
 
     def render_aov(self, nx, ny, spp, which=AOV_ALBEDO | AOV_NORMAL | AOV_DEPTH, max_depth=50,
-                   through_specular=False, **kw):
+                   through_specular=False, count=None, **kw):
         """First-hit feature buffers (srr_render_aov_host) of the samples
         [sample_begin, sample_begin + spp): dict(albedo[n,3], normal[n,3], depth[n])
         with the buffers selected in `which`; kw as make_params.  through_specular: the
         buffers of the first hit that is neither metal nor dielectric instead
-        (srr_render_aov_through_host), and the call's srr_aov_stats under "stats"."""
+        (srr_render_aov_through_host), and the call's srr_aov_stats under "stats".
+        With AOV_EMISSION in `which` the call is srr_render_aov_emission_host: the dict
+        gains emission[n,3] and "stats"; count[n] (int32, 1..spp) folds pixel i's emission
+        over its first count[i] samples only."""
         p = make_params(nx, ny, spp, max_depth, **kw)
         n = shard_pixels(p).size
         out = {}
+        if which & AOV_EMISSION:
+            return self._render_aov_emission(p, n, which, through_specular, count)
+        if count is not None:
+            raise SrrError("render_aov: count= needs AOV_EMISSION in which")
         if which & AOV_ALBEDO:
             out["albedo"] = np.zeros((n, 3), np.float32)
         if which & AOV_NORMAL:
@@ -468,12 +484,41 @@ class Renderer:
             _check(lib().srr_render_aov_host(self.h, ctypes.byref(p), which, *bufs))
         return out
 
+    def _render_aov_emission(self, p, n, which, through_specular, count):
+        out = {}
+        if which & AOV_ALBEDO:
+            out["albedo"] = np.zeros((n, 3), np.float32)
+        if which & AOV_NORMAL:
+            out["normal"] = np.zeros((n, 3), np.float32)
+        if which & AOV_DEPTH:
+            out["depth"] = np.zeros(n, np.float32)
+        out["emission"] = np.zeros((n, 3), np.float32)
+        if count is not None:
+            count = np.ascontiguousarray(count, np.int32).ravel()
+            if count.size != n:
+                raise SrrError("render_aov: count needs one int32 per shard pixel")
+        st = AovStats(ctypes.sizeof(AovStats))
+        _check(lib().srr_render_aov_emission_host(
+            self.h, ctypes.byref(p), which, int(through_specular), _ptr(out.get("albedo")), _ptr(out.get("normal")), _ptr(out.get("depth")), _ptr(out["emission"]),
+            _ptr(count), ctypes.byref(st)))
+        out["stats"] = st.as_dict()
+        return out
+
     def render_aov_device(self, params: Params, which: int, d_albedo_ptr: int = 0, d_normal_ptr: int = 0,
-                          d_depth_ptr: int = 0, through_specular=False):
+                          d_depth_ptr: int = 0, through_specular=False, d_emission_ptr: int = 0,
+                          d_count_ptr: int = 0):
         """srr_render_aov into device buffers (e.g. torch tensors' data_ptr());
-        through_specular: srr_render_aov_through, returning its stats as a dict."""
+        through_specular: srr_render_aov_through, returning its stats as a dict.  With
+        AOV_EMISSION in `which`: srr_render_aov_emission with d_emission_ptr and the optional
+        d_count_ptr, returning its stats."""
         bufs = (ctypes.c_void_p(d_albedo_ptr or None), ctypes.c_void_p(d_normal_ptr or None),
                 ctypes.c_void_p(d_depth_ptr or None))
+        if which & AOV_EMISSION:
+            st = AovStats(ctypes.sizeof(AovStats))
+            _check(lib().srr_render_aov_emission(self.h, ctypes.byref(params), which, int(through_specular), *bufs,
+                                                 ctypes.c_void_p(d_emission_ptr or None),
+                                                 ctypes.c_void_p(d_count_ptr or None), ctypes.byref(st)))
+            return st.as_dict()
         if not through_specular:
             _check(lib().srr_render_aov(self.h, ctypes.byref(params), which, *bufs))
             return None
@@ -518,9 +563,18 @@ def adaptive_converged(n, s1, s2, rel_tol, abs_eps) -> bool:
     return bool(lib().srr_adaptive_converged(int(n), float(s1), float(s2), float(rel_tol), float(abs_eps)))
 
 
-def denoise(color, albedo, normal, depth, params: DenoiseParams = None, device: int = 0) -> np.ndarray:
+def _emission_image(emission, color, fn):
+    emission = np.ascontiguousarray(emission, np.float32)
+    if emission.size != color.size:
+        raise SrrError(f"{fn}: emission needs ny*nx*3 floats")
+    return emission
+
+
+def denoise(color, albedo, normal, depth, params: DenoiseParams = None, device: int = 0,
+            emission=None) -> np.ndarray:
     """The a-trous denoiser (srr_denoise_host) over whole images in PPM order:
-    color, albedo, normal [ny, nx, 3], depth [ny, nx] -> the filtered [ny, nx, 3]."""
+    color, albedo, normal [ny, nx, 3], depth [ny, nx] -> the filtered [ny, nx, 3].
+    emission [ny, nx, 3]: filter color - emission and add it back (srr_denoise_emission_host)."""
     color = np.ascontiguousarray(color, np.float32)
     if color.ndim != 3 or color.shape[2] != 3:
         raise SrrError("denoise needs color[ny, nx, 3]")
@@ -532,6 +586,11 @@ def denoise(color, albedo, normal, depth, params: DenoiseParams = None, device: 
         raise SrrError("denoise: albedo and normal need ny*nx*3 floats, depth ny*nx")
     dp = params if params is not None else DenoiseParams.defaults()
     out = np.zeros_like(color)
+    if emission is not None:
+        emission = _emission_image(emission, color, "denoise")
+        _check(lib().srr_denoise_emission_host(device, nx, ny, ctypes.byref(dp), _ptr(color), _ptr(emission),
+                                               _ptr(albedo), _ptr(normal), _ptr(depth), _ptr(out)))
+        return out
     _check(lib().srr_denoise_host(device, nx, ny, ctypes.byref(dp), _ptr(color), _ptr(albedo), _ptr(normal),
                                   _ptr(depth), _ptr(out)))
     return out
@@ -543,10 +602,11 @@ def variance_of_mean(n, s1, s2) -> np.float32:
 
 
 def denoise_var(color, var, albedo, normal, depth, params: DenoiseVarParams = None, device: int = 0,
-                want_var: bool = True):
+                want_var: bool = True, emission=None):
     """The variance-guided a-trous filter (srr_denoise_var_host) over whole images in PPM
     order: color, albedo, normal [ny, nx, 3], var, depth [ny, nx] -> (out [ny, nx, 3],
-    var_out [ny, nx]); var_out is None when want_var is false (d_var_out = NULL)."""
+    var_out [ny, nx]); var_out is None when want_var is false (d_var_out = NULL).
+    emission [ny, nx, 3]: filter color - emission and add it back (srr_denoise_var_emission_host)."""
     color = np.ascontiguousarray(color, np.float32)
     if color.ndim != 3 or color.shape[2] != 3:
         raise SrrError("denoise_var needs color[ny, nx, 3]")
@@ -561,6 +621,12 @@ def denoise_var(color, var, albedo, normal, depth, params: DenoiseVarParams = No
     dp = params if params is not None else DenoiseVarParams.defaults()
     out = np.zeros_like(color)
     var_out = np.zeros((ny, nx), np.float32) if want_var else None
+    if emission is not None:
+        emission = _emission_image(emission, color, "denoise_var")
+        _check(lib().srr_denoise_var_emission_host(device, nx, ny, ctypes.byref(dp), _ptr(color), _ptr(var),
+                                                   _ptr(emission), _ptr(albedo), _ptr(normal), _ptr(depth),
+                                                   _ptr(out), _ptr(var_out)))
+        return out, var_out
     _check(lib().srr_denoise_var_host(device, nx, ny, ctypes.byref(dp), _ptr(color), _ptr(var), _ptr(albedo),
                                       _ptr(normal), _ptr(depth), _ptr(out), _ptr(var_out)))
     return out, var_out

@@ -23,6 +23,9 @@ n_i samples is bitwise the fixed-spp frame at n_i, however the budget was steppe
 (srr_adaptive_speculate): the same frames in fewer passes.
 ``denoise`` may then also be a capi.DenoiseVarParams: step() returns srr_denoise_var
 of the mean, the variance of the pixels' mean luminance and the AOVs.
+``denoise_emission`` filters the frame less its emission (srr_render_aov_emission over the
+samples the frame holds -- per-pixel counts for an adaptive frame --, rendered again
+whenever those change) and adds it back: srr_denoise_emission / srr_denoise_var_emission.
 """
 from __future__ import annotations
 
@@ -37,7 +40,7 @@ from . import capi
 class Progressive:
     def __init__(self, renderer: "capi.Renderer", nx: int, ny: int, max_depth: int = 50, flags: int = 0,
                  denoise=None, aov_spp: int = 16, adaptive=None, pass_spp_max: int = 0, fill_paths: int = 0,
-                 aov_through_specular: bool = False, **params):
+                 aov_through_specular: bool = False, denoise_emission: bool = False, **params):
         self.r = renderer
         self.nx, self.ny, self.max_depth = nx, ny, max_depth
         self.flags = flags  # engine flags (e.g. capi.FLAG_WAVEFRONT)
@@ -62,6 +65,9 @@ class Progressive:
         self.denoise = capi.DenoiseParams.defaults() if denoise is True else (denoise or None)
         self.aov_spp = aov_spp
         self.aov_through_specular = bool(aov_through_specular)
+        self.denoise_emission = bool(denoise_emission)
+        if self.denoise_emission and self.denoise is None:
+            raise capi.SrrError("denoise_emission needs a denoiser: set denoise")
         self.denoised = None
         self._aov = None
         if self.denoise is not None and params.get("shard", (0, 1))[1] > 1:
@@ -85,13 +91,23 @@ class Progressive:
         shape = (self.ny, self.nx, 3)
         a = self._aov
         self.denoised = capi.denoise(self.mean.reshape(shape), a["albedo"].reshape(shape), a["normal"].reshape(shape),
-                                     a["depth"].reshape(self.ny, self.nx), self.denoise).reshape(-1, 3)
+                                     a["depth"].reshape(self.ny, self.nx), self.denoise,
+                                     emission=self._render_emission(self.samples, None)).reshape(-1, 3)
         return self.denoised
 
     def _render_aov(self) -> dict:
         kw = {k: v for k, v in self.params.items() if k in ("base_seed", "batch_paths")}
         return self.r.render_aov(self.nx, self.ny, self.aov_spp, max_depth=self.max_depth,
                                  through_specular=self.aov_through_specular, **kw)
+
+    def _render_emission(self, spp: int, count):
+        """The emission of the samples the frame holds now ([ny, nx, 3]), or None when not asked for."""
+        if not self.denoise_emission:
+            return None
+        kw = {k: v for k, v in self.params.items() if k in ("base_seed", "batch_paths")}
+        em = self.r.render_aov(self.nx, self.ny, spp, capi.AOV_EMISSION, max_depth=self.max_depth,
+                               through_specular=self.aov_through_specular, count=count, **kw)["emission"]
+        return em.reshape(self.ny, self.nx, 3)
 
     def _step_adaptive(self, spp: int) -> np.ndarray:
         a = self.adaptive
@@ -108,12 +124,14 @@ class Progressive:
         shape = (self.ny, self.nx, 3)
         aov = self._aov
         feats = (aov["albedo"].reshape(shape), aov["normal"].reshape(shape), aov["depth"].reshape(self.ny, self.nx))
+        emission = self._render_emission(self.samples, self.count)  # (a pixel's count never exceeds the budget)
         if isinstance(self.denoise, capi.DenoiseVarParams):
             # (no shard: the shard's pixel order is PPM order, nothing to scatter)
             var = self.r.adaptive_variance(self.count).reshape(self.ny, self.nx)
-            den, _ = capi.denoise_var(self.mean.reshape(shape), var, *feats, self.denoise, want_var=False)
+            den, _ = capi.denoise_var(self.mean.reshape(shape), var, *feats, self.denoise, want_var=False,
+                                      emission=emission)
         else:
-            den = capi.denoise(self.mean.reshape(shape), *feats, self.denoise)
+            den = capi.denoise(self.mean.reshape(shape), *feats, self.denoise, emission=emission)
         self.denoised = den.reshape(-1, 3)
         return self.denoised
 

@@ -25,6 +25,11 @@ format of Raytracing_n.cpp:850-886).
                                            (with --denoise, --denoise-var or --aov-out: their AOVs are those of
                                             the first hit that is neither metal nor dielectric,
                                             srr_render_aov_through; one GPU)
+                              [--denoise-emission]
+                                           (with --denoise or --denoise-var: the filter runs on the frame less
+                                            its emission, srr_render_aov_emission over the frame's own samples
+                                            -- the adaptive frame's counts under --adaptive -- and adds it back;
+                                            --aov-out also writes PREFIX_emission.png; one GPU)
 
 Defaults are the reference's globals (Raytracing_n.cpp:39-43).  Differences, all
 forced by the reference: its 8 render threads race on shared state
@@ -77,6 +82,8 @@ def parse(argv=None):
     ap.add_argument("--aov-through-specular", action="store_true",
                     help="the AOVs of --denoise, --denoise-var and --aov-out follow mirrors and glass to the first "
                          "diffuse hit (one GPU)")
+    ap.add_argument("--denoise-emission", action="store_true",
+                    help="with --denoise or --denoise-var: filter the frame less its emission and add it back (one GPU)")
     return ap.parse_args(argv)
 
 
@@ -114,6 +121,12 @@ def main(argv=None) -> int:
     if a.aov_through_specular and a.gpus != 1:
         print("--aov-through-specular needs one GPU", file=sys.stderr)
         return 2
+    if a.denoise_emission and not (a.denoise or a.denoise_var):
+        print("--denoise-emission needs --denoise or --denoise-var", file=sys.stderr)
+        return 2
+    if a.denoise_emission and a.gpus != 1:
+        print("--denoise-emission needs one GPU", file=sys.stderr)
+        return 2
     sc = ref_scenes.BY_SCENEID[a.sceneid](float(a.nx) / float(a.ny), contents=a.contents)  # :894-919
     r = (capi.Renderer(sc.text(), device=a.device) if a.gpus == 1 else
          capi.Renderer(sc.text(), devices=list(range(a.device, a.device + a.gpus))))
@@ -139,21 +152,29 @@ def main(argv=None) -> int:
     if a.denoise or a.denoise_var or a.aov_out:
         aov = r.render_aov(a.nx, a.ny, a.aov_spp or min(a.ns, 16), max_depth=a.max_depth,
                            through_specular=a.aov_through_specular)
+        emission = None
+        if a.denoise_emission:  # the emission of exactly the samples the frame holds, in a call of its own
+            em = r.render_aov(a.nx, a.ny, a.ns, capi.AOV_EMISSION, max_depth=a.max_depth,
+                              through_specular=a.aov_through_specular,
+                              count=out["count"] if a.adaptive is not None else None)["emission"]
+            emission = em.reshape(a.ny, a.nx, 3)
         if a.denoise:
             shape = (a.ny, a.nx, 3)
             den = capi.denoise(out["mean"].reshape(shape), aov["albedo"].reshape(shape), aov["normal"].reshape(shape),
-                               aov["depth"].reshape(a.ny, a.nx), device=a.device)
+                               aov["depth"].reshape(a.ny, a.nx), device=a.device, emission=emission)
             out["img8"] = capi.tonemap(den.reshape(-1, 3))
         if a.denoise_var:
             shape = (a.ny, a.nx, 3)
             var = r.adaptive_variance(out["count"])
             den, _ = capi.denoise_var(out["mean"].reshape(shape), var.reshape(a.ny, a.nx), aov["albedo"].reshape(shape),
                                       aov["normal"].reshape(shape), aov["depth"].reshape(a.ny, a.nx), device=a.device,
-                                      want_var=False)
+                                      want_var=False, emission=emission)
             out["img8"] = capi.tonemap(den.reshape(-1, 3))
         if a.aov_out:
             for k, img in aov_images(aov).items():
                 capi.write_png(f"{a.aov_out}_{k}.png", a.nx, a.ny, img)
+            if emission is not None:  # tone-mapped like the frame
+                capi.write_png(f"{a.aov_out}_emission.png", a.nx, a.ny, capi.tonemap(emission.reshape(-1, 3)))
     ms = (time.perf_counter() - t0) * 1e3
     print(f"{int(ms)}ms")  # :944-947
     capi.write_ppm(a.out, a.nx, a.ny, out["img8"])
