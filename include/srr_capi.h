@@ -847,6 +847,88 @@ int srr_bounce_kat_counts(const char* scene_text, int list, int32_t* counts);
  * arguments: SRR_EINVAL, decided before the GPU is touched.  Otherwise needs a GPU. */
 int srr_device_libm(const char* fn, int64_t n, const void* x, const void* y, void* out0, void* out1);
 
+/* Test infrastructure: the kernels that turn samples into pixels, one launch wrapper
+ * of kernels.h per call on host buffers (stream 0), so that what runs is what a frame
+ * launches, the choice between a wrapper's kernels included.  One argument block serves
+ * every kind; a kind reads the fields listed for it and ignores the rest.  Arrays
+ * marked "io" are uploaded as given and downloaded after the launch, so what a kernel
+ * leaves alone comes back as it went in.  "opt" arrays may be NULL.
+ *
+ *   "window"  launch_accumulate_window: sample[rows][spp][3]; sums io [n_slots][3] is acc
+ *       (n_slots >= rows: the rows beyond are the caller's sentinel), init; mean opt io
+ *       [n_slots][3] is `out`: the raw sums with ns == 0, else sums * (float)(1.0 / ns).
+ *   "adaptive_fold"  launch_adaptive_fold (kernels.h AdaptiveFold): sample[rows][spp][3],
+ *       rows = n_active, active_slot opt [rows] into the n_slots slots (NULL: slot j,
+ *       n_slots >= rows); sums io [n_slots][3], mom io [n_slots][2], mean io [n_slots][3],
+ *       count opt io [n_slots], keep io [rows]; init, decide, n_new, budget, rel_tol, abs_eps.
+ *   "adaptive_fold_spec"  launch_adaptive_fold_spec (AdaptiveSpecFold), one window: the
+ *       fields of "adaptive_fold" without init, decide and n_new, count not optional, and
+ *       n, w, s0, batch_spp, min_spp, ctr io [2] (discarded, stopped).
+ *   "level_finish"  launch_adaptive_level_select, then launch_adaptive_finish, over n_slots
+ *       slots: count [n_slots], mom [n_slots][2], sums [n_slots][3] and the rule (budget,
+ *       min_spp, rel_tol, abs_eps) in; live io [n_slots], keep io [n_slots], lvl io [4]
+ *       (words: active, level, live, below; the first is left alone), mean io [n_slots][3],
+ *       count_out opt io [n_slots].
+ *   "compact"  launch_adaptive_compact: keep [rows], active_slot opt [rows] into n_slots,
+ *       pixels opt [n_slots] with values in [0, n_image); slot_out io [rows], pixel_out io
+ *       [rows], n_out io [1].
+ *   "aov_fold"  launch_aov_fold (AovFold): sample[rows][spp][8] is val, sums io [rows][8] is
+ *       acc; init, finish, ns, p0; albedo opt io [n_shard][3], normal opt io [n_shard][3],
+ *       depth opt io [n_shard].
+ *   "aov_fold_emission"  launch_aov_fold_emission (AovEmissionFold): sample[rows][spp][4] is
+ *       emit, s0, sums io [rows][4] is acc, ns, p0, count opt [n_shard] (any value: the
+ *       kernel clamps it into 1..ns), emission io [n_shard][3].
+ *   "finish"  launch_finish: sums [rows][3] in, ns, mean io [rows][3].
+ *   "scatter"  launch_scatter_pixels: sample[rows][3] is packed, index [rows] into the
+ *       n_image pixels of image io [n_image][3].
+ *
+ * misalign (0..3; "window" and the two adaptive folds) uploads the samples that many
+ * floats into a larger 16-byte-aligned allocation, which is how a test reaches the
+ * wrappers' route for samples that are not 16-byte aligned.
+ *
+ * SRR_EINVAL, decided before the GPU is touched: an unknown kind; a NULL array that is
+ * not optional; rows, spp, n_slots, n_shard or n_image not positive where the kind
+ * reads them, rows or n_slots above 2^24, spp above 2^16, or more than 2^28 sample
+ * floats (so no byte count overflows); misalign outside 0..3; n_slots < rows without
+ * active_slot; an active_slot entry outside [0, n_slots) or repeated; a pixels entry
+ * outside [0, n_image); an index entry outside [0, n_image); p0 < 0 or p0 + rows >
+ * n_shard; ns < 1 where a mean is taken ("window": ns < 0); n_new < 1, budget < 1,
+ * batch_spp < 1, min_spp < 0, n < 0, s0 < 0, s0 + spp > w, or n + w above 2^30; in a
+ * window with s0 > 0, a count of an active slot outside [0, n + w]; for "level_finish",
+ * a count outside [0, budget].  Otherwise needs a GPU. */
+typedef struct srr_fold_kat {
+  const float* sample;
+  int32_t rows, spp, misalign;
+  const int32_t* active_slot;
+  int32_t n_slots;
+  float* sums;
+  float* mom;
+  float* mean;
+  int32_t* count;
+  int32_t* count_out;
+  uint8_t* keep;
+  uint8_t* live;
+  int32_t* lvl;
+  uint64_t* ctr;
+  int32_t init, decide, finish;
+  int32_t n, w, s0, n_new;
+  int32_t batch_spp, min_spp, budget, ns;
+  float rel_tol, abs_eps;
+  const int32_t* pixels;
+  const int32_t* index;
+  int32_t n_image;
+  int32_t* slot_out;
+  int32_t* pixel_out;
+  int32_t* n_out;
+  int32_t p0, n_shard;
+  float* albedo;
+  float* normal;
+  float* depth;
+  float* emission;
+  float* image;
+} srr_fold_kat;
+int srr_device_fold_kat(const char* kind, const srr_fold_kat* a);
+
 /* Sobol (0,2)-points of Raytracing_n.cpp:721-812, out[n][2]. */
 int srr_sobol_points(int n, double* out);
 

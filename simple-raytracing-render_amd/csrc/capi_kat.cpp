@@ -1,7 +1,8 @@
 // The test entry points of the C-ABI (include/srr_capi.h): the device known-answer tests
 // (KATs) srr_device_kat, srr_device_mesh_kat, srr_device_world_kat, srr_device_bounce_kat with
-// their host-only *_kat_counts, and the libm sweeps srr_device_libm.  Each builds its device
-// tables with the host scene code a render uses, holds device memory in DevBuf
+// their host-only *_kat_counts, the fold and compaction KAT srr_device_fold_kat, and the libm
+// sweeps srr_device_libm.  Each builds its device
+// tables with the host scene code a render uses (the fold KAT has none), holds device memory in DevBuf
 // (capi_internal.h) and checks every argument before its first HIP call, so a refusal needs
 // no GPU.  The product's entry points are in capi.cpp.
 #include <cstdint>
@@ -393,9 +394,242 @@ int bounce_kat_flatten(Scene& sc, int l, Flat& f, std::string& err) {
   }
   return 0;
 }
+
+// ------------------------------------------------- the fold and compaction KAT
+constexpr int kFoldMaxRows = 1 << 24, kFoldMaxSpp = 1 << 16, kFoldMaxCount = 1 << 30;
+constexpr int64_t kFoldMaxFloats = (int64_t)1 << 28;
+
+int fold_bad(const std::string& what) { return fail(SRR_EINVAL, "fold KAT: " + what); }
+
+// every entry of idx[0 .. n) lies in [0, range); with `injective`, none is repeated
+bool fold_indices_ok(const int32_t* idx, int n, int range, bool injective) {
+  std::vector<uint8_t> seen(injective ? (size_t)range : 0, 0);
+  for (int j = 0; j < n; ++j) {
+    if (idx[j] < 0 || idx[j] >= range) return false;
+    if (injective && seen[idx[j]]++) return false;
+  }
+  return true;
+}
+
+// The samples on the device, `misalign` floats into a 16-byte-aligned allocation.
+struct FoldSamples {
+  DevBuf<float> buf;
+  const float* ptr;
+  FoldSamples(const float* host, size_t n, int misalign, int& rc) : buf(n ? n + 4 : 0, rc), ptr(nullptr) {
+    if (rc || !n) return;
+    ptr = buf.get() + misalign;
+    if (hipMemcpy(buf.get() + misalign, host, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+      rc = fail(SRR_EIO, "copy to device failed");
+  }
+};
+
+// An "io" array: a device copy of the caller's, written back by done(); NULL stays NULL.
+template <class T>
+struct FoldIo {
+  T* host;
+  size_t n;
+  DevBuf<T> buf;
+  FoldIo(T* h, size_t count, int& rc) : host(h), n(h ? count : 0), buf(h, h ? count : 0, rc) {}
+  T* get() const { return buf.get(); }
+  bool done() const { return !host || buf.download(host, n); }
+};
+
+// the checks of srr_device_fold_kat that need no device: 0, or the refusal
+int fold_kat_check(int kind, const srr_fold_kat& a) {
+  const int words = kFoldKats[kind].words;
+  const bool rows_used = kind != kFoldLevelFinish;
+  const bool slots_used = kind == kFoldWindow || kind == kFoldAdaptive || kind == kFoldSpec || kind == kFoldLevelFinish ||
+                          (kind == kFoldCompact && (a.active_slot || a.pixels));
+  const bool spp_used = words != 0 && kind != kFoldScatter;
+  if (rows_used && (a.rows <= 0 || a.rows > kFoldMaxRows)) return fold_bad("rows out of range");
+  if (slots_used && (a.n_slots <= 0 || a.n_slots > kFoldMaxRows)) return fold_bad("n_slots out of range");
+  if (spp_used && (a.spp <= 0 || a.spp > kFoldMaxSpp)) return fold_bad("spp out of range");
+  if (spp_used && (int64_t)a.rows * a.spp * words > kFoldMaxFloats) return fold_bad("too many samples");
+  if (words && !a.sample) return fold_bad("no samples");
+  const bool folds = kind == kFoldWindow || kind == kFoldAdaptive || kind == kFoldSpec;
+  if (a.misalign < 0 || a.misalign > 3 || (a.misalign && !folds)) return fold_bad("misalign out of range");
+  if (folds || kind == kFoldCompact) {
+    if (kind == kFoldWindow && a.active_slot) return fold_bad("the window sums take no active_slot");
+    if (a.active_slot) {
+      if (!fold_indices_ok(a.active_slot, a.rows, a.n_slots, true))
+        return fold_bad("an active_slot entry is out of range or repeated");
+    } else if (slots_used && a.n_slots < a.rows) {
+      return fold_bad("n_slots < rows without active_slot");
+    }
+  }
+  switch (kind) {
+    case kFoldWindow:
+      if (!a.sums) return fold_bad("no acc");
+      if (a.ns < 0) return fold_bad("ns out of range");
+      break;
+    case kFoldAdaptive:
+    case kFoldSpec:
+      if (!a.sums || !a.mom || !a.mean || !a.keep) return fold_bad("a state array is missing");
+      if (a.budget < 1) return fold_bad("budget out of range");
+      if (kind == kFoldAdaptive) {
+        if (a.n_new < 1 || a.n_new > kFoldMaxCount) return fold_bad("n_new out of range");
+        break;
+      }
+      if (!a.count || !a.ctr) return fold_bad("count or ctr is missing");
+      if (a.batch_spp < 1) return fold_bad("batch_spp out of range");
+      if (a.min_spp < 0 || a.n < 0 || a.s0 < 0 || a.w < 1 || a.n > kFoldMaxCount || a.w > kFoldMaxCount ||
+          (int64_t)a.n + a.w > kFoldMaxCount)
+        return fold_bad("n, w, s0 or min_spp out of range");
+      if ((int64_t)a.s0 + a.spp > a.w) return fold_bad("s0 + spp_w > w");
+      if (a.s0 > 0)
+        for (int j = 0; j < a.rows; ++j) {
+          const int32_t c = a.count[a.active_slot ? a.active_slot[j] : j];
+          if (c < 0 || c > a.n + a.w) return fold_bad("a count outside [0, n + w]");
+        }
+      break;
+    case kFoldLevelFinish:
+      if (!a.count || !a.mom || !a.sums || !a.live || !a.keep || !a.lvl || !a.mean) return fold_bad("an array is missing");
+      if (a.budget < 1 || a.min_spp < 0) return fold_bad("budget or min_spp out of range");
+      for (int i = 0; i < a.n_slots; ++i)
+        if (a.count[i] < 0 || a.count[i] > a.budget) return fold_bad("a count outside [0, budget]");
+      break;
+    case kFoldCompact:
+      if (!a.keep || !a.slot_out || !a.pixel_out || !a.n_out) return fold_bad("an array is missing");
+      if (a.pixels && (a.n_image <= 0 || !fold_indices_ok(a.pixels, a.n_slots, a.n_image, false)))
+        return fold_bad("a pixels entry is outside the output");
+      break;
+    case kFoldAov:
+    case kFoldAovEmission:
+      if (!a.sums) return fold_bad("no acc");
+      if (a.n_shard <= 0 || a.n_shard > kFoldMaxRows || a.p0 < 0 || (int64_t)a.p0 + a.rows > a.n_shard)
+        return fold_bad("p0 + np beyond the shard's pixels");
+      if (a.ns < 1) return fold_bad("ns out of range");
+      if (kind == kFoldAovEmission && (!a.emission || a.s0 < 0 || a.s0 > kFoldMaxCount)) return fold_bad("no emission, or s0 out of range");
+      break;
+    case kFoldFinish:
+      if (!a.sums || !a.mean) return fold_bad("an array is missing");
+      if (a.ns < 1) return fold_bad("ns out of range");
+      break;
+    case kFoldScatter:
+      if (!a.index || !a.image) return fold_bad("an array is missing");
+      if (a.n_image <= 0 || a.n_image > kFoldMaxRows || !fold_indices_ok(a.index, a.rows, a.n_image, false))
+        return fold_bad("an index entry is outside the image");
+      break;
+  }
+  return 0;
+}
 }  // namespace
 
 extern "C" {
+
+int srr_device_fold_kat(const char* kind_name, const srr_fold_kat* ap) {
+  // every argument is checked before the first HIP call, so a refusal needs no GPU
+  if (!kind_name || !ap) return fold_bad("bad arguments");
+  int kind = -1;
+  for (const FoldKatDesc& d : kFoldKats)
+    if (!strcmp(kind_name, d.name)) kind = d.kind;
+  if (kind < 0) return fold_bad(std::string("no kind named ") + kind_name);
+  const srr_fold_kat& a = *ap;
+  if (const int bad = fold_kat_check(kind, a)) return bad;
+
+  const int words = kFoldKats[kind].words;
+  const size_t rows = kind == kFoldLevelFinish ? 0 : (size_t)a.rows;
+  const size_t slots = kind == kFoldCompact && !a.active_slot && !a.pixels ? rows : (size_t)a.n_slots;
+  const size_t n_samples = !words ? 0 : rows * (kind == kFoldScatter ? 1 : (size_t)a.spp) * words;
+  int rc = 0;
+  FoldSamples sample(a.sample, n_samples, a.misalign, rc);
+  if (rc) return rc;
+  const char* what = "fold KAT kernel failed";
+  auto ran = [&]() { return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess; };
+  switch (kind) {
+    case kFoldWindow: {
+      FoldIo<float> acc(a.sums, 3 * slots, rc), out(a.mean, 3 * slots, rc);
+      if (rc) return rc;
+      launch_accumulate_window(sample.ptr, a.rows, a.spp, acc.get(), 0, a.init != 0, out.get(), a.ns);
+      if (!ran() || !acc.done() || !out.done()) return fail(SRR_EIO, what);
+      return 0;
+    }
+    case kFoldAdaptive:
+    case kFoldSpec: {
+      DevBuf<int32_t> active(a.active_slot, a.active_slot ? rows : 0, rc);
+      FoldIo<float> sums(a.sums, 3 * slots, rc), mom(a.mom, 2 * slots, rc), mean(a.mean, 3 * slots, rc);
+      FoldIo<int32_t> count(a.count, slots, rc);
+      FoldIo<uint8_t> keep(a.keep, rows, rc);
+      FoldIo<unsigned long long> ctr((unsigned long long*)a.ctr, kind == kFoldSpec ? kSpecWords : 0, rc);
+      if (rc) return rc;
+      if (kind == kFoldAdaptive) {
+        const AdaptiveFold A{sample.ptr, active.get(), a.rows, a.spp, sums.get(), (float2*)mom.get(), a.init, a.decide,
+                             a.n_new, a.budget, a.rel_tol, a.abs_eps, keep.get(), mean.get(), count.get()};
+        launch_adaptive_fold(A, 0);
+      } else {
+        const AdaptiveSpecFold A{sample.ptr, active.get(), a.rows, a.spp, sums.get(), (float2*)mom.get(), a.n, a.w, a.s0,
+                                 a.batch_spp, a.min_spp, a.budget, a.rel_tol, a.abs_eps, keep.get(), mean.get(),
+                                 count.get(), ctr.get()};
+        launch_adaptive_fold_spec(A, 0);
+      }
+      if (!ran() || !sums.done() || !mom.done() || !mean.done() || !count.done() || !keep.done() || !ctr.done())
+        return fail(SRR_EIO, what);
+      return 0;
+    }
+    case kFoldLevelFinish: {
+      DevBuf<int32_t> count(a.count, slots, rc);
+      DevBuf<float> mom(a.mom, 2 * slots, rc), sums(a.sums, 3 * slots, rc);
+      FoldIo<uint8_t> live(a.live, slots, rc), keep(a.keep, slots, rc);
+      FoldIo<int32_t> lvl(a.lvl, kLvlWords, rc), count_out(a.count_out, slots, rc);
+      FoldIo<float> mean(a.mean, 3 * slots, rc);
+      if (rc) return rc;
+      const AdaptiveRule R{a.budget, a.min_spp, a.rel_tol, a.abs_eps};
+      launch_adaptive_level_select(a.n_slots, count.get(), (const float2*)mom.get(), R, live.get(), keep.get(), lvl.get(), 0);
+      launch_adaptive_finish(a.n_slots, sums.get(), count.get(), a.budget, mean.get(), count_out.get(), lvl.get(), 0);
+      if (!ran() || !live.done() || !keep.done() || !lvl.done() || !count_out.done() || !mean.done())
+        return fail(SRR_EIO, what);
+      return 0;
+    }
+    case kFoldCompact: {
+      DevBuf<uint8_t> keep(a.keep, rows, rc);
+      DevBuf<int32_t> active(a.active_slot, a.active_slot ? rows : 0, rc), pixels(a.pixels, a.pixels ? slots : 0, rc);
+      DevBuf<int32_t> blk((rows + 255) / 256, rc);
+      FoldIo<int32_t> slot_out(a.slot_out, rows, rc), pixel_out(a.pixel_out, rows, rc), n_out(a.n_out, 1, rc);
+      if (rc) return rc;
+      launch_adaptive_compact(keep.get(), active.get(), a.rows, pixels.get(), blk.get(), slot_out.get(), pixel_out.get(),
+                              n_out.get(), 0);
+      if (!ran() || !slot_out.done() || !pixel_out.done() || !n_out.done()) return fail(SRR_EIO, what);
+      return 0;
+    }
+    case kFoldAov: {
+      const size_t shard = (size_t)a.n_shard;
+      FoldIo<float> acc(a.sums, 8 * rows, rc), albedo(a.albedo, 3 * shard, rc), normal(a.normal, 3 * shard, rc),
+          depth(a.depth, shard, rc);
+      if (rc) return rc;
+      const AovFold A{sample.ptr, a.rows, a.spp, acc.get(), a.init, a.finish, a.ns, a.p0, albedo.get(), normal.get(),
+                      depth.get()};
+      launch_aov_fold(A, 0);
+      if (!ran() || !acc.done() || !albedo.done() || !normal.done() || !depth.done()) return fail(SRR_EIO, what);
+      return 0;
+    }
+    case kFoldAovEmission: {
+      const size_t shard = (size_t)a.n_shard;
+      FoldIo<float> acc(a.sums, 4 * rows, rc), emission(a.emission, 3 * shard, rc);
+      DevBuf<int32_t> count(a.count, a.count ? shard : 0, rc);
+      if (rc) return rc;
+      const AovEmissionFold A{sample.ptr, a.rows, a.spp, a.s0, acc.get(), a.ns, a.p0, count.get(), emission.get()};
+      launch_aov_fold_emission(A, 0);
+      if (!ran() || !acc.done() || !emission.done()) return fail(SRR_EIO, what);
+      return 0;
+    }
+    case kFoldFinish: {
+      DevBuf<float> acc(a.sums, 3 * rows, rc);
+      FoldIo<float> mean(a.mean, 3 * rows, rc);
+      if (rc) return rc;
+      launch_finish(acc.get(), mean.get(), a.rows, a.ns, 0);
+      if (!ran() || !mean.done()) return fail(SRR_EIO, what);
+      return 0;
+    }
+    default: {  // kFoldScatter
+      DevBuf<int32_t> index(a.index, rows, rc);
+      FoldIo<float> image(a.image, 3 * (size_t)a.n_image, rc);
+      if (rc) return rc;
+      launch_scatter_pixels(sample.ptr, index.get(), a.rows, image.get(), 0);
+      if (!ran() || !image.done()) return fail(SRR_EIO, what);
+      return 0;
+    }
+  }
+}
 
 int srr_device_kat(const char* name, int n, int width, float* records) {
   if (!name || !records || n <= 0 || width <= 0) return fail(SRR_EINVAL, "bad KAT arguments");

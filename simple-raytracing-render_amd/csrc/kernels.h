@@ -399,6 +399,27 @@ constexpr bool libm_table_in_id_order() {
 }
 static_assert(kLibmFnCount == kLibmOcmlPow5 + 1 && libm_table_in_id_order(), "kLibmFns[i] must be LibmId i");
 int launch_libm(int fn, int64_t n, const void* d_x, const void* d_y, void* d_out0, void* d_out1);
+// the fold and compaction KAT (srr_device_fold_kat): no kernel of its own -- each kind runs the
+// launch wrapper below that a frame runs, on the caller's buffers.  Row i is kind i; words: the
+// floats per sample of the kind's sample array (0: the kind has none)
+enum FoldKatKind : int { kFoldWindow, kFoldAdaptive, kFoldSpec, kFoldLevelFinish, kFoldCompact, kFoldAov,
+                         kFoldAovEmission, kFoldFinish, kFoldScatter };
+struct FoldKatDesc {
+  FoldKatKind kind;
+  const char* name;
+  int words;
+};
+constexpr FoldKatDesc kFoldKats[] = {
+    {kFoldWindow, "window", 3},    {kFoldAdaptive, "adaptive_fold", 3},        {kFoldSpec, "adaptive_fold_spec", 3},
+    {kFoldLevelFinish, "level_finish", 0}, {kFoldCompact, "compact", 0},       {kFoldAov, "aov_fold", 8},
+    {kFoldAovEmission, "aov_fold_emission", 4}, {kFoldFinish, "finish", 0},    {kFoldScatter, "scatter", 3}};
+constexpr int kFoldKatCount = (int)(sizeof(kFoldKats) / sizeof(kFoldKats[0]));
+constexpr bool fold_table_in_kind_order() {
+  for (int i = 0; i < kFoldKatCount; ++i)
+    if ((int)kFoldKats[i].kind != i) return false;
+  return true;
+}
+static_assert(kFoldKatCount == kFoldScatter + 1 && fold_table_in_kind_order(), "kFoldKats[i] must be FoldKatKind i");
 // MERL table lookup (merl.h) for n queries; device pointers
 int launch_merl_lookup(const double* table, int64_t n, const double* angles, double* rgb, int32_t* cell);
 // acc[pixel] (+)= the window's samples in order; init: acc starts at 0 (no

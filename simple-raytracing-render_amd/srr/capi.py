@@ -714,6 +714,48 @@ def bounce_kat_counts(scene_text: str, light_list: int) -> dict:
                 materials=int(c[5]))
 
 
+class FoldKat(ctypes.Structure):
+    """srr_fold_kat of include/srr_capi.h."""
+    _i, _p = ctypes.c_int32, ctypes.c_void_p
+    _fields_ = [("sample", _p), ("rows", _i), ("spp", _i), ("misalign", _i), ("active_slot", _p), ("n_slots", _i),
+                ("sums", _p), ("mom", _p), ("mean", _p), ("count", _p), ("count_out", _p), ("keep", _p), ("live", _p),
+                ("lvl", _p), ("ctr", _p), ("init", _i), ("decide", _i), ("finish", _i), ("n", _i), ("w", _i),
+                ("s0", _i), ("n_new", _i), ("batch_spp", _i), ("min_spp", _i), ("budget", _i), ("ns", _i),
+                ("rel_tol", ctypes.c_float), ("abs_eps", ctypes.c_float), ("pixels", _p), ("index", _p),
+                ("n_image", _i), ("slot_out", _p), ("pixel_out", _p), ("n_out", _p), ("p0", _i), ("n_shard", _i),
+                ("albedo", _p), ("normal", _p), ("depth", _p), ("emission", _p), ("image", _p)]
+
+
+# the arrays of FoldKat and their element types; a call checks dtype and contiguity, never converts
+_FOLD_KAT_ARRAYS = dict(sample=np.float32, active_slot=np.int32, sums=np.float32, mom=np.float32, mean=np.float32,
+                        count=np.int32, count_out=np.int32, keep=np.uint8, live=np.uint8, lvl=np.int32, ctr=np.uint64,
+                        pixels=np.int32, index=np.int32, slot_out=np.int32, pixel_out=np.int32, n_out=np.int32,
+                        albedo=np.float32, normal=np.float32, depth=np.float32, emission=np.float32, image=np.float32)
+
+
+def device_fold_kat(kind: str, **fields) -> None:
+    """srr_device_fold_kat (test infrastructure): one launch wrapper of the sample-folding
+    and compaction kernels on host arrays.  Fields are those of srr_fold_kat; arrays are
+    C-contiguous numpy arrays of the field's type, and the "io" ones are written in place.
+    Array sizes are the caller's to get right (include/srr_capi.h gives them per kind)."""
+    L = lib()
+    L.srr_device_fold_kat.argtypes = [ctypes.c_char_p, ctypes.POINTER(FoldKat)]
+    a = FoldKat()
+    names = {f[0] for f in FoldKat._fields_}
+    for k, v in fields.items():
+        if k not in names:
+            raise TypeError(f"srr_fold_kat has no field {k}")
+        if k in _FOLD_KAT_ARRAYS:
+            if v is None:
+                continue
+            if not (isinstance(v, np.ndarray) and v.dtype == _FOLD_KAT_ARRAYS[k] and v.flags.c_contiguous):
+                raise TypeError(f"srr_fold_kat.{k}: a C-contiguous {np.dtype(_FOLD_KAT_ARRAYS[k]).name} array is required")
+            setattr(a, k, v.ctypes.data)
+        else:
+            setattr(a, k, v)
+    _check(L.srr_device_fold_kat(kind.encode(), ctypes.byref(a)))
+
+
 def write_ppm(path: str, nx: int, ny: int, img8: np.ndarray) -> None:
     img8 = np.ascontiguousarray(img8, np.uint8)
     _check(lib().srr_write_ppm(path.encode(), nx, ny, _ptr(img8)))

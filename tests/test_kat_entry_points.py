@@ -56,7 +56,54 @@ def bounce_with_material(m):
     return rec
 
 
+def fold(kind, **over):
+    """A call of srr_device_fold_kat whose arguments are all good (8 rows of 4 samples), then `over`."""
+    rows, spp = 8, 4
+    i32 = lambda *shape, fill=0: np.full(shape, fill, np.int32)
+    f32 = lambda *shape: np.zeros(shape, np.float32)
+    words = dict(window=3, adaptive_fold=3, adaptive_fold_spec=3, aov_fold=8, aov_fold_emission=4, scatter=3).get(kind)
+    a = dict(rows=rows, spp=spp, n_slots=rows, sums=f32(rows, 8), mom=f32(rows, 2), mean=f32(rows, 3), count=i32(rows),
+             keep=np.zeros(rows, np.uint8), live=np.zeros(rows, np.uint8), lvl=i32(4), ctr=np.zeros(2, np.uint64),
+             n_new=4, budget=16, batch_spp=4, min_spp=4, ns=4, n=0, w=spp, s0=0, rel_tol=0.05, abs_eps=1e-3,
+             slot_out=i32(rows), pixel_out=i32(rows), n_out=i32(1), n_shard=rows, n_image=rows, index=i32(rows),
+             emission=f32(rows, 3), image=f32(rows, 3))
+    if words:
+        a["sample"] = f32(rows, 1 if kind == "scatter" else spp, words)
+    if kind == "level_finish":
+        del a["rows"], a["spp"]
+    a.update(over)
+    capi.device_fold_kat(kind, **a)
+
+
+def slots(*v):
+    return np.array(v, np.int32)
+
+
 REFUSED = {
+    "fold: unknown kind": lambda: fold("accumulate"),
+    "fold: active_slot out of range": lambda: fold("adaptive_fold", active_slot=slots(0, 1, 2, 3, 4, 5, 6, 8)),
+    "fold: active_slot negative": lambda: fold("adaptive_fold_spec", active_slot=slots(0, 1, 2, 3, 4, 5, 6, -1)),
+    "fold: active_slot repeated": lambda: fold("compact", active_slot=slots(0, 1, 2, 3, 4, 5, 6, 3)),
+    "fold: n_slots < rows": lambda: fold("adaptive_fold", n_slots=7),
+    "fold: pixels outside the output": lambda: fold("compact", pixels=slots(0, 1, 2, 3, 4, 5, 6, 8)),
+    "fold: index outside the image": lambda: fold("scatter", index=slots(0, 1, 2, 3, 4, 5, 6, 8)),
+    "fold: index negative": lambda: fold("scatter", index=slots(0, 1, 2, 3, 4, 5, 6, -1)),
+    "fold: p0 + np beyond the shard": lambda: fold("aov_fold", p0=1),
+    "fold: emission p0 + np beyond the shard": lambda: fold("aov_fold_emission", p0=1),
+    "fold: negative p0": lambda: fold("aov_fold", p0=-1, n_shard=16),
+    "fold: negative count": lambda: fold("level_finish", count=slots(0, 1, 2, 3, 4, 5, 6, -1)),
+    "fold: count above budget": lambda: fold("level_finish", count=slots(0, 1, 2, 3, 4, 5, 6, 17)),
+    "fold: count above the pass": lambda: fold("adaptive_fold_spec", w=8, s0=4, count=slots(4, 4, 4, 4, 4, 4, 4, 9)),
+    "fold: batch_spp 0": lambda: fold("adaptive_fold_spec", batch_spp=0),
+    "fold: spp_w 0": lambda: fold("window", spp=0),
+    "fold: n_active 0": lambda: fold("adaptive_fold", rows=0),
+    "fold: s0 + spp_w > w": lambda: fold("adaptive_fold_spec", w=7, s0=4),
+    "fold: misalign 4": lambda: fold("window", misalign=4),
+    "fold: ns 0": lambda: fold("finish", ns=0),
+    "fold: n_new 0": lambda: fold("adaptive_fold", n_new=0),
+    "fold: sizes overflow": lambda: fold("window", rows=1 << 24, spp=1 << 16, n_slots=1 << 24),
+    "fold: rows overflow": lambda: fold("compact", rows=(1 << 24) + 1),
+    "fold: no samples": lambda: fold("window", sample=None),
     "unknown name": lambda: function_kat.device_kat("erfc", records("erf")),
     "wrong width": lambda: function_kat.device_kat("erf", records("sphere")),
     "n = 0": lambda: function_kat.device_kat("erf", records("erf", 0)),
@@ -74,6 +121,10 @@ def test_refused_before_the_device_is_touched(what):
 
 
 NO_DEVICE = {
+    "fold window": (lambda: fold("window"), ENOMEM, "device allocation failed"),
+    "fold spec": (lambda: fold("adaptive_fold_spec", w=8, s0=4, count=slots(4, 4, 4, 4, 4, 4, 4, 8)), ENOMEM,
+                  "device allocation failed"),
+    "fold compact": (lambda: fold("compact"), ENOMEM, "device allocation failed"),
     "erf": (lambda: function_kat.device_kat("erf", records("erf")), ENOMEM, "device allocation failed"),
     "sphere": (lambda: function_kat.device_kat("sphere", records("sphere")), ENOMEM, "device allocation failed"),
     "texture_image": (lambda: function_kat.device_kat("texture_image", records("texture_image")), ENOMEM,
